@@ -39,7 +39,7 @@ image:
 	docker build -f deploy/docker/Dockerfile -t $(IMAGE_REPO):$(IMAGE_TAG) .
 
 bench:
-	$(PYTHON) bench.py
+	$(PYTHON) bench.py --full
 
 bench-remote:
 	$(PYTHON) -m flex_gpu_scheduler_amd.tools.remote_bench --matrix

@@ -8,6 +8,12 @@ scheduler shard (its own store + scheduler over `--nodes` 8x MI355X nodes),
 so per-GPU work is fixed as N grows (weak scaling) and `value` is the sum of
 pods/s over ranks divided by the slowest rank's time.
 
+A plain run does only what the headline figure needs: it reads the device
+properties of its MI355X (the synthetic nodes' HBM is sized from them), sets
+up the shard, warms up, times `--steps` steps and prints the result line.
+`--dump-outputs DIR` also writes what the last timed step computed (below).
+Everything else is behind `--full`, and described from here on.
+
 GPU use: every rank probes its own MI355X concurrently with the HIP probes
 (device props, checksum health test, MFMA tile check and the per-partition
 HBM bandwidth table the node agent publishes; untimed) -> `config.gpu_probes`,
@@ -33,7 +39,19 @@ placed on more than one node) and gang_avoidable_split_fraction (split although
 one node could host the gang), and on >= 2 GPUs placement_verdict_<k> and
 placed_busbw_GBps_<k>.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+`--dump-outputs DIR` writes rank 0's gang records of the last timed step (the
+step's `--waves-per-step` waves, gangs in creation order) as float64 arrays,
+one value per gang unless noted: `gang_wave.npy` (wave index within the
+step), `gang_size.npy` (ranks), `gang_nodes.npy` (distinct nodes the ranks
+were bound to), `gang_hostable.npy` (1: one node could take the whole gang
+when its first rank was planned, 0: none could, -1: not planned) and
+`wave_pods.npy` (pods bound, one value per wave). The records' timestamps are
+clock readings, not results, and are left out. The waves depend only on
+`--seed`, `--nodes` and the wave index, and the nodes on `--nodes` and the
+device's HBM size, so two runs with the same arguments schedule identical
+inputs.
 
 Launch: under torch.distributed.run (WORLD_SIZE set) each process is one
 rank. A bare `python bench.py --gpus N` with N > 1 starts its N ranks itself
@@ -146,6 +164,56 @@ def run_nodes(nodes: int, waves: int, seed: int, options: dict, colocation: str 
         shard.close()
 
 
+_RENDER: tuple = ()
+
+
+def _render_wave(i: int) -> tuple[int, list]:
+    from flex_gpu_scheduler_amd.utils.workload import make_wave
+
+    spec, namespace, seed, interleave = _RENDER
+    w = make_wave(spec, i, namespace=namespace, seed=seed)
+    return len(w.pods), w.chunks_json() if interleave else (w.groups_json(), w.pods_json())
+
+
+def render_waves(spec, namespace: str, seed: int, n: int, interleave: bool) -> tuple[list, list]:
+    """Waves 0..n-1 of the shard (`Shard.wave`) as Shard.run takes them: the
+    JSON of each (`prepared`) and a stand-in for the Wave that holds its pod
+    count. Rendering a wave costs more than scheduling it, so up to 16 forked
+    worker processes share the work; the caller has no threads and no GPU
+    runtime yet."""
+    import multiprocessing as mp
+    import types
+
+    global _RENDER
+    _RENDER = (spec, namespace, seed, interleave)
+    workers = min(16, len(os.sched_getaffinity(0)), max(1, n // 4))
+    if workers > 1:
+        with mp.get_context("fork").Pool(workers) as pool:
+            out = pool.map(_render_wave, range(n), chunksize=max(1, min(16, n // (4 * workers))))
+    else:
+        out = [_render_wave(i) for i in range(n)]
+    return [types.SimpleNamespace(pods=range(k)) for k, _ in out], [p for _, p in out]
+
+
+def dump_outputs(out_dir: str, gangs: list[dict], last_step: range, wave_pods: list[int]) -> None:
+    """--dump-outputs: the gang records of the waves `last_step` (the last
+    timed step), gangs in creation order, as DIR/<name>.npy in float64 (the
+    module docstring lists the arrays). A few KB per wave."""
+    import numpy as np
+
+    rows = []
+    for g in gangs:
+        # "<namespace>/s<wave>-<k>-x<size>" or "...-q" (workload.make_wave)
+        wave, k = g["pod_group"].rsplit("/", 1)[-1].split("-")[:2]
+        if int(wave[1:]) in last_step:
+            rows.append((int(wave[1:]) - last_step.start, int(k), g["size"], g["nodes"], g["hostable"]))
+    rows.sort()
+    os.makedirs(out_dir, exist_ok=True)
+    for col, name in ((0, "gang_wave"), (2, "gang_size"), (3, "gang_nodes"), (4, "gang_hostable")):
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.array([r[col] for r in rows], dtype=np.float64))
+    np.save(os.path.join(out_dir, "wave_pods.npy"), np.array(wave_pods, dtype=np.float64))
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--gpus", type=int, default=1)
@@ -153,6 +221,12 @@ def main() -> int:
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--nodes", type=int, default=64, help="8x MI355X nodes per scheduler shard")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything that is not the headline figure (untimed): GPU health, MFMA and HBM "
+                         "bandwidth probes, cache check, placement validation, open-loop search, 1,024-node run, "
+                         "service mode, BASELINE scenarios; the --no-* options below pick among them")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write rank 0's gang records of the last timed step as DIR/<name>.npy")
     ap.add_argument("--no-gpu-probe", action="store_true")
     ap.add_argument("--trace", default="", help="write a Chrome trace of rank 0's timed steps")
     ap.add_argument("--sched-options", default="{}",
@@ -188,23 +262,39 @@ def main() -> int:
     from flex_gpu_scheduler_amd.utils.benchrun import Shard, gang_latency_summary, gang_split_summary
     from flex_gpu_scheduler_amd.utils.workload import ClusterSpec
 
+    # Pre-render every wave's JSON (data preparation, outside the timed
+    # region), first of all: the worker processes are forked before this one
+    # has loaded torch or HIP or started a thread. A wave depends on the node
+    # count, not on the HBM size the probe reports below.
+    rank = int(os.environ.get("RANK", "0"))
+    wps = max(1, args.waves_per_step)
+    n_waves = (args.warmup + args.steps) * wps
+    # Each chunk's PodGroups are written just before its pods (as job
+    # submitters do), unless XSCHED_BENCH_INTERLEAVE=0 (all PodGroups first;
+    # A/B runs).
+    interleave = os.environ.get("XSCHED_BENCH_INTERLEAVE", "1") != "0"
+    waves, prepared = render_waves(ClusterSpec(nodes=args.nodes), f"bench-r{rank}", args.seed + 7919 * rank,
+                                   n_waves + (1 if args.full else 0), interleave)  # --full: +1, the untimed check wave
+
     ctx = init_distributed(want_cuda=True)
     extras: dict = {}
     hbm_gib = 288
+    probe_row = None
     if ctx.cuda and not args.no_gpu_probe:
         from flex_gpu_scheduler_amd.ops.hip_probe import probe
 
         pr = probe()
         props = pr.props(ctx.local_rank)
+        hbm_gib = max(1, int(props["totalGlobalMem"]) // (1 << 30))
+        extras["gpu"] = {"name": props.get("gcnArchName"), "computeUnits": props.get("computeUnits"),
+                         "hbm_gib": hbm_gib}
+    if ctx.cuda and not args.no_gpu_probe and args.full:
         health = pr.health(ctx.local_rank)
         if not health["healthy"]:
             raise SystemExit(f"GPU {ctx.local_rank} failed the checksum health test: {health}")
         mfma = pr.mfma_check(ctx.local_rank)
         if not mfma["healthy"]:
             raise SystemExit(f"GPU {ctx.local_rank} failed the MFMA tile check: {mfma}")
-        hbm_gib = max(1, int(props["totalGlobalMem"]) // (1 << 30))
-        extras["gpu"] = {"name": props.get("gcnArchName"), "computeUnits": props.get("computeUnits"),
-                         "hbm_gib": hbm_gib}
         # The node agent's per-GPU table, measured on every rank's own GPU at
         # once (untimed); a failure is reported, not fatal.
         row = {"rank": ctx.rank, "local_rank": ctx.local_rank, "healthy": True, "mfma_ok": True,
@@ -214,9 +304,7 @@ def main() -> int:
         except Exception as e:  # noqa: BLE001
             row["hbm"] = {"error": f"{type(e).__name__}: {e}"}
         probe_row = row
-    else:
-        probe_row = None
-    probe_rows = ctx.gather(probe_row)
+    probe_rows = ctx.gather(probe_row) if args.full else [None]
     if ctx.rank == 0 and any(probe_rows):
         extras["gpu_probes"] = [r for r in probe_rows if r]
 
@@ -237,15 +325,6 @@ def main() -> int:
 
     shard = Shard(spec, namespace=f"bench-r{ctx.rank}", seed=args.seed + 7919 * ctx.rank,
                   options=json.loads(args.sched_options), config=flagship_config(gang_colocation=args.gang_colocation))
-    # Pre-render every wave's JSON (data preparation, outside the timed region).
-    wps = max(1, args.waves_per_step)
-    n_waves = (args.warmup + args.steps) * wps
-    waves = [shard.wave(i) for i in range(n_waves + 1)]  # +1: the untimed check wave
-    # Each chunk's PodGroups are written just before its pods (as job
-    # submitters do), unless XSCHED_BENCH_INTERLEAVE=0 (all PodGroups first;
-    # A/B runs).
-    interleave = os.environ.get("XSCHED_BENCH_INTERLEAVE", "1") != "0"
-    prepared = [w.chunks_json() if interleave else (w.groups_json(), w.pods_json()) for w in waves]
 
     progress(f"rank {ctx.rank}: warm-up ({args.warmup * wps} waves)")
     for i in range(args.warmup * wps):
@@ -272,21 +351,25 @@ def main() -> int:
     if args.trace and ctx.rank == 0:
         with open(args.trace, "w") as f:
             f.write(shard.sched.trace_json())
+    if args.dump_outputs and ctx.rank == 0:
+        last = range(n_waves - wps if args.steps > 0 else n_waves, n_waves)
+        dump_outputs(args.dump_outputs, gangs, last, [len(waves[i].pods) for i in last])
 
-    # Untimed: one more wave, and once it is bound the cache debugger
+    # Untimed (--full): one more wave, and once it is bound the cache debugger
     # compares the cache with the listers and re-derives every node's
     # accounting (resources, GPU ledger, gang counts) from its pods.
     check: dict = {}
-    shard.run(waves[-1], prepared=prepared[-1], check_cache=check)
-    extras["cache_check"] = {"clean": bool(check.get("clean")), "assumed": check.get("assumed"),
-                             "accounting_mismatches": len(check.get("accounting", []))}
+    if args.full:
+        shard.run(waves[-1], prepared=prepared[-1], check_cache=check)
+        extras["cache_check"] = {"clean": bool(check.get("clean")), "assumed": check.get("assumed"),
+                                 "accounting_mismatches": len(check.get("accounting", []))}
     t_max = ctx.all_max(elapsed)
     pods_total = ctx.all_sum(float(pods))
     all_gangs = [g for part in ctx.gather(gangs) for g in part]
     per_rank = ctx.gather(round(pods / t_rank, 1) if t_rank > 0 else 0.0)
     del waves, prepared
     stats = shard.sched.stats()
-    if not args.no_placement and (ctx.distributed or ctx.cuda):
+    if args.full and not args.no_placement and (ctx.distributed or ctx.cuda):
         # Untimed: gangs placed on the live node, resolved by the device
         # plugin, all-reduced on exactly those GPUs (parallel/placement.py).
         # A failure there is reported, not fatal to the headline line. The
@@ -313,7 +396,7 @@ def main() -> int:
         return pin_cpus(args.cpus, 0, order=ranked_domains())
 
     progress(f"timed region done: {pods / t_rank if t_rank > 0 else 0:.0f} pods/s on rank 0")
-    if not args.no_open_loop:
+    if args.full and not args.no_open_loop:
         progress("open-loop capacity search")
         # Untimed: Poisson gang arrivals at 50% / 90% of this shard's measured
         # open-loop capacity, gang types interleaved, held then deleted
@@ -376,7 +459,7 @@ def main() -> int:
                                                                     for r in loads)
     shard.close()
 
-    if args.nodes1024_waves > 0:
+    if args.full and args.nodes1024_waves > 0:
         progress("1,024-node run")
         # Untimed: the same workload on one 1,024-node shard (12k pods/wave).
         repin()
@@ -391,7 +474,7 @@ def main() -> int:
                 sum(v["avoidable"] for v in sp.values()) / max(1, n_multi), 6)
         except Exception as e:  # noqa: BLE001
             extras["nodes1024"] = {"error": f"{type(e).__name__}: {e}"}
-    if not args.no_service_mode:
+    if args.full and not args.no_service_mode:
         progress("service mode")
         # Untimed: the deployable shape — scheduler and API server in separate
         # processes over loopback HTTP (tools/remote_bench.py): steady state
@@ -428,7 +511,7 @@ def main() -> int:
             extras["service_mode"] = {"error": f"{type(e).__name__}: {e}"}
 
     value = pods_total / t_max if t_max > 0 else 0.0
-    if not args.no_scenarios:
+    if args.full and not args.no_scenarios:
         # The five BASELINE.json configurations, each with its placement check
         # (outside the timed region; utils/scenarios.py).
         from flex_gpu_scheduler_amd.utils.scenarios import run_all

@@ -19,17 +19,17 @@ for step in "$@"; do
     pytest) timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread \
               > "$OUT/pytest_gpu.txt" 2>&1 ;;
     smoke) timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.txt" 2>&1 ;;
-    bench) timeout -k 10 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench1.json" \
+    bench) timeout -k 10 500 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > "$OUT/bench1.json" \
              2> "$OUT/bench1.err" ;;
     bench3) for i in 1 2 3; do
-              timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --no-scenarios --no-placement \
+              timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --no-scenarios --no-placement \
                 --no-service-mode > "$OUT/bench64_$i.json" 2> "$OUT/bench64_$i.err" || exit $?
             done ;;
     bench_r3shape)
       # The round-3 measurement shape (20 timed single-wave steps) next to the
       # default 16-wave steps, same tree and box.
       for i in 1 2; do
-        timeout -k 10 200 python3 bench.py --steps 20 --warmup 5 --waves-per-step 1 --no-scenarios --no-placement \
+        timeout -k 10 200 python3 bench.py --full --steps 20 --warmup 5 --waves-per-step 1 --no-scenarios --no-placement \
           --no-service-mode --no-open-loop > "$OUT/bench_r3shape_$i.json" 2> "$OUT/bench_r3shape_$i.err" || exit $?
       done ;;
     benchab)
@@ -38,7 +38,7 @@ for step in "$@"; do
       var=${AB_VAR:-XSCHED_PARSE_POOL}
       for i in 1 2; do
         for v in ${AB_VALUES:-0 1}; do
-          env "$var=$v" timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --no-scenarios --no-placement \
+          env "$var=$v" timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --no-scenarios --no-placement \
             --no-service-mode > "$OUT/benchab_${var}_${v}_$i.json" 2> "$OUT/benchab_${var}_${v}_$i.err" || exit $?
         done
       done ;;
@@ -48,9 +48,9 @@ for step in "$@"; do
       for i in 1 2 3; do
         for t in abtree .; do
           which=$( [ "$t" = . ] && echo cur || echo old )
-          (cd "$t" && timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --no-scenarios --no-placement \
+          (cd "$t" && timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --no-scenarios --no-placement \
             --no-service-mode) > "$OUT/treeab_${which}_64_$i.json" 2> "$OUT/treeab_${which}_64_$i.err" || exit $?
-          (cd "$t" && timeout -k 10 300 python3 bench.py --nodes 1024 --steps 4 --warmup 1 --no-scenarios --no-placement \
+          (cd "$t" && timeout -k 10 300 python3 bench.py --full --nodes 1024 --steps 4 --warmup 1 --no-scenarios --no-placement \
             --no-service-mode --no-open-loop) > "$OUT/treeab_${which}_1024_$i.json" 2> "$OUT/treeab_${which}_1024_$i.err" || exit $?
         done
       done ;;
@@ -65,16 +65,16 @@ for step in "$@"; do
       for i in 1 2; do
         for t in abtree .; do
           which=$( [ "$t" = . ] && echo cur || echo old )
-          (cd "$t" && timeout -k 10 400 python3 bench.py --nodes 1024 --steps 4 --warmup 1 --no-scenarios \
+          (cd "$t" && timeout -k 10 400 python3 bench.py --full --nodes 1024 --steps 4 --warmup 1 --no-scenarios \
             --no-placement --no-service-mode --nodes1024-waves 0) > "$OUT/treeab1024ol_${which}_$i.json" \
             2> "$OUT/treeab1024ol_${which}_$i.err" || exit $?
         done
       done ;;
     nodes1024_3) for i in 1 2 3; do
-                   timeout -k 10 400 python3 bench.py --nodes 1024 --steps 4 --warmup 1 --no-scenarios --no-placement \
+                   timeout -k 10 400 python3 bench.py --full --nodes 1024 --steps 4 --warmup 1 --no-scenarios --no-placement \
                      --no-service-mode > "$OUT/bench_nodes_1024_$i.json" 2> "$OUT/bench_nodes_1024_$i.err" || exit $?
                  done ;;
-    nodes1024) timeout -k 10 400 python3 bench.py --nodes 1024 --steps 4 --warmup 1 --no-scenarios --no-placement \
+    nodes1024) timeout -k 10 400 python3 bench.py --full --nodes 1024 --steps 4 --warmup 1 --no-scenarios --no-placement \
                  --no-service-mode > "$OUT/bench_nodes_1024.json" 2> "$OUT/bench_nodes_1024.err" ;;
     pmc) OUTDIR="$OUT" bash scripts/pmc_round.sh ;;
     probe_timing) OUTDIR="$OUT" bash scripts/probe_timing.sh ;;
@@ -178,7 +178,7 @@ for step in "$@"; do
       # Kernel trace + per-kernel stats of one short bench run (the probe,
       # health, MFMA and placement kernels on the GPU path).
       timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/rocprof_bench" -o bench -- \
-        python3 bench.py --steps 5 --warmup 1 --no-open-loop --no-scenarios --no-service-mode \
+        python3 bench.py --full --steps 5 --warmup 1 --no-open-loop --no-scenarios --no-service-mode \
         > "$OUT/rocprof_bench.log" 2>&1 ;;
     *) echo "unknown step $step"; exit 2 ;;
   esac

@@ -24,7 +24,7 @@ for s in ${STEPS:-pytest sched5000 calib pmc}; do
                  --only PreemptionBasic CapacityScheduling-Reclaim --cpus l3 ;;
     calib) OUTDIR="$OUT" step calib 500 bash scripts/pmc_calibrate.sh ;;
     pmc) OUTDIR="$OUT" step pmc 450 bash scripts/pmc_round.sh ;;
-    bench) step bench 600 python -u bench.py --steps 20 --warmup 3 ;;
+    bench) step bench 600 python -u bench.py --full --steps 20 --warmup 3 ;;
   esac
 done
 echo "[session] done" | tee -a "$OUT/session.log"

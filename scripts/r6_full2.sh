@@ -1,5 +1,6 @@
 # One full default bench.py run (the driver's N=1 command) with its stderr progress.
 set -e
-mkdir -p gpurun_out/${TAG:-r6ae}
-timeout -k 10 1000 python bench.py > gpurun_out/${TAG:-r6ae}/bench1.json 2> gpurun_out/${TAG:-r6ae}/bench1.err
-tail -c 300 gpurun_out/${TAG:-r6ae}/bench1.json
+OUT=${OUT:-out}/${TAG:-r6ae}
+mkdir -p $OUT
+timeout -k 10 1000 python bench.py --full > $OUT/bench1.json 2> $OUT/bench1.err
+tail -c 300 $OUT/bench1.json

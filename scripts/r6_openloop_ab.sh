@@ -5,7 +5,7 @@ mkdir -p $OUT
 for i in 1 2; do
   for mode in child inproc; do
     flag=""; [ $mode = inproc ] && flag="--open-loop-in-process"
-    timeout -k 10 400 python bench.py $flag --no-service-mode --no-scenarios --no-placement --nodes1024-waves 0 > $OUT/ol_${mode}_$i.json 2>> $OUT/ol.err
+    timeout -k 10 400 python bench.py --full $flag --no-service-mode --no-scenarios --no-placement --nodes1024-waves 0 > $OUT/ol_${mode}_$i.json 2>> $OUT/ol.err
     python -c "
 import json; d=json.load(open('$OUT/ol_${mode}_$i.json')); c=d['config']; ol=c['gang_admit_open_loop']
 print('$mode', $i, d['value'], c['open_loop_capacity_pods_per_s'], ol['load_90']['all_gangs']['p99_create_to_bound_ms'], c.get('deny_mode_open_loop_p99_create_to_bound_ms'), c.get('deny_mode_denied_gang_fraction'))

@@ -49,7 +49,7 @@ def test_bench_launches_its_own_ranks():
     env = dict(os.environ, PYTHONPATH=ROOT, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="", OMP_NUM_THREADS="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--nodes", "8",
+    cmd = [sys.executable, "bench.py", "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--nodes", "8",
            "--waves-per-step", "2", "--no-gpu-probe", "--no-scenarios", "--no-service-mode", "--cpus", "none"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-4000:]
@@ -91,7 +91,7 @@ def test_bench_eight_ranks_self_launched_gloo():
     env = dict(os.environ, PYTHONPATH=ROOT, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="", OMP_NUM_THREADS="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, "bench.py", "--gpus", "8", "--steps", "1", "--warmup", "1", "--nodes", "4",
+    cmd = [sys.executable, "bench.py", "--full", "--gpus", "8", "--steps", "1", "--warmup", "1", "--nodes", "4",
            "--waves-per-step", "1", "--no-gpu-probe", "--no-scenarios", "--no-open-loop", "--no-service-mode",
            "--cpus", "none"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)

@@ -254,6 +254,8 @@ def test_concurrent_gangs_split_only_when_no_node_could_host_them():
                 total += k
             groups = [submit(store, f"t{trial}-g{i}", k) for i, k in enumerate(sizes)]
             assert wait_for(lambda: all(all(node_of(store, g)) for g in groups), timeout=20.0), sizes
+            # A gang's record is completed just after its last bind shows in the store.
+            assert wait_for(lambda: len(s.gang_records()) >= len(groups), timeout=20.0), sizes
             recs = {r["pod_group"]: r for r in s.gang_records()}
             for i, g in enumerate(groups):
                 r = recs.get(f"default/t{trial}-g{i}")

@@ -112,8 +112,9 @@ def test_smoke_entry():
 def test_bench_one_gpu_json_contract():
     # The open-loop search, scenarios and service mode are exercised by the
     # bench runs themselves (and CPU tests); here the line and the placement.
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--nodes", "16", "--no-open-loop",
-                        "--no-scenarios", "--no-service-mode"], cwd=ROOT, capture_output=True, text=True, timeout=380)
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1", "--nodes", "16",
+                        "--no-open-loop", "--no-scenarios", "--no-service-mode"], cwd=ROOT, capture_output=True,
+                       text=True, timeout=380)
     assert r.returncode == 0, r.stderr[-4000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
