@@ -177,7 +177,7 @@ class Plugin {
   virtual Status pre_bind(CycleState& s, const PodPtr& p, const std::string& node) { return {}; }
   virtual Status bind(CycleState& s, const PodPtr& p, const std::string& node) { return Status(Code::Skip); }
   virtual void post_bind(CycleState& s, const PodPtr& p, const std::string& node) {}
-  // Equivalence-cache contract (scheduler.cc eq-cache). True when this
+  // Equivalence-cache contract (scheduler/filter_walk.cc eq_entry). True when this
   // plugin's Filter verdict / raw Score for `p` on a node is a function of the
   // pod's template (Pod::template_hash) and that NodeInfo's content (its
   // generation) alone, for the snapshot's node epoch. Plugins that read

@@ -30,6 +30,7 @@
 #include "common/parallel.h"
 #include "framework/framework.h"
 #include "scheduler/cache.h"
+#include "scheduler/executor.h"
 #include "scheduler/extender.h"
 #include "scheduler/gang_placement.h"
 #include "scheduler/informers.h"
@@ -65,62 +66,6 @@ class StoreClient : public ApiClient {
   std::mutex events_mu_;
   std::unordered_map<std::string, Recent> recent_;
   size_t recent_sweep_at_ = 4096;
-};
-
-// Bounded worker pool for binding cycles.
-class Executor {
- public:
-  explicit Executor(int threads);
-  ~Executor();
-  void submit(std::function<void()> fn);
-  // While a Batch is alive, submit() calls from its thread to this executor
-  // are collected and handed over under one lock with one wake-up when it
-  // ends (a gang's Allows fire k binding cycles from one Permit call).
-  class Batch {
-   public:
-    explicit Batch(Executor& e);
-    ~Batch();
-    Batch(const Batch&) = delete;
-    Batch& operator=(const Batch&) = delete;
-
-   private:
-    friend class Executor;
-    Executor& e_;
-    Batch* prev_;
-    std::vector<std::function<void()>> fns_;
-  };
-  void stop();
-  size_t pending() const;
-  // A task about to block for a long time (VolumeBinding's PreBind waiting
-  // for the PV controller) brackets the wait with these, so blocked tasks
-  // never take the pool's last runnable workers (BlockingScope below).
-  void enter_blocking();
-  void exit_blocking();
-  size_t threads() const;
-
- private:
-  // A worker that finishes a task spins briefly on `queued_` before it
-  // sleeps, and submit() skips the futex wake while a spinning worker can
-  // take the task: under load the scheduling thread hands bindings over
-  // without a syscall.
-  static constexpr int64_t kSpinNs = 30'000;  // XSCHED_BIND_SPIN_NS overrides (A/B runs)
-  static constexpr int kMaxSpinners = 2;
-  int64_t spin_ns_ = kSpinNs;
-  bool try_pop(std::function<void()>& fn);  // under mu_
-  void spawn_locked();
-  static constexpr size_t kMaxThreads = 1024;
-  int base_ = 1;
-  int blocked_ = 0;  // under mu_
-  mutable AdaptiveMutex mu_;
-  std::condition_variable_any cv_;
-  std::deque<std::function<void()>> q_;
-  std::vector<std::thread> threads_;
-  bool stop_ = false;
-  std::atomic<int> busy_{0};
-  std::atomic<int> queued_{0};
-  std::atomic<int> spinners_{0};
-  int waiters_ = 0;  // workers in cv_.wait (under mu_)
-  int wakes_ = 0;    // notifications sent and not yet consumed by a waking worker (under mu_)
 };
 
 struct SchedulerOptions {
@@ -262,70 +207,65 @@ class Scheduler {
   double loop_age_seconds() const;
 
  private:
-  struct ScheduleResult {
-    std::string host;
-    int evaluated = 0, feasible = 0;
-  };
   struct Diagnosis {
     NodeStatusMap node_to_status;
     std::set<std::string> unschedulable_plugins;
   };
-  // Equivalence cache for one (profile, pod template): a slot per snapshot
-  // node position, valid for one node epoch (node set / Node objects).
-  struct EqEntry {
-    uint64_t epoch = 0;
-    EqTable table;
-    // The last serial Filter scan of this template (find_nodes_that_fit):
-    // per scan offset from `start`, the node version it saw and its verdict.
-    struct ScanMemo {
-      bool valid = false;
-      int start = 0, n = 0, to_find = 0, processed = 0;
-      uint64_t epoch = 0;
-      std::vector<int64_t> gens;
-      std::vector<char> ok;
-    } scan;
-  };
-  EqEntry* eq_entry(Framework& fw, const Pod& p);
-  void release_retired();
-  std::mutex retired_spare_mu_;
-  std::vector<std::vector<NodeInfoPtr>> retired_spare_;  // emptied retired batches, capacity kept
-  std::vector<Status> fail_buf_;  // find_nodes_that_fit scratch (scheduling thread)
-  std::vector<char> nom_mark_;    // nodes with nominated pods, per snapshot position (refresh_nom_mark)
-  std::vector<const std::vector<PodPtr>*> nom_list_;  // ... and their lists in the view (valid for the cycle)
-  std::vector<std::string> nom_changed_;
-  const NominatedMap* nom_src_ = nullptr;  // the view nom_mark_ describes
-  uint64_t nom_epoch_ = UINT64_MAX;
-  bool nom_mark_valid_ = false;
-  void refresh_nom_mark(const NominatedMap* view);
-  std::vector<const Status*> fail_ptr_;
-  static constexpr size_t kInformerWindow = 64;
-  size_t informer_window_ = kInformerWindow;  // XSCHED_INFORMER_WINDOW overrides (A/B runs)
-  ParallelSite filter_site_;  // inline-vs-parallel cost model of Filter
-  // Per-profile metric cells of the scheduling cycle, cached per metrics
-  // epoch (scheduling thread / sched_mu_ only).
-  struct CycleMetrics {
-    uint64_t epoch = ~0ULL;
-    Histogram* algo = nullptr;
-    Histogram* e2e = nullptr;
-    Histogram* attempt[3] = {};  // scheduled, unschedulable, error
-    Counter* attempts[3] = {};
-  };
-  std::unordered_map<const Framework*, CycleMetrics> cycle_metrics_;
-  CycleMetrics& cycle_metrics(const Framework& fw);
-  // Binding-cycle histograms shared by the binder threads: looked up once
-  // per metrics epoch (under bind_metrics_mu_), then read lock-free. Cells
-  // are never freed (Metrics::reset retires them), so a stale pointer read
-  // across a reset only loses that observation.
-  struct BindMetrics {
-    std::atomic<uint64_t> epoch{~0ULL};
-    std::atomic<Histogram*> binding{nullptr}, attempts{nullptr};
-    std::atomic<Histogram*> permit_wait[2] = {nullptr, nullptr};  // Success, Unschedulable
-    std::atomic<Histogram*> pod_duration[8] = {};                  // attempts=1..8
-  };
-  BindMetrics bind_metrics_;
-  std::mutex bind_metrics_mu_;
-  BindMetrics& bind_metrics();
 
+  // ---- scheduler.cc: construction, start/stop, the scheduling loop ----
+  void scheduling_loop();
+  bool responsible_for(const Pod& p) const;
+
+  std::shared_ptr<ObjectStore> store_;
+  std::shared_ptr<Clock> clock_;
+  SchedulerOptions opts_;
+  std::unique_ptr<TimerService> timers_;
+  std::unique_ptr<Parallelizer> parallelizer_;
+  // Informer windows parse their pods' JSON on a few helpers ("xs-parse").
+  std::unique_ptr<Parallelizer> parse_pool_;
+  ParallelSite parse_site_;
+  std::unique_ptr<Metrics> metrics_;
+  std::unique_ptr<SchedulerCache> cache_;
+  std::unique_ptr<Informers> informers_;
+  std::unique_ptr<Nominator> nominator_;
+  std::unique_ptr<SchedulingQueue> queue_;
+  std::shared_ptr<ApiClient> client_;
+  ExtenderList extenders_;
+  // The informer store's objects, as extenders and plugins ask for them.
+  const ObjectLookup store_lookup_ = [this](const std::string& kind, const std::string& ns, const std::string& name) {
+    return store_->get(kind, ns, name);
+  };
+  std::shared_ptr<const GpuNames> gpu_names_;  // from the profiles' FlexGPU args
+  std::vector<std::unique_ptr<WaitingPods>> waiting_;
+  std::vector<std::unique_ptr<GangPlacement>> gang_placements_;  // one per profile (Handle::gangs)
+  std::vector<std::unique_ptr<Framework>> frameworks_;
+  std::unordered_map<std::string, Framework*> by_name_;
+  std::unique_ptr<Executor> binder_;
+  // FailedScheduling events: one FIFO worker, off the scheduling loop.
+  std::unique_ptr<Executor> status_writer_;
+  Snapshot snapshot_;
+  Tracer tracer_;
+  WatcherPtr watcher_;
+  std::vector<std::string> plugin_kinds_;
+
+  std::thread informer_thread_, sched_thread_;
+  std::atomic<bool> running_{false};
+  std::mutex sched_mu_;  // serializes scheduling cycles (loop vs schedule_one)
+  std::atomic<int> inflight_{0};
+  std::atomic<int> in_cycle_{0};
+  std::atomic<int64_t> loop_tick_us_{0};  // RealClock time of the last loop iteration
+  std::mt19937_64 rng_;
+  std::vector<uint64_t> timer_ids_;
+  // Stats counters: relaxed atomics, bumped by the scheduling, binding and
+  // informer threads without a shared lock.
+  struct Counters {
+    std::atomic<uint64_t> attempts{0}, scheduled{0}, unschedulable{0}, errors{0}, bound{0}, bind_failures{0};
+    std::atomic<uint64_t> preemption_attempts{0}, eq_filter_hits{0}, eq_filter_misses{0};
+    std::atomic<uint64_t> scan_memo_served{0}, scan_memo_mismatches{0};
+  } cnt_;
+  std::atomic<uint64_t> bound_total_{0};  // bound pods, released for wait_bound (cnt_.bound counts the same)
+
+  // ---- scheduler_events.cc: informer ingestion ----
   void informer_loop();
   void handle_event(const WatchEvent& ev);
   void handle_pod_event(const WatchEvent& ev);
@@ -350,35 +290,124 @@ class Scheduler {
   }
   void apply_pod_update(const WatchEvent& ev, const PodPtr& np, PodPtr old);
   void handle_node_event(const WatchEvent& ev);
-  void scheduling_loop();
-  void schedule_cycle(const QueuedPodInfoPtr& qpi);
+  static constexpr size_t kInformerWindow = 64;
+  size_t informer_window_ = kInformerWindow;  // XSCHED_INFORMER_WINDOW overrides (A/B runs)
+
+  // ---- gang_records.cc: gang records and denials ----
+  void note_gang_enqueue(const Pod& p, int64_t t);
+  void note_gang_event(const Pod& p, bool bound);
+  void note_gang_planned(const Pod& p, bool hostable);
+  void note_gang_denied(const Pod& p, const char* why);
+  mutable std::mutex stats_mu_;  // gang records and denials, condition memo
+  std::unordered_map<std::string, GangRecord> gangs_;  // open groups
+  // Completed gangs until a caller collects them: a deque, so the push on a
+  // binding thread (under stats_mu_) never moves the records already there
+  // (a benchmark collects ~10^5 of them at once).
+  std::deque<GangRecord> gang_done_;
+  std::unordered_map<int, Histogram*> gang_hist_;  // xsched_gang_admit_seconds{size} (under stats_mu_)
+  uint64_t gang_hist_epoch_ = ~0ULL;
+  static constexpr size_t kMaxGangDenials = 256;
+  std::vector<GangDenial> gang_denials_;
+  uint64_t gang_denials_total_ = 0;
+  std::atomic<uint64_t> gang_parks_total_{0};
+
+  // ---- filter_walk.cc: PreFilter and the Filter walk ----
+  // Equivalence cache for one (profile, pod template): a slot per snapshot
+  // node position, valid for one node epoch (node set / Node objects).
+  struct EqEntry {
+    uint64_t epoch = 0;
+    EqTable table;
+    // The last serial Filter scan of this template (find_nodes_that_fit):
+    // per scan offset from `start`, the node version it saw and its verdict.
+    struct ScanMemo {
+      bool valid = false;
+      int start = 0, n = 0, to_find = 0, processed = 0;
+      uint64_t epoch = 0;
+      std::vector<int64_t> gens;
+      std::vector<char> ok;
+    } scan;
+  };
+  EqEntry* eq_entry(Framework& fw, const Pod& p);
+  void refresh_nom_mark(const NominatedMap* view);
   // `feasible_pos` (optional) receives each feasible node's snapshot position.
   Status find_nodes_that_fit(Framework& fw, CycleState& s, const Pod& p, Diagnosis& d, NodeList& feasible,
                              EqEntry* eq = nullptr, bool full_diagnosis = false, std::vector<int>* feasible_pos = nullptr);
   int num_feasible_nodes_to_find(Framework& fw, int n) const;
-  // Filter over a PreFilter node set given as a short position list (the
-  // nodes hosting a gang): only those nodes are evaluated; the others get
-  // the set's `excluded` verdict in the diagnosis.
-  Status filter_listed(Framework& fw, CycleState& s, const Pod& p, Diagnosis& d, NodeList& feasible, EqEntry* eq,
-                       const NodeRestriction& rs, std::vector<int>* feasible_pos, bool ext);
+  struct FilterPass;  // one pass of find_nodes_that_fit over the snapshot
+  void diagnose_every_node(Diagnosis& d, const Status& st, const std::vector<std::pair<int, const Status*>>* own = nullptr);
+  Status extender_tail(const Pod& p, int n, NodeList& feasible, std::vector<int>* feasible_pos, Diagnosis& d, bool ext);
+  // Filter scratch reused across cycles (scheduling thread only).
+  std::vector<Status> fail_buf_;
+  std::vector<const Status*> fail_ptr_;
+  std::vector<const NodeInfo*> found_buf_;
+  std::vector<int> found_pos_buf_;
+  std::vector<char> nom_mark_;    // nodes with nominated pods, per snapshot position (refresh_nom_mark)
+  std::vector<const std::vector<PodPtr>*> nom_list_;  // ... and their lists in the view (valid for the cycle)
+  std::vector<std::string> nom_changed_;
+  const NominatedMap* nom_src_ = nullptr;  // the view nom_mark_ describes
+  uint64_t nom_epoch_ = UINT64_MAX;
+  bool nom_mark_valid_ = false;
+  ParallelSite filter_site_;  // inline-vs-parallel cost model of Filter
+  int next_start_node_ = 0;
+  // Node window shared by consecutive members of one gang and template
+  // (find_nodes_that_fit; scheduling thread only).
+  uint64_t window_gang_ = 0, window_tmpl_ = 0;
+  int window_start_ = 0, window_n_ = -1;
+  std::unordered_map<Framework*, std::unordered_map<uint64_t, std::unique_ptr<EqEntry>>> eq_;  // scheduling thread only
+
+  // ---- scheduler_extenders.cc: Filter and Prioritize calls to the HTTP extenders ----
   // findNodesThatPassExtenders: interested filter extenders narrow
   // `feasible` (and `pos`) in order; their failures join the diagnosis.
   Status run_extender_filters(const Pod& p, NodeList& feasible, std::vector<int>* pos, Diagnosis& d);
+  bool extenders_interested(const Pod& p) const;
+  Json pod_object(const Pod& p) const;  // the informer store's Pod (what extenders receive)
   // Extender priorities x weight x (MaxNodeScore / MaxExtenderPriority)
   // added to the plugin totals; errors are ignored as upstream does.
   void add_extender_scores(const Pod& p, const NodeList& feasible, std::vector<NodeScore>& scores,
                            Json* breakdown = nullptr);
-  bool extenders_interested(const Pod& p) const;
-  Json pod_object(const Pod& p) const;  // the informer store's Pod (what extenders receive)
+
+  // ---- schedule_cycle.cc: scheduling cycle, binding cycle, failures ----
+  void schedule_cycle(const QueuedPodInfoPtr& qpi);
+  void activate_stashed(PodsToActivate& stash);
+  // Score of the feasible nodes (after PreScore) as the scheduling cycle runs
+  // it: node-local raw scores come from the template's equivalence slots
+  // (`eq` may be null; `positions`: the nodes' snapshot positions).
+  Status score_feasible(Framework& fw, CycleState& s, const Pod& p, const NodeList& feasible, const int* positions,
+                        EqEntry* eq, std::vector<NodeScore>& scores);
   // Index of the highest total (reservoir-sampled among ties).
   size_t select_host(const std::vector<NodeScore>& scores);
   // Cycle scratch reused across cycles (scheduling thread only).
   NodeList feasible_buf_;
-  std::vector<const NodeInfo*> found_buf_;
-  std::vector<int> found_pos_buf_;
   std::vector<int> feasible_pos_buf_;
   std::vector<NodeScore> scores_buf_;
   EqScoreCache esc_buf_;
+  void release_retired();
+  std::mutex retired_spare_mu_;
+  std::vector<std::vector<NodeInfoPtr>> retired_spare_;  // emptied retired batches, capacity kept
+  // Per-profile metric cells of the scheduling cycle, cached per metrics
+  // epoch (scheduling thread / sched_mu_ only).
+  struct CycleMetrics {
+    uint64_t epoch = ~0ULL;
+    Histogram* algo = nullptr;
+    Histogram* e2e = nullptr;
+    Histogram* attempt[3] = {};  // scheduled, unschedulable, error
+    Counter* attempts[3] = {};
+  };
+  std::unordered_map<const Framework*, CycleMetrics> cycle_metrics_;
+  CycleMetrics& cycle_metrics(const Framework& fw);
+  // Binding-cycle histograms shared by the binder threads: looked up once
+  // per metrics epoch (under bind_metrics_mu_), then read lock-free. Cells
+  // are never freed (Metrics::reset retires them), so a stale pointer read
+  // across a reset only loses that observation.
+  struct BindMetrics {
+    std::atomic<uint64_t> epoch{~0ULL};
+    std::atomic<Histogram*> binding{nullptr}, attempts{nullptr};
+    std::atomic<Histogram*> permit_wait[2] = {nullptr, nullptr};  // Success, Unschedulable
+    std::atomic<Histogram*> pod_duration[8] = {};                  // attempts=1..8
+  };
+  BindMetrics bind_metrics_;
+  std::mutex bind_metrics_mu_;
+  BindMetrics& bind_metrics();
   // Everything the binding cycle of one assumed pod needs, in one heap
   // object: the Permit continuation and the binder task capture only this
   // pointer (fits std::function's inline buffer, no per-closure allocation).
@@ -401,78 +430,14 @@ class Scheduler {
   };
   static void run_bind_task(BindTask* t);
   void binding_cycle(const BindTask& t, const Status& permit_status);
+  // An assumed pod fails after Reserve: Unreserve, forget it in the cache,
+  // bump `counter`, requeue it (handle_failure, with the failed plugin).
+  // `freed`: also tell queued pods and plugins that its resources came back.
+  void fail_assumed(Framework& fw, CycleState& s, const QueuedPodInfoPtr& qpi, const PodPtr& assumed, const Status& st,
+                    const std::string& reason, int64_t cycle, std::atomic<uint64_t>& counter, bool freed);
   void handle_failure(Framework& fw, const QueuedPodInfoPtr& qpi, const Status& st, const std::string& reason,
                       const std::string& nominated, int64_t cycle, const std::set<std::string>& plugins);
-  void note_gang_enqueue(const Pod& p, int64_t t);
-  void note_gang_event(const Pod& p, bool bound);
-  void note_gang_planned(const Pod& p, bool hostable);
-  void note_gang_denied(const Pod& p, const char* why);
-  bool responsible_for(const Pod& p) const;
-
-  std::shared_ptr<ObjectStore> store_;
-  std::shared_ptr<Clock> clock_;
-  SchedulerOptions opts_;
-  std::unique_ptr<TimerService> timers_;
-  std::unique_ptr<Parallelizer> parallelizer_;
-  // Informer windows parse their pods' JSON on a few helpers ("xs-parse").
-  std::unique_ptr<Parallelizer> parse_pool_;
-  ParallelSite parse_site_;
-  std::unique_ptr<Metrics> metrics_;
-  std::unique_ptr<SchedulerCache> cache_;
-  std::unique_ptr<Informers> informers_;
-  std::unique_ptr<Nominator> nominator_;
-  std::unique_ptr<SchedulingQueue> queue_;
-  std::shared_ptr<ApiClient> client_;
-  ExtenderList extenders_;
-  std::shared_ptr<const GpuNames> gpu_names_;  // from the profiles' FlexGPU args
-  std::vector<std::unique_ptr<WaitingPods>> waiting_;
-  std::vector<std::unique_ptr<GangPlacement>> gang_placements_;  // one per profile (Handle::gangs)
-  std::vector<std::unique_ptr<Framework>> frameworks_;
-  std::unordered_map<std::string, Framework*> by_name_;
-  std::unique_ptr<Executor> binder_;
-  // FailedScheduling events: one FIFO worker, off the scheduling loop.
-  std::unique_ptr<Executor> status_writer_;
-  Snapshot snapshot_;
-  Tracer tracer_;
-  WatcherPtr watcher_;
-  std::vector<std::string> plugin_kinds_;
-
-  std::thread informer_thread_, sched_thread_;
-  std::atomic<bool> running_{false};
-  std::mutex sched_mu_;  // serializes scheduling cycles (loop vs schedule_one)
-  std::atomic<int> inflight_{0};
-  std::atomic<int> in_cycle_{0};
-  std::atomic<int64_t> loop_tick_us_{0};  // RealClock time of the last loop iteration
-  int next_start_node_ = 0;
-  // Node window shared by consecutive members of one gang and template
-  // (find_nodes_that_fit; scheduling thread only).
-  uint64_t window_gang_ = 0, window_tmpl_ = 0;
-  int window_start_ = 0, window_n_ = -1;
-  std::mt19937_64 rng_;
-  std::vector<uint64_t> timer_ids_;
-  std::unordered_map<Framework*, std::unordered_map<uint64_t, std::unique_ptr<EqEntry>>> eq_;  // scheduling thread only
-
-  mutable std::mutex stats_mu_;  // gang records and denials, condition memo
-  // Stats counters: relaxed atomics, bumped by the scheduling, binding and
-  // informer threads without a shared lock.
-  struct Counters {
-    std::atomic<uint64_t> attempts{0}, scheduled{0}, unschedulable{0}, errors{0}, bound{0}, bind_failures{0};
-    std::atomic<uint64_t> preemption_attempts{0}, eq_filter_hits{0}, eq_filter_misses{0};
-    std::atomic<uint64_t> scan_memo_served{0}, scan_memo_mismatches{0};
-  } cnt_;
-  std::atomic<uint64_t> bound_total_{0};  // bound pods, released for wait_bound (cnt_.bound counts the same)
   std::atomic<bool> fit_error_dumped_{false};  // dump_on_fit_error written
-  std::unordered_map<std::string, GangRecord> gangs_;  // open groups
-  // Completed gangs until a caller collects them: a deque, so the push on a
-  // binding thread (under stats_mu_) never moves the records already there
-  // (a benchmark collects ~10^5 of them at once).
-  std::deque<GangRecord> gang_done_;
-  std::unordered_map<int, Histogram*> gang_hist_;  // xsched_gang_admit_seconds{size} (under stats_mu_)
-  uint64_t gang_hist_epoch_ = ~0ULL;
-  static constexpr size_t kMaxGangDenials = 256;
-  std::vector<GangDenial> gang_denials_;
-  uint64_t gang_denials_total_ = 0;
-  std::atomic<uint64_t> gang_parks_total_{0};
 };
 
 }  // namespace xsched

@@ -1,5 +1,6 @@
 """Equivalence cache (Pod::template_hash + node-local Filter/Score reuse,
-csrc/scheduler/scheduler.cc eq_entry / find_nodes_that_fit, Framework::run_score).
+csrc/scheduler/filter_walk.cc eq_entry / find_nodes_that_fit, schedule_cycle.cc
+score_feasible, Framework::run_score).
 
 The cache must be exact: the same workload scheduled cycle by cycle with the
 cache on and off must produce identical placements and GPU assignments. The
