@@ -532,6 +532,7 @@ std::shared_ptr<Node> Node::from_json(const Json& obj, const GpuNames& gn) {
   }
   n->gpu_partitions.assign(n->gpu_count, parts);
   n->gpu_numa.assign(n->gpu_count, -1);
+  n->gpu_xcd_faults.assign(n->gpu_count, 0);
   int mid = gn.memory_id();
   if (n->gpu_count > 0 && n->allocatable.has(mid))  // homogeneous split (gpu_node.go:51-55)
     n->gpu_memory_per_gpu = n->allocatable.get(mid) / n->gpu_count;
@@ -550,6 +551,32 @@ std::shared_ptr<Node> Node::from_json(const Json& obj, const GpuNames& gn) {
         }
         if (g["numa"].is_number()) n->gpu_numa[idx] = static_cast<int>(g["numa"].as_int());
       }
+      // "xcdFaults": {"<gpu index>": [xcd, ...]}. A GPU the agent withheld as
+      // a whole ("unhealthy") is not in this node's GPU count: its entry says
+      // why it is gone and fences nothing here.
+      std::vector<int64_t> withheld;
+      for (const auto& u : t["unhealthy"].items())
+        if (u.is_number()) withheld.push_back(u.as_int());
+      if (const Json* xf = t.get("xcdFaults"); xf && xf->is_object()) {
+        for (int idx = 0; idx < n->gpu_count; ++idx) {
+          const Json* lst = xf->get(std::to_string(idx));
+          if (!lst || std::find(withheld.begin(), withheld.end(), idx) != withheld.end()) continue;
+          for (const auto& x : lst->items())
+            if (x.is_number() && x.as_int() >= 0 && x.as_int() < 8)
+              n->gpu_xcd_faults[idx] |= static_cast<uint8_t>(1u << x.as_int());
+        }
+      }
+      // The agent lowers allocatable memory by the fenced partitions' share;
+      // the per-GPU size is that of the hardware (fenced XCDs out of the divisor).
+      int64_t fenced_xcds = 0;
+      for (int idx = 0; idx < n->gpu_count; ++idx) {
+        const int p = std::max(1, n->gpu_partitions[idx]), xpp = 8 / p;
+        if (p == 1) continue;
+        for (int q = 0; q < p; ++q)
+          if ((n->gpu_xcd_faults[idx] >> (q * xpp)) & ((1u << xpp) - 1u)) fenced_xcds += xpp;
+      }
+      if (fenced_xcds > 0 && fenced_xcds < 8 * static_cast<int64_t>(n->gpu_count) && n->allocatable.has(mid))
+        n->gpu_memory_per_gpu = n->allocatable.get(mid) * 8 / (8 * static_cast<int64_t>(n->gpu_count) - fenced_xcds);
     } catch (const JsonError&) {
       // malformed topology annotation: keep label/allocatable-derived model
     }

@@ -378,6 +378,9 @@ struct Node {
   int gpu_count = 0;
   std::vector<int> gpu_partitions;  // partitions per physical GPU (1 = SPX .. 8 = CPX)
   std::vector<int> gpu_numa;        // NUMA node per GPU (-1 unknown)
+  // Bit k set: physical XCD k of that GPU holds a faulty CU (`xcdFaults` in
+  // the topology annotation); the ledger fences the partitions that own one.
+  std::vector<uint8_t> gpu_xcd_faults;
   int64_t gpu_memory_per_gpu = 0;   // memory slice units per physical GPU
   const std::string& name() const { return meta.name; }
   static std::shared_ptr<Node> from_json(const Json& obj, const GpuNames& gn = default_gpu_names());

@@ -129,6 +129,14 @@ void GpuLedger::init(const Node& n) {
   for (int g = 0; g < gpu_count; ++g) offset[g + 1] = offset[g] + std::max(1, parts[g]);
   monopoly.assign(gpu_count, 0);
   slots.assign(offset[gpu_count], Slot{});
+  // Partition p of a P-way GPU owns XCDs [p*8/P, (p+1)*8/P).
+  for (int g = 0; g < gpu_count; ++g) {
+    const unsigned mask = g < static_cast<int>(n.gpu_xcd_faults.size()) ? n.gpu_xcd_faults[g] : 0u;
+    const int xpp = xcds_per_part(g);
+    if (!mask || xpp <= 0) continue;
+    for (int p = 0; p < parts[g]; ++p)
+      slots[offset[g] + p].fenced = ((mask >> (p * xpp)) & ((1u << xpp) - 1u)) != 0;
+  }
   free.assign(gpu_count, GpuFree{});
   tot_whole = tot_xcds = 0;
   tot_mem = 0;
@@ -154,7 +162,8 @@ GpuLedger::GpuFree GpuLedger::compute(int g) const {
   bool untouched = true;
   for (int s = offset[g]; s < offset[g + 1]; ++s) {
     const Slot& sl = slots[s];
-    if (sl.exclusive > 0 || sl.used_mem > 0 || sl.mem_pods > 0) untouched = false;
+    if (sl.exclusive > 0 || sl.used_mem > 0 || sl.mem_pods > 0 || sl.fenced) untouched = false;
+    if (sl.fenced) continue;
     if (sl.exclusive == 0 && sl.used_mem == 0 && sl.mem_pods == 0) {
       ++f.free_slots;
       f.xcds += xpp;
@@ -226,7 +235,7 @@ bool GpuLedger::gpu_untouched(int g) const {
 bool GpuLedger::slot_free(int g, int p) const {
   if (monopoly[g] > 0) return false;
   const Slot& s = slots[offset[g] + p];
-  return s.exclusive == 0 && s.used_mem == 0 && s.mem_pods == 0;
+  return !s.fenced && s.exclusive == 0 && s.used_mem == 0 && s.mem_pods == 0;
 }
 
 // ------------------------------------------------------------- NodeInfo ----
@@ -336,7 +345,7 @@ std::vector<std::string> GpuLedger::diff(const GpuLedger& o) const {
   } else {
     for (size_t i = 0; i < slots.size(); ++i)
       if (slots[i].exclusive != o.slots[i].exclusive || slots[i].used_mem != o.slots[i].used_mem ||
-          slots[i].mem_pods != o.slots[i].mem_pods) {
+          slots[i].mem_pods != o.slots[i].mem_pods || slots[i].fenced != o.slots[i].fenced) {
         out.push_back("gpu.slots[" + std::to_string(i) + "]");
         break;
       }

@@ -195,6 +195,9 @@ struct GpuLedgerState {
     int exclusive = 0;     // whole-GPU or partition owners (expected 0/1)
     int64_t used_mem = 0;  // Σ memory-slice pods on this partition
     int mem_pods = 0;
+    // The partition owns an XCD with a faulty CU (Node::gpu_xcd_faults): never
+    // free, in no total; apply() still accounts pods already on it.
+    bool fenced = false;
   };
   int gpu_count = 0;
   int64_t mem_per_gpu = 0;
@@ -207,7 +210,7 @@ struct GpuLedgerState {
   // and Score read O(#GPUs) or O(1) aggregates instead of walking slots.
   struct GpuFree {
     int whole = 0;         // 1 if an untouched SPX GPU
-    int free_slots = 0;    // partitions with no owner and no memory use
+    int free_slots = 0;    // unfenced partitions with no owner and no memory use
     int xcds = 0;          // XCDs in those partitions
     int64_t mem = 0;       // free memory over non-exclusive partitions
     int64_t max_slot_mem = -1;  // largest free memory of one non-exclusive partition (-1: none)
@@ -248,7 +251,7 @@ struct GpuLedger : GpuLedgerState {
   // A whole-GPU claim needs an untouched GPU in SPX mode: on a partitioned
   // GPU the container would see 2/4/8 separate devices, not one MI355X.
   bool whole_gpu_free(int g) const { return free[g].whole != 0; }
-  bool slot_free(int g, int p) const;   // exclusive-free and no memory use
+  bool slot_free(int g, int p) const;   // not fenced, exclusive-free and no memory use
   void copy_zones(const GpuLedger& o) {
     const int n = std::max(zone_n, o.zone_n);
     std::copy_n(o.zone_gpus, n, zone_gpus);

@@ -141,7 +141,7 @@ Placement place_memory(const GpuLedger& L, int64_t m, bool* breaks_whole = nullp
     bool breaks = L.whole_gpu_free(g);
     for (int p = 0; p < L.parts[g]; ++p) {
       const auto& s = L.slots[L.offset[g] + p];
-      if (s.exclusive > 0) continue;
+      if (s.exclusive > 0 || s.fenced) continue;
       int64_t remain = cap - s.used_mem - m;
       if (remain < 0) continue;
       if (bg < 0 || (!breaks && best_breaks) || (breaks == best_breaks && remain < best_remain)) {

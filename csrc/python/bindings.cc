@@ -155,16 +155,19 @@ py::dict node_info_dict(const NodeInfo& ni) {
   g["mem_per_gpu"] = ni.gpu.mem_per_gpu;
   g["partitions"] = ni.gpu.parts;
   g["monopoly"] = ni.gpu.monopoly;
-  py::list slots;
+  py::list slots, fenced;
   for (int gi = 0; gi < ni.gpu.gpu_count; ++gi) {
-    py::list ps;
+    py::list ps, fs;
     for (int s = ni.gpu.offset[gi]; s < ni.gpu.offset[gi + 1]; ++s) {
       const auto& sl = ni.gpu.slots[s];
       ps.append(py::make_tuple(sl.exclusive, sl.used_mem, sl.mem_pods));
+      fs.append(sl.fenced);
     }
     slots.append(ps);
+    fenced.append(fs);
   }
   g["slots"] = slots;
+  g["fenced"] = fenced;  // parallel to "slots": the partition holds a faulty XCD
   g["free_gpus"] = ni.gpu.free_gpus();
   g["free_xcds"] = ni.gpu.free_xcds();
   g["free_memory"] = ni.gpu.free_memory();

@@ -342,7 +342,8 @@ def cmd_node_agent(args) -> int:
                       heartbeat=args.heartbeat, telemetry_period=args.telemetry_period,
                       publish_metrics=not args.no_telemetry, reserved_cpu=args.reserved_cpu,
                       reserved_memory_gib=args.reserved_memory_gib,
-                      health_fn=hip_health_fn() if args.health_probe else None,
+                      health_fn=(hip_health_fn(sweep=args.health_sweep, sweep_period_s=args.health_sweep_period)
+                                 if args.health_probe or args.health_sweep else None),
                       bandwidth_fn=hip_bandwidth_fn() if args.bandwidth_probe else None,
                       kubelet_managed=args.kubelet_managed).start()
     if args.device_plugin:
@@ -351,6 +352,7 @@ def cmd_node_agent(args) -> int:
         agent.device_plugins = start_plugins(agent.host, client, agent.name, socket_dir=args.device_plugin_dir)
         for dp in agent.device_plugins:
             dp.set_unhealthy(agent.unhealthy)
+            dp.set_unhealthy_xcds(agent.unhealthy_xcds)
     print(json.dumps({"node": agent.name, "gpus": len(agent.host.gpus)}), flush=True)
     stop = threading.Event()
     _wait_forever(stop)
@@ -497,6 +499,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--telemetry-period", type=float, default=60.0)
     p.add_argument("--no-telemetry", action="store_true")
     p.add_argument("--health-probe", action="store_true", help="run the HIP health probe on each GPU")
+    p.add_argument("--health-sweep", action="store_true",
+                   help="health probe plus the CU sweep: MFMA, VALU and LDS checked on every CU; a bad XCD "
+                        "fences its compute partition (xcdFaults) instead of the whole GPU. Implies --health-probe")
+    p.add_argument("--health-sweep-period", type=float, default=600.0, metavar="SECONDS",
+                   help="reuse a sweep's verdict this long before sweeping the GPU again")
     p.add_argument("--bandwidth-probe", action="store_true",
                    help="measure HBM bandwidth per compute-partition size on each GPU and publish it "
                         "(amd.com/gpu-hbm-bandwidth)")

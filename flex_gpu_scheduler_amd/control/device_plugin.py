@@ -31,7 +31,8 @@ from concurrent import futures
 import grpc
 
 from ..gpu.discovery import HostInfo
-from ..models.mi355x import GPU, GPU_MEMORY, GPU_XCD, INDEX_ANNOTATION, PARTITION_ANNOTATION, XCDS_PER_GPU
+from ..models.mi355x import (GPU, GPU_MEMORY, GPU_XCD, INDEX_ANNOTATION, PARTITION_ANNOTATION, XCDS_PER_GPU,
+                             fenced_partitions)
 from .client import Client
 from .deviceplugin_api import DEVICE_PLUGIN_PATH, HEALTHY, KUBELET_SOCKET, UNHEALTHY, VERSION, method_path, pb
 
@@ -59,6 +60,7 @@ class GpuDevicePlugin:
         short = resource.split("/")[-1]
         self.endpoint = f"xsched-{short}.sock"
         self.unhealthy = set(unhealthy or ())
+        self.unhealthy_xcds: dict[int, set[int]] = {}  # GPU index -> bad physical XCD ids
         self._server: grpc.Server | None = None
         self._cv = threading.Condition()
         self._gen = 0
@@ -75,11 +77,28 @@ class GpuDevicePlugin:
             if self.resource == GPU:
                 if g.partitions == 1:
                     out.append(pb.Device(ID=f"gpu-{g.index}", health=health, topology=topo))
-            elif self.resource == GPU_XCD:
-                out += [pb.Device(ID=f"xcd-{g.index}-{k}", health=health, topology=topo) for k in range(XCDS_PER_GPU)]
+                continue
+            # XCDs (and their share of the HBM devices) of compute partitions
+            # that hold a bad XCD: partition p of a P-way GPU owns XCDs
+            # [p*8/P, (p+1)*8/P), the ledger's convention.
+            fenced = fenced_partitions(g.partitions, self.unhealthy_xcds.get(g.index, ())) if g.partitions > 1 else []
+            if self.resource == GPU_XCD:
+                xpp = XCDS_PER_GPU // max(1, g.partitions)
+                out += [pb.Device(ID=f"xcd-{g.index}-{k}", health=UNHEALTHY if k // xpp in fenced else health,
+                                  topology=topo) for k in range(XCDS_PER_GPU)]
             else:
-                out += [pb.Device(ID=f"mem-{g.index}-{i}", health=health, topology=topo) for i in range(g.hbm_gib)]
+                lost = len(fenced) * g.hbm_gib // max(1, g.partitions)
+                out += [pb.Device(ID=f"mem-{g.index}-{i}", health=UNHEALTHY if i >= g.hbm_gib - lost else health,
+                                  topology=topo) for i in range(g.hbm_gib)]
         return out
+
+    def set_unhealthy_xcds(self, xcds: dict[int, set[int]]) -> None:
+        xcds = {int(g): set(x) for g, x in xcds.items() if x}
+        with self._cv:
+            if xcds != self.unhealthy_xcds:
+                self.unhealthy_xcds = xcds
+                self._gen += 1
+                self._cv.notify_all()
 
     def set_unhealthy(self, gpus: set[int]) -> None:
         with self._cv:

@@ -12,7 +12,9 @@ exporter + metrics-server:
     GPUs) for NodeResourceTopologyMatch;
   * optionally runs the HIP health probe (ops/hip_probe.py: pattern write +
     checksum per GPU) and withholds unhealthy GPUs from allocatable, tainting
-    the node when none are healthy;
+    the node when none are healthy; a verdict that names bad XCDs (GpuHealth,
+    e.g. from the CU sweep) fences only the compute partitions holding them
+    on a DPX/QPX/CPX GPU (`xcdFaults` in the topology annotation);
   * samples load (gpu/telemetry.py) and publishes its WatcherMetrics document
     for the Trimaran plugins.
 """
@@ -22,13 +24,14 @@ import json
 import logging
 import threading
 import time
+from dataclasses import dataclass, field
 from datetime import datetime, timezone
 from typing import Callable
 
 from ..gpu.discovery import HostInfo, discover_host
 from ..gpu.telemetry import HostSampler, NodeTelemetry, publish
-from ..models.mi355x import (GPU, GPU_MEMORY, GPU_XCD, TOPOLOGY_ANNOTATION, XCDS_PER_GPU, mi355x_node,
-                             mi355x_nrt)
+from ..models.mi355x import (GPU, GPU_MEMORY, GPU_XCD, TOPOLOGY_ANNOTATION, XCDS_PER_GPU, fenced_partitions,
+                             mi355x_node, mi355x_nrt)
 from .client import Client, is_conflict
 
 log = logging.getLogger(__name__)
@@ -44,12 +47,30 @@ def _now() -> str:
     return datetime.now(timezone.utc).strftime("%Y-%m-%dT%H:%M:%SZ")
 
 
+@dataclass(frozen=True)
+class GpuHealth:
+    """A health verdict finer than one boolean: `bad_xcds` are the GPU's
+    physical XCD ids (0-7) that hold a faulty CU. An SPX GPU with a bad XCD is
+    withheld like an unhealthy one; on a DPX/QPX/CPX GPU only the compute
+    partitions that contain a bad XCD are fenced. `ok` False with no bad XCD
+    is a whole-GPU failure."""
+    ok: bool
+    bad_xcds: frozenset = frozenset()
+    detail: dict = field(default_factory=dict, compare=False)
+
+    def __post_init__(self):
+        object.__setattr__(self, "bad_xcds", frozenset(int(x) for x in self.bad_xcds if 0 <= int(x) < XCDS_PER_GPU))
+
+    def __bool__(self) -> bool:
+        return bool(self.ok) and not self.bad_xcds
+
+
 class NodeAgent:
     def __init__(self, client: Client, node_name: str, *, host_fn: Callable[[], HostInfo] | None = None,
                  root: str = "/", labels: dict | None = None, reserved_cpu: int = 0, reserved_memory_gib: int = 0,
                  heartbeat: float = 10.0, telemetry_period: float = 60.0, publish_metrics: bool = True,
-                 health_fn: Callable[[int], bool] | None = None, sampler=None, kubelet_managed: bool = False,
-                 bandwidth_fn: Callable[[int], dict] | None = None):
+                 health_fn: Callable[[int], "bool | GpuHealth"] | None = None, sampler=None,
+                 kubelet_managed: bool = False, bandwidth_fn: Callable[[int], dict] | None = None):
         self.client, self.name = client, node_name
         self.host_fn = host_fn or (lambda: discover_host(root))
         self.labels = dict(labels or {})
@@ -70,6 +91,8 @@ class NodeAgent:
         self._root = root
         self.telemetry: NodeTelemetry | None = None
         self.unhealthy: set[int] = set()
+        # GPU index -> physical XCD ids a GpuHealth verdict named as bad.
+        self.unhealthy_xcds: dict[int, set[int]] = {}
         self._stop = threading.Event()
         self._threads: list[threading.Thread] = []
         self.host: HostInfo | None = None
@@ -80,9 +103,16 @@ class NodeAgent:
 
     # --------------------------------------------------------------- objects
     def check_health(self, host: HostInfo) -> set[int]:
+        return self.probe_health(host)[0]
+
+    def probe_health(self, host: HostInfo) -> tuple[set[int], dict[int, set[int]]]:
+        """(GPUs to withhold, bad XCDs per GPU). A `bool` from health_fn means
+        the whole GPU; a GpuHealth with bad XCDs withholds an SPX GPU and only
+        marks the XCDs of a partitioned one."""
         if self.health_fn is None:
-            return set()
-        bad = set()
+            return set(), {}
+        bad: set[int] = set()
+        xcds: dict[int, set[int]] = {}
         # HIP ordinals follow the KFD node order of the GPUs this process can
         # open; GPUs whose KFD node is hidden (other containers' devices) are
         # not probed. With no KFD info at all (fake hosts) use the index.
@@ -90,12 +120,28 @@ class NodeAgent:
         targets = [(i, g) for i, g in enumerate(visible)] if visible else [(g.index, g) for g in host.gpus]
         for ordinal, g in targets:
             try:
-                if not self.health_fn(ordinal):
+                r = self.health_fn(ordinal)
+                if isinstance(r, GpuHealth) and r.bad_xcds:
+                    xcds[g.index] = set(r.bad_xcds)
+                    if g.partitions == 1:
+                        bad.add(g.index)
+                elif not (r.ok if isinstance(r, GpuHealth) else r):
                     bad.add(g.index)
             except Exception as e:  # noqa: BLE001
                 log.warning("health probe GPU %d failed: %s", g.index, e)
                 bad.add(g.index)
-        return bad
+        return bad, xcds
+
+    @staticmethod
+    def _fenced(gpus, xcd_faults) -> dict[int, tuple[int, int]]:
+        """GPU index -> (XCDs, HBM GiB) in the partitions fenced by `xcd_faults`
+        on the partitioned GPUs among `gpus`."""
+        out = {}
+        for g in gpus:
+            parts = fenced_partitions(g.partitions, (xcd_faults or {}).get(g.index, ()))
+            if g.partitions > 1 and parts:
+                out[g.index] = (len(parts) * XCDS_PER_GPU // g.partitions, len(parts) * g.hbm_gib // g.partitions)
+        return out
 
     def measure_bandwidth(self, host: HostInfo) -> None:
         """Partition bandwidth table per healthy GPU (HIP ordinal order, as
@@ -118,7 +164,8 @@ class NodeAgent:
                             self.bandwidth_retry_s, e)
                 self._bandwidth_retry_at[g.index] = now + self.bandwidth_retry_s
 
-    def build_node(self, host: HostInfo, unhealthy: set[int] = frozenset()) -> dict:
+    def build_node(self, host: HostInfo, unhealthy: set[int] = frozenset(),
+                   xcd_faults: dict[int, set[int]] | None = None) -> dict:
         healthy = [g for g in host.gpus if g.index not in unhealthy]
         infos = [g.to_gpu_info() for g in healthy]
         mem_kib = max(0, host.memory_bytes // 1024 - self.reserved_memory_gib * (1 << 20))
@@ -142,6 +189,9 @@ class NodeAgent:
                          computePartition=g.compute_partition, xgmiLinks=len(g.xgmi_links),
                          xgmiLinkMBps=max((lk.bandwidth_mbps for lk in g.xgmi_links), default=0))
         topo["unhealthy"] = sorted(unhealthy)
+        faults = {str(i): sorted(x) for i, x in sorted((xcd_faults or {}).items()) if x}
+        if faults:
+            topo["xcdFaults"] = faults
         node["metadata"]["annotations"][TOPOLOGY_ANNOTATION] = json.dumps(topo, sort_keys=True)
         if self.bandwidth:
             node["metadata"]["annotations"][BANDWIDTH_ANNOTATION] = json.dumps(
@@ -152,6 +202,11 @@ class NodeAgent:
         cap[GPU_XCD] = str(XCDS_PER_GPU * len(host.gpus))
         cap[GPU_MEMORY] = str(sum(g.hbm_gib for g in host.gpus))
         node["status"]["capacity"] = cap
+        fenced = self._fenced(healthy, xcd_faults)
+        if fenced:
+            alloc = node["status"]["allocatable"]
+            alloc[GPU_XCD] = str(int(alloc[GPU_XCD]) - sum(x for x, _ in fenced.values()))
+            alloc[GPU_MEMORY] = str(int(alloc[GPU_MEMORY]) - sum(m for _, m in fenced.values()))
         if self.kubelet_managed:
             for k in (GPU, GPU_XCD, GPU_MEMORY):
                 node["status"]["allocatable"].pop(k, None)
@@ -167,7 +222,8 @@ class NodeAgent:
         return {"type": "Ready", "status": "True", "reason": "AgentReady", "message": "MI355X node agent is posting",
                 "lastHeartbeatTime": now, "lastTransitionTime": now}
 
-    def build_nrt(self, host: HostInfo, unhealthy: set[int] = frozenset()) -> dict:
+    def build_nrt(self, host: HostInfo, unhealthy: set[int] = frozenset(),
+                  xcd_faults: dict[int, set[int]] | None = None) -> dict:
         sockets = max(1, len(host.numa_nodes))
         cpus = [len(host.numa_cpus.get(s, [])) or host.cpus // sockets for s in range(sockets)]
         mem_gib = host.memory_bytes // (1 << 30) // sockets
@@ -178,6 +234,14 @@ class NodeAgent:
             for r in z["resources"]:
                 if r["name"] == "cpu":
                     r["capacity"] = r["allocatable"] = r["available"] = str(c)
+        fenced = self._fenced([g for g in host.gpus if g.index not in unhealthy], xcd_faults)
+        for g in host.gpus:
+            if g.index not in fenced or not 0 <= max(g.numa, 0) < len(nrt["zones"]):
+                continue
+            lost = dict(zip((GPU_XCD, GPU_MEMORY), fenced[g.index]))
+            for r in nrt["zones"][max(g.numa, 0)]["resources"]:
+                if r["name"] in lost:  # capacity still reports the hardware
+                    r["allocatable"] = r["available"] = str(int(r["allocatable"]) - lost[r["name"]])
         return nrt
 
     # --------------------------------------------------------------- publish
@@ -219,13 +283,15 @@ class NodeAgent:
 
     def sync(self) -> HostInfo:
         host = self.host_fn()
-        self.unhealthy = self.check_health(host)
+        self.unhealthy, self.unhealthy_xcds = self.probe_health(host)
         self.measure_bandwidth(host)
         for dp in self.device_plugins:
             dp.host = host
             dp.set_unhealthy(self.unhealthy)
-        self._upsert("nodes", self.build_node(host, self.unhealthy), keep_spec=True)
-        self._upsert("noderesourcetopologies", self.build_nrt(host, self.unhealthy), keep_spec=False)
+            dp.set_unhealthy_xcds(self.unhealthy_xcds)
+        self._upsert("nodes", self.build_node(host, self.unhealthy, self.unhealthy_xcds), keep_spec=True)
+        self._upsert("noderesourcetopologies", self.build_nrt(host, self.unhealthy, self.unhealthy_xcds),
+                     keep_spec=False)
         self.host = host
         return host
 
@@ -264,9 +330,9 @@ class NodeAgent:
 
     def _heartbeat_and_resync(self) -> None:
         host = self.host_fn()
-        unhealthy = self.check_health(host)
+        unhealthy, xcds = self.probe_health(host)
         changed = (self.host is None or [g.to_gpu_info() for g in host.gpus] != [g.to_gpu_info() for g in self.host.gpus]
-                   or unhealthy != self.unhealthy)
+                   or unhealthy != self.unhealthy or xcds != self.unhealthy_xcds)
         if changed:
             self.sync()
         else:
@@ -278,15 +344,48 @@ class NodeAgent:
             t.join(timeout=5)
 
 
-def hip_health_fn() -> Callable[[int], bool]:
+def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0,
+                  sweep_args: dict | None = None) -> Callable[[int], "bool | GpuHealth"]:
     """Health callback backed by the HIP probes (HBM pattern + checksum and an
-    MFMA tile check per GPU)."""
+    MFMA tile check per GPU).
+
+    `sweep`: also run the CU sweep (HipProbe.cu_sweep, `sweep_args` are its
+    keywords), which checks MFMA, VALU and LDS on every CU. The callback runs
+    on every heartbeat, so a sweep's verdict is reused for `sweep_period_s`.
+    On a device that shows all 8 XCDs the verdict is a GpuHealth naming the
+    bad physical XCDs; a partition device numbers its XCDs logically, so
+    there a failed sweep fails the device as a whole (a plain bool). CUs the
+    sweep could not reach are logged, never counted as failed."""
     from ..ops.hip_probe import probe
 
     p = probe()
-    # HBM pattern/checksum and an exact-integer MFMA tile: a GPU whose matrix
-    # cores mis-compute is withheld even if its memory checks out.
-    return lambda dev: bool(p.health(dev)["healthy"]) and bool(p.mfma_check(dev)["healthy"])
+    last: dict[int, tuple[float, object]] = {}  # dev -> (monotonic time, sweep verdict)
+
+    def sweep_verdict(dev: int):
+        now = time.monotonic()
+        if dev in last and now - last[dev][0] < sweep_period_s:
+            return last[dev][1]
+        s = p.cu_sweep(dev, **(sweep_args or {}))["summary"]
+        log.log(logging.WARNING if s["bad_xcds"] else logging.INFO,
+                "cu sweep GPU %d: %d CUs on %d XCDs in %.2f ms (%d launch(es)), covered=%s uncovered=%s bad_xcds=%s",
+                dev, s["cus_seen"], len(s["xcds"]), s["ms"], s["rounds"], s["covered"],
+                {x: n for x, n in s["uncovered"].items() if n}, s["bad_xcds"])
+        if int(p.props(dev)["computeUnits"]) // 32 >= XCDS_PER_GPU:
+            v = GpuHealth(not s["bad_xcds"], frozenset(s["bad_xcds"]), {"sweep": s})
+        else:
+            v = not s["bad_xcds"]
+        last[dev] = (now, v)
+        return v
+
+    def check(dev: int):
+        # HBM pattern/checksum and an exact-integer MFMA tile: a GPU whose matrix
+        # cores mis-compute is withheld even if its memory checks out.
+        ok = bool(p.health(dev)["healthy"]) and bool(p.mfma_check(dev)["healthy"])
+        if not sweep or not ok:
+            return ok
+        return sweep_verdict(dev)
+
+    return check
 
 
 def hip_bandwidth_fn(nbytes: int = 1 << 30, iters: int = 10) -> Callable[[int], dict]:

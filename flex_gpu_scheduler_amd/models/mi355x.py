@@ -45,6 +45,14 @@ class GpuInfo:
         return PARTITIONS[self.partition_mode]
 
 
+def fenced_partitions(partitions: int, bad_xcds) -> list[int]:
+    """Compute partitions of a `partitions`-way GPU that contain one of the
+    physical XCDs (0-7) in `bad_xcds`. Partition p owns XCDs
+    [p*8/P, (p+1)*8/P): the scheduler ledger's convention (xcds_per_part)."""
+    p = max(1, partitions)
+    return sorted({int(x) * p // XCDS_PER_GPU for x in bad_xcds if 0 <= int(x) < XCDS_PER_GPU})
+
+
 def default_gpus(n: int = GPUS_PER_NODE, mode: str = "spx", sockets: int = 2) -> list[GpuInfo]:
     per = max(1, n // sockets)
     return [GpuInfo(i, mode, numa=min(sockets - 1, i // per)) for i in range(n)]

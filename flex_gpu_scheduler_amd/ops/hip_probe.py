@@ -1,12 +1,13 @@
 """ctypes front-end for the HIP/CDNA4 device probes (csrc/hip/hbm_probe.hip,
-csrc/hip/mfma_probe.hip).
+csrc/hip/mfma_probe.hip, csrc/hip/cu_sweep.hip).
 
 The probes are what the node agent runs before advertising an MI355X as
 schedulable: device properties, HBM streaming bandwidth (optionally with a
 partition-sized CU budget), an XCD census that verifies the compute-partition
 mode, a checksum health test, an exact-integer MFMA tile check of the matrix
-cores and the dense bf16 MFMA throughput of the whole GPU or of one
-partition's XCDs.
+cores, the dense bf16 MFMA throughput of the whole GPU or of one
+partition's XCDs, and a sweep that checks MFMA, VALU and LDS on every CU and
+names the XCD of a CU that mis-computes.
 """
 from __future__ import annotations
 
@@ -20,7 +21,7 @@ MODES = {"read": 0, "write": 1, "copy": 2, "triad": 3}
 
 
 class ProbeError(RuntimeError):
-    pass
+    rc: int | None = None  # the C ABI's return code, where one caused the error
 
 
 @dataclass
@@ -41,6 +42,11 @@ class Bandwidth:
 # Working sets default to 1 GiB per array: 4x the MI355X's 256 MB Infinity
 # Cache, so a streaming rate is HBM's, not the cache's.
 DEFAULT_BYTES = 1 << 30
+
+# k_cu_sweep (csrc/hip/cu_sweep.hip)
+SWEEP_ENGINES = {1: "mfma", 2: "valu", 4: "lds"}  # fail bit -> digest of that engine
+SWEEP_LDS_MAX = 160 << 10
+SWEEP_BAD_ARGS = -1000
 
 
 class HipProbe:
@@ -87,6 +93,13 @@ class HipProbe:
         L.xs_mfma_peak.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
                                    ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                    ctypes.POINTER(ctypes.c_int)]
+        L.xs_cu_sweep_last_error.restype = ctypes.c_char_p
+        L.xs_cu_sweep_max_lds.argtypes = [ctypes.c_int]
+        L.xs_cu_sweep_max_lds.restype = ctypes.c_size_t
+        L.xs_cu_sweep_expected.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32)]
+        L.xs_cu_sweep.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, ctypes.c_int,
+                                  ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int),
+                                  ctypes.POINTER(ctypes.c_double)]
 
     def _err(self, rc: int, what: str) -> ProbeError:
         return ProbeError(f"{what} failed ({rc}): {self.lib.xs_last_error().decode(errors='replace')}")
@@ -272,6 +285,106 @@ class HipProbe:
         if rc != 0:
             raise ProbeError(f"mfma_peak failed: {self.lib.xs_mfma_last_error().decode(errors='replace')}")
         return {"tflops": tf.value, "ms": ms.value, "active_blocks": act.value, "xcd_mask": xcd_mask}
+
+
+    # ------------------------------------------------------------- CU sweep
+    def cu_sweep_max_lds(self, dev: int = 0) -> int:
+        """Bytes of LDS one sweep workgroup can cover on `dev` (160 KiB on an MI355X)."""
+        n = int(self.lib.xs_cu_sweep_max_lds(dev))
+        if n <= 0:
+            raise ProbeError(f"cu_sweep_max_lds failed: {self.lib.xs_cu_sweep_last_error().decode(errors='replace')}")
+        return n
+
+    def cu_sweep_expected(self, k: int = 64, lds_bytes: int = SWEEP_LDS_MAX) -> dict:
+        """The digests a healthy CU leaves, computed on the host."""
+        out = (ctypes.c_uint32 * 3)()
+        rc = self.lib.xs_cu_sweep_expected(k, lds_bytes, out)
+        if rc != 0:
+            raise _sweep_error(self, rc, "cu_sweep_expected")
+        return {"mfma": out[0], "valu": out[1], "lds": out[2]}
+
+    def cu_sweep(self, dev: int = 0, blocks: int = 0, k: int = 64, lds_bytes: int | None = None,
+                 inject: tuple | None = None, max_rounds: int = 4) -> dict:
+        """k_cu_sweep: MFMA, VALU and LDS checked on every CU a workgroup lands
+        on. `lds_bytes` None: all of a CU's LDS. `inject` = (xcd, cu key or
+        None for every CU of that XCD, engine bits): those workgroups flip one
+        bit of what they computed (tests the comparator on a healthy GPU).
+
+        A launch whose grid could cover the device (blocks 0 = 4 per CU) is
+        repeated while some CU has not been seen, at most `max_rounds`
+        launches in all; records accumulate. Returns {"records": [...],
+        "summary": summarize_sweep(...) plus rounds, ms, blocks}."""
+        props = self.props(dev)
+        cus = int(props["computeUnits"])
+        if lds_bytes is None:
+            lds_bytes = self.cu_sweep_max_lds(dev)
+        n_blocks = blocks if blocks != 0 else 4 * cus
+        ix, ic, ie = -1, -1, 0
+        if inject is not None:
+            ix, ic, ie = int(inject[0]), -1 if inject[1] is None else int(inject[1]), int(inject[2])
+        expected = None
+        records: list[dict] = []
+        total_ms, rounds = 0.0, 0
+        summary: dict = {}
+        for _ in range(max(1, max_rounds if n_blocks >= cus else 1)):
+            buf = (ctypes.c_uint32 * (8 * max(1, n_blocks)))()
+            n, ms = ctypes.c_int(), ctypes.c_double()
+            rc = self.lib.xs_cu_sweep(dev, n_blocks, k, lds_bytes, ix, ic, ie, buf, ctypes.byref(n), ctypes.byref(ms))
+            if rc != 0:
+                raise _sweep_error(self, rc, "cu_sweep")
+            if expected is None:
+                expected = self.cu_sweep_expected(k, lds_bytes)
+            rounds += 1
+            total_ms += ms.value
+            for i in range(n.value):
+                w = buf[8 * i:8 * i + 8]
+                rec = {"xcd": w[0], "cu": w[1], "simd_mask": w[2], "fail": w[3], "mfma": w[4], "valu": w[5],
+                       "lds": w[6]}
+                # A digest that differs from the host's is a failure even if
+                # the device-side comparator (on the same CU) passed it.
+                for bit, name in SWEEP_ENGINES.items():
+                    if rec[name] != expected[name]:
+                        rec["fail"] |= bit
+                records.append(rec)
+            summary = summarize_sweep(records, cus)
+            if summary["covered"]:
+                break
+        summary.update(rounds=rounds, ms=total_ms, blocks=n_blocks, k=k, lds_bytes=lds_bytes)
+        return {"records": records, "summary": summary}
+
+
+def _sweep_error(p: HipProbe, rc: int, what: str) -> ProbeError:
+    detail = "bad arguments" if rc == SWEEP_BAD_ARGS else p.lib.xs_cu_sweep_last_error().decode(errors="replace")
+    e = ProbeError(f"{what} failed ({rc}): {detail}")
+    e.rc = rc
+    return e
+
+
+def summarize_sweep(records: list[dict], compute_units: int) -> dict:
+    """Aggregate k_cu_sweep records ({"xcd", "cu", "fail", ...}; one per
+    workgroup, a CU may appear many times) into a verdict per XCD.
+
+    A CU is failed when any of its records has a fail bit; an XCD is bad when
+    it has a failed CU. CUs no workgroup reached are `uncovered`, never failed
+    (other tenants may hold them)."""
+    seen: dict[int, set[int]] = {}
+    failed: dict[int, dict[int, int]] = {}
+    for r in records:
+        x, c = int(r["xcd"]), int(r["cu"])
+        seen.setdefault(x, set()).add(c)
+        if int(r.get("fail", 0)):
+            failed.setdefault(x, {})[c] = failed.get(x, {}).get(c, 0) | int(r["fail"])
+    expected = compute_units // len(seen) if seen else 0
+    xcds, uncovered = {}, {}
+    for x in sorted(seen):
+        bits = 0
+        for b in failed.get(x, {}).values():
+            bits |= b
+        xcds[x] = {"cus_seen": len(seen[x]), "cus_expected": expected, "failed_cus": sorted(failed.get(x, {})),
+                   "fail_bits": bits}
+        uncovered[x] = max(0, expected - len(seen[x]))
+    return {"xcds": xcds, "bad_xcds": sorted(failed), "covered": bool(seen) and not any(uncovered.values()),
+            "uncovered": uncovered, "cus_seen": sum(len(v) for v in seen.values())}
 
 
 _probe: HipProbe | None = None
