@@ -20,6 +20,7 @@
 #include <mutex>
 #include <thread>
 #include <unordered_map>
+#include <vector>
 #include <pthread.h>
 
 namespace xsched {
@@ -69,6 +70,12 @@ class TimerService {
 
   uint64_t schedule_at(int64_t deadline_us, Fn fn);
   uint64_t schedule_after(int64_t delay_us, Fn fn) { return schedule_at(clock_->now_us() + delay_us, std::move(fn)); }
+  // One-shot timer without a heap-allocated callable (a Permit timeout per
+  // waiting pod): `fn(target, arg)` runs if `target` is still alive when the
+  // timer fires. Timer and heap map nodes are reused, so arming and
+  // cancelling such a timer allocates nothing in steady state.
+  using TargetFn = void (*)(const std::shared_ptr<void>& target, int arg);
+  uint64_t schedule_after(int64_t delay_us, TargetFn fn, std::weak_ptr<void> target, int arg);
   // Periodic timer; the period is measured from each firing.
   uint64_t every(int64_t period_us, Fn fn);
   bool cancel(uint64_t id);
@@ -81,16 +88,29 @@ class TimerService {
  private:
   struct Timer {
     Fn fn;
+    TargetFn target_fn = nullptr;  // instead of fn
+    std::weak_ptr<void> target;
+    int arg = 0;
     int64_t period_us = 0;
     std::multimap<int64_t, uint64_t>::iterator pos;
   };
   void loop();
+  // Under mu_. Erased map nodes go to the spare lists and come back on the
+  // next insert.
+  std::multimap<int64_t, uint64_t>::iterator heap_insert(int64_t deadline_us, uint64_t id);
+  void heap_erase(std::multimap<int64_t, uint64_t>::iterator it);
+  void timer_insert(uint64_t id, Timer&& t);
+  void timer_erase(std::unordered_map<uint64_t, Timer>::iterator it);
+  uint64_t arm(int64_t deadline_us, Timer&& t);
 
   std::shared_ptr<Clock> clock_;
   AdaptiveMutex mu_;  // schedule/cancel per waiting pod, from the scheduling and binder threads
   std::condition_variable_any cv_, drained_cv_;
   std::multimap<int64_t, uint64_t> heap_;
   std::unordered_map<uint64_t, Timer> timers_;
+  static constexpr size_t kSpareNodes = 4096;
+  std::vector<std::multimap<int64_t, uint64_t>::node_type> spare_heap_;
+  std::vector<std::unordered_map<uint64_t, Timer>::node_type> spare_timers_;
   uint64_t next_id_ = 1;
   bool stop_ = false;
   bool running_cb_ = false;

@@ -694,7 +694,11 @@ Status Framework::run_permit(CycleState& s, const PodPtr& p, const std::string& 
                              std::function<void(const Status&)> on_done) {
   auto it = chain_.find(kPermit);
   if (it == chain_.end()) return {};
-  std::map<std::string, int64_t> timeouts;
+  // The plugins that answered Wait; beyond the inline few (never seen), a vector.
+  constexpr size_t kInline = 4;
+  WaitingPods::Timeout inline_timeouts[kInline];
+  std::vector<WaitingPods::Timeout> more_timeouts;
+  size_t nwait = 0;
   for (const auto& pl : it->second) {
     auto [st, timeout] = pl->permit(s, p, node);
     if (st.is_success()) continue;
@@ -703,13 +707,20 @@ Status Framework::run_permit(CycleState& s, const PodPtr& p, const std::string& 
       return st;
     }
     if (st.is_wait()) {
-      timeouts[pl->name()] = std::min(std::max<int64_t>(timeout, 0), kMaxPermitTimeoutUs);
+      WaitingPods::Timeout t{pl->name_ptr(), std::min(std::max<int64_t>(timeout, 0), kMaxPermitTimeoutUs)};
+      if (nwait < kInline) {
+        inline_timeouts[nwait] = t;
+      } else {
+        if (more_timeouts.empty()) more_timeouts.assign(inline_timeouts, inline_timeouts + kInline);
+        more_timeouts.push_back(t);
+      }
+      ++nwait;
       continue;
     }
     return Status(Code::Error, "running Permit plugin " + pl->name() + ": " + st.message()).with_plugin(pl->name_ptr());
   }
-  if (timeouts.empty()) return {};
-  handle_.waiting_pods->add(p, node, timeouts, std::move(on_done));
+  if (nwait == 0) return {};
+  handle_.waiting_pods->add(p, node, nwait <= kInline ? inline_timeouts : more_timeouts.data(), nwait, std::move(on_done));
   // Prebuilt (the reference appends the pod name; the caller only tests
   // is_wait(), so the message is not built per waiting gang member).
   static const Status kWait(Code::Wait, "one or more plugins asked to wait and no plugin rejected the pod");

@@ -103,6 +103,17 @@ void CycleState::erase(std::string_view key) {
   kv_.erase(std::remove_if(kv_.begin(), kv_.end(), [&](const auto& kv) { return *kv.first == key; }), kv_.end());
 }
 
+void CycleState::reset() {
+  std::unique_lock<std::shared_mutex> g(mu_);
+  version_.store(next_version(), std::memory_order_release);
+  spare_.clear();
+  spare_.swap(kv_);  // both keep their capacity
+  record_metrics = false;
+  skip_filter_plugins_mark = false;
+  filter_skip = 0;
+  nominated.reset();
+}
+
 std::shared_ptr<CycleState> CycleState::clone() const {
   auto c = std::make_shared<CycleState>();
   std::shared_lock<std::shared_mutex> g(mu_);

@@ -161,6 +161,26 @@ class CycleState {
   }
   void write(std::string_view key, std::shared_ptr<StateData> v);
   void erase(std::string_view key);
+  // A recycled state starts its next cycle: flags cleared, a fresh version
+  // (every reader's memo is stale), and the entries set aside for reuse().
+  void reset();
+  // Last cycle's object of this key and type if reset() set one aside, else a
+  // new T. The caller overwrites every field: nothing of the earlier cycle
+  // may show through. Only for state the cycle's owner alone still references
+  // once the cycle is over (the scheduler recycles a state after its last user).
+  template <typename T>
+  std::shared_ptr<T> reuse(std::string_view key) {
+    {
+      std::unique_lock<std::shared_mutex> g(mu_);
+      for (auto& kv : spare_)
+        if (kv.second && *kv.first == key)
+          if (auto p = std::dynamic_pointer_cast<T>(kv.second)) {
+            kv.second.reset();
+            return p;
+          }
+    }
+    return std::make_shared<T>();
+  }
   std::shared_ptr<CycleState> clone() const;
   bool record_metrics = false;
   bool skip_filter_plugins_mark = false;
@@ -181,6 +201,7 @@ class CycleState {
   std::atomic<uint64_t> version_;
   // Keys are interned (IStr): a clone copies pointers, not strings.
   std::vector<std::pair<const std::string*, std::shared_ptr<StateData>>> kv_;
+  std::vector<std::pair<const std::string*, std::shared_ptr<StateData>>> spare_;  // reset(): for reuse()
 };
 using CycleStatePtr = std::shared_ptr<CycleState>;
 

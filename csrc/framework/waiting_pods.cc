@@ -1,5 +1,6 @@
 #include "framework/waiting_pods.h"
 
+#include <algorithm>
 #include <vector>
 
 namespace xsched {
@@ -7,41 +8,88 @@ namespace xsched {
 std::vector<std::string> WaitingPod::pending_plugins() const {
   std::lock_guard<AdaptiveMutex> g(mu_);
   std::vector<std::string> out;
-  for (const auto& kv : pending_) out.push_back(kv.first);
+  for (const Pending& e : pending_)
+    if (e.plugin) out.push_back(*e.plugin);
+  for (const Pending& e : more_)
+    if (e.plugin) out.push_back(*e.plugin);
+  std::sort(out.begin(), out.end());  // by plugin name, as the map this replaced
   return out;
 }
 
+// Entries keep their position (a timeout names its entry by index): taking
+// one clears it in place.
+void WaitingPod::add_pending(const std::string* plugin, uint64_t timer) {
+  for (Pending& e : pending_)
+    if (!e.plugin) {
+      e = Pending{plugin, timer};
+      ++npending_;
+      return;
+    }
+  more_.push_back(Pending{plugin, timer});
+  ++npending_;
+}
+
+uint64_t WaitingPod::take_pending(const std::string& plugin) {
+  auto take = [&](Pending& e) {
+    uint64_t id = e.timer;
+    e = Pending{};
+    --npending_;
+    return id;
+  };
+  for (Pending& e : pending_)
+    if (e.plugin && *e.plugin == plugin) return take(e);
+  for (Pending& e : more_)
+    if (e.plugin && *e.plugin == plugin) return take(e);
+  return 0;
+}
+
+void WaitingPod::on_timeout(const std::shared_ptr<void>& self, int index) {
+  WaitingPod* wp = static_cast<WaitingPod*>(self.get());
+  const std::string* plugin = nullptr;
+  {
+    std::lock_guard<AdaptiveMutex> g(wp->mu_);
+    if (index < kInlinePending) plugin = wp->pending_[index].plugin;
+    else if (static_cast<size_t>(index - kInlinePending) < wp->more_.size()) plugin = wp->more_[index - kInlinePending].plugin;
+  }
+  if (plugin) wp->reject(*plugin, "rejected due to timeout after waiting at permit");
+}
+
 bool WaitingPod::allow(const std::string& plugin) {
-  std::vector<uint64_t> cancel;
+  uint64_t cancel = 0;
   {
     std::lock_guard<AdaptiveMutex> g(mu_);
     if (done_) return false;
-    auto it = pending_.find(plugin);
-    if (it != pending_.end()) {
-      cancel.push_back(it->second);
-      pending_.erase(it);
-    }
-    if (!pending_.empty()) {
-      for (uint64_t id : cancel) owner_->timers_->cancel(id);
+    cancel = take_pending(plugin);
+    if (npending_ > 0) {
+      if (cancel) owner_->timers_->cancel(cancel);
       return false;
     }
     done_ = true;
   }
-  for (uint64_t id : cancel) owner_->timers_->cancel(id);
+  if (cancel) owner_->timers_->cancel(cancel);
   resolve(Status());
   return true;
 }
 
 bool WaitingPod::reject(const std::string& plugin, const std::string& msg) {
-  std::vector<uint64_t> cancel;
+  uint64_t cancel[kInlinePending];
+  int n = 0;
+  std::vector<uint64_t> more;
   {
     std::lock_guard<AdaptiveMutex> g(mu_);
     if (done_) return false;
     done_ = true;
-    for (const auto& kv : pending_) cancel.push_back(kv.second);
-    pending_.clear();
+    for (Pending& e : pending_) {
+      if (e.plugin) cancel[n++] = e.timer;
+      e = Pending{};
+    }
+    for (Pending& e : more_)
+      if (e.plugin) more.push_back(e.timer);
+    more_.clear();
+    npending_ = 0;
   }
-  for (uint64_t id : cancel) owner_->timers_->cancel(id);
+  for (int i = 0; i < n; ++i) owner_->timers_->cancel(cancel[i]);
+  for (uint64_t id : more) owner_->timers_->cancel(id);
   resolve(Status(Code::Unschedulable, msg).with_plugin(plugin));
   return true;
 }
@@ -56,27 +104,50 @@ void WaitingPod::resolve(const Status& st) {
   if (cb) cb(st);
 }
 
-WaitingPodPtr WaitingPods::add(const PodPtr& pod, const std::string& node, const std::map<std::string, int64_t>& timeouts,
+WaitingPodPtr WaitingPods::add(const PodPtr& pod, const std::string& node, const Timeout* timeouts, size_t n,
                                WaitingPod::Done on_done) {
   auto wp = std::make_shared<WaitingPod>(pod, node, this);
   wp->on_done_ = std::move(on_done);
   wp->created_us_ = timers_->clock().now_us();
   {
     std::lock_guard<AdaptiveMutex> g(mu_);
-    pods_[pod->uid()] = wp;
-    if (pod->pg_key) by_group_[pod->pg_key].push_back(wp);
+    if (auto it = pods_.find(pod->uid()); it != pods_.end()) {
+      it->second = wp;
+    } else if (spare_pods_.empty()) {
+      pods_.emplace(pod->uid(), wp);
+    } else {
+      auto nh = std::move(spare_pods_.back());
+      spare_pods_.pop_back();
+      nh.key().assign(pod->uid());
+      nh.mapped() = wp;
+      pods_.insert(std::move(nh));
+    }
+    if (pod->pg_key) {
+      auto git = by_group_.find(pod->pg_key);
+      if (git == by_group_.end()) {
+        if (spare_groups_.empty()) {
+          git = by_group_.try_emplace(pod->pg_key).first;
+        } else {
+          auto nh = std::move(spare_groups_.back());
+          spare_groups_.pop_back();
+          nh.key() = pod->pg_key;
+          git = by_group_.insert(std::move(nh)).position;
+        }
+      }
+      git->second.push_back(wp);
+    }
   }
   // Arm timers after registration so a zero timeout cannot fire before the
   // pod is visible to IterateOverWaitingPods.
   std::lock_guard<AdaptiveMutex> g(wp->mu_);
-  for (const auto& kv : timeouts) {
-    std::string plugin = kv.first;
-    std::weak_ptr<WaitingPod> weak = wp;
-    uint64_t id = timers_->schedule_after(kv.second, [weak, plugin] {
-      if (auto p = weak.lock())
-        p->reject(plugin, "rejected due to timeout after waiting at permit");
-    });
-    wp->pending_[plugin] = id;
+  for (size_t i = 0; i < n; ++i) {
+    // The entry this timer will name: the first free inline slot, else the
+    // next position of more_ (add_pending fills the same one).
+    int index = 0;
+    while (index < WaitingPod::kInlinePending && wp->pending_[index].plugin) ++index;
+    if (index == WaitingPod::kInlinePending) index += static_cast<int>(wp->more_.size());
+    uint64_t id = timers_->schedule_after(timeouts[i].timeout_us, &WaitingPod::on_timeout, std::weak_ptr<WaitingPod>(wp), index);
+    wp->add_pending(timeouts[i].plugin, id);
   }
   return wp;
 }
@@ -98,13 +169,26 @@ void WaitingPods::iterate(const std::function<void(const WaitingPodPtr&)>& fn) c
 }
 
 void WaitingPods::iterate_group(uint64_t pg_key, const std::function<void(const WaitingPodPtr&)>& fn) const {
-  std::vector<WaitingPodPtr> snap;
+  thread_local std::vector<WaitingPodPtr> scratch;
+  thread_local bool scratch_busy = false;
+  std::vector<WaitingPodPtr> nested;
+  const bool mine = !scratch_busy;
+  std::vector<WaitingPodPtr>& snap = mine ? scratch : nested;
   {
     std::lock_guard<AdaptiveMutex> g(mu_);
     auto it = by_group_.find(pg_key);
     if (it == by_group_.end()) return;
-    snap = it->second;
+    snap.assign(it->second.begin(), it->second.end());
   }
+  struct Release {
+    std::vector<WaitingPodPtr>& v;
+    bool mine;
+    ~Release() {
+      v.clear();  // the references go, the buffer stays
+      if (mine) scratch_busy = false;
+    }
+  } release{snap, mine};
+  if (mine) scratch_busy = true;
   for (const auto& wp : snap) fn(wp);
 }
 
@@ -127,10 +211,15 @@ void WaitingPods::remove(const std::string& uid) {
           v.pop_back();
           break;
         }
-      if (v.empty()) by_group_.erase(git);
+      if (v.empty()) {
+        auto nh = by_group_.extract(git);
+        if (spare_groups_.size() < kSpareNodes) spare_groups_.push_back(std::move(nh));
+      }
     }
   }
-  pods_.erase(it);
+  auto nh = pods_.extract(it);
+  nh.mapped().reset();
+  if (spare_pods_.size() < kSpareNodes) spare_pods_.push_back(std::move(nh));
 }
 
 void WaitingPods::reject_all(const std::string& msg) {

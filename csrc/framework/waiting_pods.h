@@ -16,6 +16,7 @@
 #include <mutex>
 #include <string>
 #include <unordered_map>
+#include <vector>
 
 #include "common/clock.h"
 #include "framework/types.h"
@@ -44,8 +45,23 @@ class WaitingPod : public std::enable_shared_from_this<WaitingPod> {
   PodPtr pod_;
   std::string node_;
   WaitingPods* owner_;
+  // Plugins still to allow the pod, each with its timeout's timer id. One or
+  // two in practice: held inline, more spill to `more_`.
+  struct Pending {
+    const std::string* plugin = nullptr;  // interned (Plugin::name_ptr)
+    uint64_t timer = 0;
+  };
+  static constexpr int kInlinePending = 4;
+  void add_pending(const std::string* plugin, uint64_t timer);
+  // Removes `plugin`'s entry; its timer id, or 0 if it was not pending.
+  uint64_t take_pending(const std::string& plugin);
+  // Timeout of pending entry `index` (the timer's argument).
+  static void on_timeout(const std::shared_ptr<void>& self, int index);
+
   mutable AdaptiveMutex mu_;
-  std::map<std::string, uint64_t> pending_;  // plugin -> timer id
+  Pending pending_[kInlinePending];
+  int npending_ = 0;           // live entries of pending_ (plugin != nullptr)
+  std::vector<Pending> more_;  // beyond kInlinePending
   bool done_ = false;
   Done on_done_;
   int64_t created_us_ = 0;
@@ -55,13 +71,20 @@ using WaitingPodPtr = std::shared_ptr<WaitingPod>;
 class WaitingPods {
  public:
   explicit WaitingPods(TimerService* timers) : timers_(timers) {}
-  // Registers a waiting pod with plugin->timeout_us; on_done fires once.
-  WaitingPodPtr add(const PodPtr& pod, const std::string& node, const std::map<std::string, int64_t>& timeouts,
+  // A plugin that answered Wait, with its timeout.
+  struct Timeout {
+    const std::string* plugin;  // interned (Plugin::name_ptr)
+    int64_t timeout_us;
+  };
+  // Registers a waiting pod with its `n` plugin timeouts; on_done fires once.
+  WaitingPodPtr add(const PodPtr& pod, const std::string& node, const Timeout* timeouts, size_t n,
                     WaitingPod::Done on_done);
   WaitingPodPtr get(const std::string& uid) const;
   void iterate(const std::function<void(const WaitingPodPtr&)>& fn) const;
   // Waiting pods whose Pod::pg_key is `pg_key` (callers still compare the
   // group name: the key is a 64-bit hash). O(group), not O(all waiting).
+  // `fn` runs without the lock, on a per-thread snapshot of the group (its
+  // buffer is reused; a nested call from `fn` takes a snapshot of its own).
   void iterate_group(uint64_t pg_key, const std::function<void(const WaitingPodPtr&)>& fn) const;
   size_t size() const;
   // Reject every waiting pod (shutdown).
@@ -72,8 +95,15 @@ class WaitingPods {
   void remove(const std::string& uid);
   TimerService* timers_;
   mutable AdaptiveMutex mu_;
-  std::unordered_map<std::string, WaitingPodPtr> pods_;
-  std::unordered_map<uint64_t, std::vector<WaitingPodPtr>> by_group_;
+  using Pods = std::unordered_map<std::string, WaitingPodPtr>;
+  using Groups = std::unordered_map<uint64_t, std::vector<WaitingPodPtr>>;
+  Pods pods_;
+  Groups by_group_;
+  // Map nodes of removed entries (a pod's uid buffer, a group's vector
+  // capacity), reused by the next add(); under mu_.
+  static constexpr size_t kSpareNodes = 4096;
+  std::vector<Pods::node_type> spare_pods_;
+  std::vector<Groups::node_type> spare_groups_;
 };
 
 }  // namespace xsched

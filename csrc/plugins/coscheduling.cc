@@ -971,8 +971,12 @@ class Coscheduling : public Plugin {
   void note_outstanding(const Pod& p, int64_t remaining) {
     if (!gated(p.gpu_demand)) return;
     std::lock_guard<std::mutex> g(park_mu_);
-    erase_outstanding_locked(p.pg_key);
-    Owed& o = outstanding_[p.pg_key];
+    // The entry is rewritten in place (each waiting member of a gang comes
+    // here): same result as erase + insert, without the map node per call.
+    auto it = outstanding_.find(p.pg_key);
+    if (it != outstanding_.end()) owed_[kind_slot(it->second.kind)] -= it->second.units;
+    else it = outstanding_.try_emplace(p.pg_key).first;
+    Owed& o = it->second;
     o.kind = p.gpu_demand.kind;
     o.units = units_for(p.gpu_demand, remaining);
     o.at_us = h_.clock->now_us();

@@ -27,6 +27,7 @@
 //     fail after Filter passed) and k > 1 GPUs are supported.
 #include <algorithm>
 #include <cstdint>
+#include <cstdio>
 #include <string>
 
 #include "common/log.h"
@@ -44,18 +45,24 @@ struct Placement {
   std::vector<int> gpus;
   std::vector<std::pair<int, int>> parts;
   bool ok() const { return !gpus.empty(); }
+  void clear() {
+    gpus.clear();
+    parts.clear();
+  }
 };
+// The place_* functions fill a caller's Placement (cleared first): Reserve
+// keeps one per thread, so its vectors are grown once, not per pod.
 
 // k untouched GPUs; NUMA-local when possible (the NUMA node with the fewest
 // free GPUs that still fits, i.e. bin-pack sockets), lowest indexes first.
-Placement place_whole(const GpuLedger& L, int64_t k) {
-  Placement pl;
+void place_whole(const GpuLedger& L, int64_t k, Placement& pl) {
+  pl.clear();
   if (k <= 0) k = 1;
   // Free GPUs per NUMA node, counted in place (no per-call containers: this
   // runs in every whole-GPU pod's Reserve).
   int n_free = 0;
   for (int g = 0; g < L.gpu_count; ++g) n_free += L.whole_gpu_free(g);
-  if (n_free < k) return pl;
+  if (n_free < k) return;
   // The NUMA node with the fewest free GPUs that still fits (lowest id among
   // equals); -1 ("unknown") never qualifies. Used only when the free GPUs
   // span more than one NUMA value or sit on one known node.
@@ -80,7 +87,6 @@ Placement place_whole(const GpuLedger& L, int64_t k) {
   const bool by_numa = distinct > 1 || (distinct == 1 && first_numa >= 0);
   for (int g = 0; g < L.gpu_count && static_cast<int64_t>(pl.gpus.size()) < k; ++g)
     if (L.whole_gpu_free(g) && (!by_numa || best_numa == INT32_MIN || L.numa[g] == best_numa)) pl.gpus.push_back(g);
-  return pl;
 }
 
 // x XCDs from exclusive partitions of one GPU. The GPU is chosen by
@@ -94,9 +100,9 @@ int xcd_waste(const GpuLedger& L, int g, int64_t x) {
 }
 
 // `build` false: only *waste_out is wanted (Score), no placement vectors.
-Placement place_xcd(const GpuLedger& L, int64_t x, int* waste_out = nullptr, bool build = true) {
-  Placement pl;
-  if (x <= 0) return pl;
+void place_xcd(const GpuLedger& L, int64_t x, Placement& pl, int* waste_out = nullptr, bool build = true) {
+  pl.clear();
+  if (x <= 0) return;
   int best_g = -1, best_free = 1 << 30, best_waste = 1 << 30;
   for (int g = 0; g < L.gpu_count; ++g) {
     if (L.monopoly[g] > 0) continue;
@@ -114,13 +120,12 @@ Placement place_xcd(const GpuLedger& L, int64_t x, int* waste_out = nullptr, boo
     }
   }
   if (waste_out) *waste_out = best_g < 0 ? 0 : best_waste;
-  if (best_g < 0 || !build) return pl;
+  if (best_g < 0 || !build) return;
   int xpp = L.xcds_per_part(best_g);
   int need = static_cast<int>((x + xpp - 1) / xpp);
   for (int p = 0; p < L.parts[best_g] && static_cast<int>(pl.parts.size()) < need; ++p)
     if (L.slot_free(best_g, p)) pl.parts.emplace_back(best_g, p);
   pl.gpus.push_back(best_g);
-  return pl;
 }
 
 // Memory slice on the partition with the least remaining memory after
@@ -128,8 +133,8 @@ Placement place_xcd(const GpuLedger& L, int64_t x, int* waste_out = nullptr, boo
 // breaks an untouched SPX GPU while any other partition can take it: that GPU
 // is the only kind a whole-GPU (training-rank) pod can use.
 // `build` false: only *breaks_whole is wanted (Score), no placement vectors.
-Placement place_memory(const GpuLedger& L, int64_t m, bool* breaks_whole = nullptr, bool build = true) {
-  Placement pl;
+void place_memory(const GpuLedger& L, int64_t m, Placement& pl, bool* breaks_whole = nullptr, bool build = true) {
+  pl.clear();
   int bg = -1, bp = -1;
   int64_t best_remain = 0;
   bool best_breaks = true;
@@ -153,30 +158,54 @@ Placement place_memory(const GpuLedger& L, int64_t m, bool* breaks_whole = nullp
     }
   }
   if (breaks_whole) *breaks_whole = bg >= 0 && best_breaks;
-  if (bg < 0 || !build) return pl;
+  if (bg < 0 || !build) return;
   pl.gpus.push_back(bg);
   pl.parts.emplace_back(bg, bp);
-  return pl;
 }
 
-Placement place(const GpuLedger& L, const Demand& d) {
+void place(const GpuLedger& L, const Demand& d, Placement& pl) {
   switch (d.kind) {
-    case Demand::Gpu: return place_whole(L, d.amount);
-    case Demand::Xcd: return place_xcd(L, d.amount);
-    case Demand::Memory: return place_memory(L, d.amount);
-    default: return {};
+    case Demand::Gpu: return place_whole(L, d.amount, pl);
+    case Demand::Xcd: return place_xcd(L, d.amount, pl);
+    case Demand::Memory: return place_memory(L, d.amount, pl);
+    default: pl.clear();
+  }
+}
+
+// Both write into `s` (cleared first, its buffer kept).
+void append_int(std::string& s, int v) {
+  char buf[16];
+  int n = std::snprintf(buf, sizeof buf, "%d", v);
+  s.append(buf, static_cast<size_t>(n));
+}
+
+void join_ints(const std::vector<int>& v, std::string& s) {
+  s.clear();
+  for (size_t i = 0; i < v.size(); ++i) {
+    if (i) s += ',';
+    append_int(s, v[i]);
+  }
+}
+
+void join_parts(const std::vector<std::pair<int, int>>& v, std::string& s) {
+  s.clear();
+  for (size_t i = 0; i < v.size(); ++i) {
+    if (i) s += ',';
+    append_int(s, v[i].first);
+    s += ':';
+    append_int(s, v[i].second);
   }
 }
 
 std::string join_ints(const std::vector<int>& v) {
   std::string s;
-  for (size_t i = 0; i < v.size(); ++i) s += (i ? "," : "") + std::to_string(v[i]);
+  join_ints(v, s);
   return s;
 }
 
 std::string join_parts(const std::vector<std::pair<int, int>>& v) {
   std::string s;
-  for (size_t i = 0; i < v.size(); ++i) s += (i ? "," : "") + std::to_string(v[i].first) + ":" + std::to_string(v[i].second);
+  join_parts(v, s);
   return s;
 }
 
@@ -281,13 +310,15 @@ class FlexGPU : public Plugin {
         // Stranded XCDs dominate: a node that can host the slice without
         // waste always outranks one that would burn a whole SPX GPU on it.
         int waste = 0;
-        place_xcd(ni.gpu, d.amount, &waste, /*build=*/false);
+        Placement none;  // build=false: stays empty
+        place_xcd(ni.gpu, d.amount, none, &waste, /*build=*/false);
         return {ni.gpu.free_xcds() + 64 * waste, {}};
       }
       case Demand::Memory: {
         // Breaking a whole SPX GPU for a slice costs more than any packing gain.
         bool breaks = false;
-        place_memory(ni.gpu, d.amount, &breaks, /*build=*/false);
+        Placement none;  // build=false: stays empty
+        place_memory(ni.gpu, d.amount, none, &breaks, /*build=*/false);
         return {ni.gpu.free_memory() + (breaks ? 8 * ni.gpu.mem_per_gpu : 0), {}};
       }
       default: return {0, {}};
@@ -305,16 +336,20 @@ class FlexGPU : public Plugin {
     if (d.kind == Demand::Conflict) return Status::unresolvable("pod conflict resources");
     NodeInfoPtr ni = h_.snapshot ? h_.snapshot->get(node) : nullptr;
     if (!ni) return Status::error("getting node \"" + node + "\" from Snapshot");
-    Placement pl = place(ni->gpu, d);
+    // Reserve runs on a scheduling thread; per thread, so a debug cycle on
+    // another thread does not share the scratch.
+    thread_local Placement pl;
+    place(ni->gpu, d, pl);
     if (!pl.ok()) return Status::unschedulable("allocate index fail");
     XS_LOGV(6, "assigned gpu indexes").kv("pod", p->key()).kv("node", node).kv("indexes", join_ints(pl.gpus))
         .kv("partitions", join_parts(pl.parts));
     const GpuNames& gn = gn_;
-    auto st = std::make_shared<AssignmentState>();
-    st->index = join_ints(pl.gpus);
-    if (!pl.parts.empty()) st->partitions = join_parts(pl.parts);
+    auto st = s.reuse<AssignmentState>(kFlexGPUStateKey);
+    join_ints(pl.gpus, st->index);
+    join_parts(pl.parts, st->partitions);  // empty for whole-GPU / HBM pods
     h_.cache->annotate_assumed_pod(p->uid(), [&](Pod& cp) {
       StrMap& am = cp.meta.annotations.mut();
+      am.reserve(am.size() + 2);  // one growth for the (at most) two entries
       auto put = [&](const std::string& k, const std::string& v) {
         for (auto& a : am)
           if (a.first == k) {

@@ -95,7 +95,7 @@ class TopologyMatch : public Plugin {
       return {};
     auto pg = h_.informers->pod_group_of(p);
     if (!pg || pg->min_member <= 1) return {};
-    GangPlacement::Plan plan = h_.gangs->plan(*h_.snapshot, p, pg->min_member);
+    GangPlacement::Plan plan = h_.gangs->plan(*h_.snapshot, p, pg->min_member, &s);
     if (!plan.gang) return {};
     if (!plan.started && h_.gang_planned) h_.gang_planned(p, plan.hostable);
     if (!plan.restriction) return {};
@@ -347,7 +347,14 @@ class TopologyMatch : public Plugin {
   // and one assigned-count read per cycle instead of per node).
   Status pre_score(CycleState& s, const Pod& p, const NodeList&) override {
     if (strategy_ != Strategy::XGMI) return {};
-    auto ctx = std::make_shared<GangCtx>();
+    auto ctx = s.reuse<GangCtx>(kGangKey);  // a recycled state's last one, every field reset
+    ctx->gang = false;
+    ctx->key = 0;
+    ctx->remaining = 0;
+    ctx->kind = GangCtx::kWhole;
+    ctx->amount = 0;
+    ctx->hosts.clear();
+    ctx->hosts_known = false;
     if (!p.pod_group.empty()) {
       auto pg = h_.informers->pod_group_of(p);
       const GpuDemand& d = p.gpu_demand;

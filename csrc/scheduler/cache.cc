@@ -24,8 +24,68 @@ NodeInfo& SchedulerCache::writable(NodeInfoPtr& slot) {
   return *slot;
 }
 
+// dirty_ and pod_states_ gain and lose one node per scheduled pod: their map
+// nodes (and the key strings' buffers) go round through spare lists instead
+// of the allocator.
+void SchedulerCache::dirty_insert(const std::string& node) {
+  if (dirty_.count(node)) return;
+  if (spare_dirty_.empty()) {
+    dirty_.insert(node);
+    return;
+  }
+  auto nh = std::move(spare_dirty_.back());
+  spare_dirty_.pop_back();
+  nh.value().assign(node);
+  dirty_.insert(std::move(nh));
+}
+
+void SchedulerCache::dirty_clear() {
+  while (!dirty_.empty()) {
+    auto nh = dirty_.extract(dirty_.begin());
+    if (spare_dirty_.size() < kSpareNodes) spare_dirty_.push_back(std::move(nh));
+  }
+}
+
+void SchedulerCache::set_assumed(PodState& st, bool assumed) {
+  if (st.assumed != assumed) assumed_n_ += assumed ? 1 : -1;
+  st.assumed = assumed;
+}
+
+void SchedulerCache::insert_state_locked(const PodPtr& p, bool assumed) {
+  PodStates::iterator it;
+  if (spare_states_.empty()) {
+    it = pod_states_.insert_or_assign(p->uid(), PodState{p, 0, false, false}).first;
+  } else {
+    auto nh = std::move(spare_states_.back());
+    spare_states_.pop_back();
+    nh.key().assign(p->uid());
+    nh.mapped() = PodState{p, 0, false, false};
+    auto r = pod_states_.insert(std::move(nh));
+    it = r.position;
+    if (!r.inserted) {  // callers look the uid up first; kept for safety
+      set_assumed(it->second, false);
+      it->second = PodState{p, 0, false, false};
+    }
+  }
+  set_assumed(it->second, assumed);
+  pod_count_.store(pod_states_.size(), std::memory_order_relaxed);
+}
+
+void SchedulerCache::erase_state_locked(PodStates::iterator it) {
+  set_assumed(it->second, false);
+  auto nh = pod_states_.extract(it);
+  nh.mapped() = PodState{};
+  if (spare_states_.size() < kSpareNodes) spare_states_.push_back(std::move(nh));
+  pod_count_.store(pod_states_.size(), std::memory_order_relaxed);
+}
+
+bool SchedulerCache::assumed_locked(const std::string& uid) const {
+  auto it = pod_states_.find(uid);
+  return it != pod_states_.end() && it->second.assumed;
+}
+
 void SchedulerCache::mark_dirty(const std::string& node) {
-  dirty_.insert(node);
+  dirty_insert(node);
   auto it = nodes_.find(node);
   if (it != nodes_.end()) writable(it->second).generation = ++generation_;
 }
@@ -33,17 +93,48 @@ void SchedulerCache::mark_dirty(const std::string& node) {
 void SchedulerCache::group_delta(const Pod& p, int d) {
   if (!p.pg_key) return;
   std::lock_guard<AdaptiveMutex> g(group_mu_);
-  auto it = group_assigned_.try_emplace(p.pg_key, 0).first;
+  // A gang's entries come and go with it: the two maps' nodes (and a host
+  // list's capacity) are reused by the next gang.
+  auto it = group_assigned_.find(p.pg_key);
+  if (it == group_assigned_.end()) {
+    if (spare_group_assigned_.empty()) {
+      it = group_assigned_.try_emplace(p.pg_key, 0).first;
+    } else {
+      auto nh = std::move(spare_group_assigned_.back());
+      spare_group_assigned_.pop_back();
+      nh.key() = p.pg_key;
+      nh.mapped() = 0;
+      it = group_assigned_.insert(std::move(nh)).position;
+    }
+  }
   it->second += d;
-  if (it->second <= 0) group_assigned_.erase(it);
-  auto& hosts = group_nodes_[p.pg_key];
+  if (it->second <= 0) {
+    auto nh = group_assigned_.extract(it);
+    if (spare_group_assigned_.size() < kSpareNodes) spare_group_assigned_.push_back(std::move(nh));
+  }
+  auto git = group_nodes_.find(p.pg_key);
+  if (git == group_nodes_.end()) {
+    if (spare_group_nodes_.empty()) {
+      git = group_nodes_.try_emplace(p.pg_key).first;
+    } else {
+      auto nh = std::move(spare_group_nodes_.back());
+      spare_group_nodes_.pop_back();
+      nh.key() = p.pg_key;
+      nh.mapped().clear();
+      git = group_nodes_.insert(std::move(nh)).position;
+    }
+  }
+  auto& hosts = git->second;
   auto h = std::find_if(hosts.begin(), hosts.end(), [&](const auto& e) { return e.first == p.node_name; });
   if (h == hosts.end()) {
     if (d > 0) hosts.emplace_back(p.node_name, d);
   } else if ((h->second += d) <= 0) {
     hosts.erase(h);
   }
-  if (hosts.empty()) group_nodes_.erase(p.pg_key);
+  if (hosts.empty()) {
+    auto nh = group_nodes_.extract(git);
+    if (spare_group_nodes_.size() < kSpareNodes) spare_group_nodes_.push_back(std::move(nh));
+  }
 }
 
 int SchedulerCache::group_placement(uint64_t pg_key, std::vector<std::string>& hosts) const {
@@ -134,7 +225,7 @@ void SchedulerCache::remove_node(const std::string& name) {
   } else {
     writable(it->second).node = nullptr;  // ghost until its pods are deleted
   }
-  dirty_.insert(name);
+  dirty_insert(name);
 }
 
 void SchedulerCache::set_nrt(const std::string& node, const NRTPtr& nrt) {
@@ -178,7 +269,7 @@ void SchedulerCache::remove_pod_locked(const PodPtr& p) {
     if (pit != prio_count_.end() && --pit->second <= 0) prio_count_.erase(pit);
   }
   // mark_dirty, with the node already found and writable.
-  dirty_.insert(p->node_name);
+  dirty_insert(p->node_name);
   ni.generation = ++generation_;
   if (ni.node == nullptr && ni.pods.empty()) nodes_.erase(it);
 }
@@ -189,16 +280,14 @@ Status SchedulerCache::assume_pod(const PodPtr& p) {
   in_place_ = true;
   add_pod_locked(p);
   in_place_ = false;
-  pod_states_[p->uid()] = PodState{p, 0, false};
-  pod_count_.store(pod_states_.size(), std::memory_order_relaxed);
-  assumed_.insert(p->uid());
+  insert_state_locked(p, /*assumed=*/true);
   return {};
 }
 
 void SchedulerCache::finish_binding(const Pod& p) {
   std::lock_guard<AdaptiveMutex> g(mu_);
   auto it = pod_states_.find(p.uid());
-  if (it == pod_states_.end() || !assumed_.count(p.uid())) return;
+  if (it == pod_states_.end() || !it->second.assumed) return;
   it->second.binding_finished = true;
   it->second.deadline_us = clock_->now_us() + ttl_us_;
 }
@@ -207,12 +296,10 @@ void SchedulerCache::forget_pod(const Pod& p) {
   std::lock_guard<AdaptiveMutex> g(mu_);
   auto it = pod_states_.find(p.uid());
   if (it == pod_states_.end()) return;
-  if (!assumed_.count(p.uid())) return;  // only assumed pods can be forgotten
+  if (!it->second.assumed) return;  // only assumed pods can be forgotten
   PodPtr cur = it->second.pod;
   remove_pod_locked(cur);
-  assumed_.erase(p.uid());
-  pod_states_.erase(it);
-  pod_count_.store(pod_states_.size(), std::memory_order_relaxed);
+  erase_state_locked(it);
 }
 
 namespace {
@@ -227,7 +314,7 @@ bool same_accounting(const Pod& assumed, const Pod& bound) {
 }
 }  // namespace
 
-bool SchedulerCache::confirm_assumed_locked(std::unordered_map<std::string, PodState>::iterator it, const PodPtr& p) {
+bool SchedulerCache::confirm_assumed_locked(PodStates::iterator it, const PodPtr& p) {
   if (!same_accounting(*it->second.pod, *p)) return false;
   // The node's NodeInfo already holds an equivalent object: leave it (and its
   // generation, so equivalence-cache verdicts for the node stay valid) and
@@ -236,8 +323,8 @@ bool SchedulerCache::confirm_assumed_locked(std::unordered_map<std::string, PodS
   // (victim ordering, PreemptionToleration's toleration window).
   it->second.pod->scheduled_at = p->scheduled_at;
   it->second.pod->start_time = p->start_time;
-  assumed_.erase(p->uid());
-  it->second = PodState{p, 0, false};
+  set_assumed(it->second, false);
+  it->second = PodState{p, 0, false, false};
   return true;
 }
 
@@ -245,14 +332,14 @@ void SchedulerCache::add_pod(const PodPtr& p) {
   std::lock_guard<AdaptiveMutex> g(mu_);
   auto it = pod_states_.find(p->uid());
   if (it != pod_states_.end()) {
-    if (assumed_.count(p->uid())) {
+    if (it->second.assumed) {
       if (confirm_assumed_locked(it, p)) return;
       // Confirmation of an assumed pod: replace with the informer's object
       // (it carries the bound annotations) on the node it was bound to.
       remove_pod_locked(it->second.pod);
       add_pod_locked(p);
-      assumed_.erase(p->uid());
-      it->second = PodState{p, 0, false};
+      set_assumed(it->second, false);
+      it->second = PodState{p, 0, false, false};
     } else {
       remove_pod_locked(it->second.pod);
       add_pod_locked(p);
@@ -261,8 +348,7 @@ void SchedulerCache::add_pod(const PodPtr& p) {
     return;
   }
   add_pod_locked(p);
-  pod_states_[p->uid()] = PodState{p, 0, false};
-  pod_count_.store(pod_states_.size(), std::memory_order_relaxed);
+  insert_state_locked(p, /*assumed=*/false);
 }
 
 void SchedulerCache::update_pod(const PodPtr& old_pod, const PodPtr& new_pod) {
@@ -270,17 +356,16 @@ void SchedulerCache::update_pod(const PodPtr& old_pod, const PodPtr& new_pod) {
   auto it = pod_states_.find(new_pod->uid());
   if (it == pod_states_.end()) {
     add_pod_locked(new_pod);
-    pod_states_[new_pod->uid()] = PodState{new_pod, 0, false};
-    pod_count_.store(pod_states_.size(), std::memory_order_relaxed);
+    insert_state_locked(new_pod, /*assumed=*/false);
     return;
   }
-  if (assumed_.count(new_pod->uid())) {
+  if (it->second.assumed) {
     // An update for an assumed pod means it got bound: confirm it.
     if (confirm_assumed_locked(it, new_pod)) return;
     remove_pod_locked(it->second.pod);
     add_pod_locked(new_pod);
-    assumed_.erase(new_pod->uid());
-    it->second = PodState{new_pod, 0, false};
+    set_assumed(it->second, false);
+    it->second = PodState{new_pod, 0, false, false};
     return;
   }
   remove_pod_locked(it->second.pod);
@@ -293,9 +378,7 @@ void SchedulerCache::remove_pod(const Pod& p) {
   auto it = pod_states_.find(p.uid());
   if (it == pod_states_.end()) return;
   remove_pod_locked(it->second.pod);
-  assumed_.erase(p.uid());
-  pod_states_.erase(it);
-  pod_count_.store(pod_states_.size(), std::memory_order_relaxed);
+  erase_state_locked(it);
 }
 
 void SchedulerCache::remove_pods(const std::vector<PodPtr>& ps) {
@@ -304,15 +387,13 @@ void SchedulerCache::remove_pods(const std::vector<PodPtr>& ps) {
     auto it = pod_states_.find(p->uid());
     if (it == pod_states_.end()) continue;
     remove_pod_locked(it->second.pod);
-    assumed_.erase(p->uid());
-    pod_states_.erase(it);
-    pod_count_.store(pod_states_.size(), std::memory_order_relaxed);
+    erase_state_locked(it);
   }
 }
 
 bool SchedulerCache::is_assumed(const std::string& uid) const {
   std::lock_guard<AdaptiveMutex> g(mu_);
-  return assumed_.count(uid) > 0;
+  return assumed_locked(uid);
 }
 
 PodPtr SchedulerCache::get_pod(const std::string& uid) const {
@@ -334,19 +415,19 @@ PodPtr SchedulerCache::mutate_pod(const std::string& uid, const std::function<vo
   return fresh;
 }
 
-PodPtr SchedulerCache::annotate_assumed_pod(const std::string& uid, const std::function<void(Pod&)>& fn,
-                                            bool recompute) {
+PodPtr SchedulerCache::annotate_assumed_pod_impl(const std::string& uid, void (*fn)(Pod&, void*), void* ctx,
+                                                 bool recompute) {
   {
     std::lock_guard<AdaptiveMutex> g(mu_);
     auto it = pod_states_.find(uid);
     if (it == pod_states_.end()) return nullptr;
     auto nit = nodes_.find(it->second.pod->node_name);
-    if (assumed_.count(uid) && !it->second.binding_finished && nit != nodes_.end()) {
+    if (it->second.assumed && !it->second.binding_finished && nit != nodes_.end()) {
       PodPtr pod = it->second.pod;
       in_place_ = true;  // scheduling thread, same cycle as assume_pod
       NodeInfo& ni = writable(nit->second);
       ni.gpu.apply(pod->gpu, -1);
-      fn(*pod);
+      fn(*pod, ctx);
       if (recompute) pod->recompute_gpu_assignment(*gpu_names_);
       ni.gpu.apply(pod->gpu, +1);
       mark_dirty(pod->node_name);
@@ -354,7 +435,7 @@ PodPtr SchedulerCache::annotate_assumed_pod(const std::string& uid, const std::f
       return pod;
     }
   }
-  return mutate_pod(uid, fn);
+  return mutate_pod(uid, [fn, ctx](Pod& p) { fn(p, ctx); });
 }
 
 namespace {
@@ -397,7 +478,7 @@ int SchedulerCache::update_snapshot(Snapshot& s, int64_t* lock_wait_us, const st
   int64_t t0 = lock_wait_us ? clock_->now_us() : 0;
   std::lock_guard<AdaptiveMutex> g(mu_);
   if (lock_wait_us) *lock_wait_us = clock_->now_us() - t0;
-  if (check_assumed && is_assumed) *is_assumed = assumed_.count(*check_assumed) > 0;
+  if (check_assumed && is_assumed) *is_assumed = assumed_locked(*check_assumed);
   int clones = 0;
   if (structure_changed_) {
     for (auto& ni : s.nodes) s.retired.push_back(std::move(ni));
@@ -451,7 +532,7 @@ int SchedulerCache::update_snapshot(Snapshot& s, int64_t* lock_wait_us, const st
       sync_affinity_lists(s, i);
     }
   }
-  dirty_.clear();
+  dirty_clear();
   if (s.deltas_wanted && !track_deltas_) {
     // Events were not recorded so far: jump the sequence past the log so
     // no state memoized before now can be replayed.
@@ -478,19 +559,14 @@ int SchedulerCache::update_snapshot(Snapshot& s, int64_t* lock_wait_us, const st
 void SchedulerCache::cleanup_expired_assumed_pods() {
   std::lock_guard<AdaptiveMutex> g(mu_);
   int64_t now = clock_->now_us();
+  if (assumed_n_ == 0) return;  // the usual case: nothing to walk
   std::vector<std::string> expired;
-  for (const auto& uid : assumed_) {
-    auto it = pod_states_.find(uid);
-    if (it == pod_states_.end()) continue;
-    if (it->second.binding_finished && it->second.deadline_us > 0 && now > it->second.deadline_us)
-      expired.push_back(uid);
-  }
+  for (const auto& [uid, st] : pod_states_)
+    if (st.assumed && st.binding_finished && st.deadline_us > 0 && now > st.deadline_us) expired.push_back(uid);
   for (const auto& uid : expired) {
     auto it = pod_states_.find(uid);
     remove_pod_locked(it->second.pod);
-    assumed_.erase(uid);
-    pod_states_.erase(it);
-    pod_count_.store(pod_states_.size(), std::memory_order_relaxed);
+    erase_state_locked(it);
   }
 }
 
@@ -509,7 +585,7 @@ size_t SchedulerCache::pod_count() const { return pod_count_.load(std::memory_or
 
 size_t SchedulerCache::assumed_count() const {
   std::lock_guard<AdaptiveMutex> g(mu_);
-  return assumed_.size();
+  return assumed_n_;
 }
 
 NodeInfoPtr SchedulerCache::node_info_copy(const std::string& name) const {
@@ -534,10 +610,9 @@ std::vector<SchedulerCache::GpuCensusRow> SchedulerCache::gpu_census() const {
     row.emplace(name, out.size());
     out.push_back(std::move(r));
   }
-  for (const auto& uid : assumed_) {
-    auto it = pod_states_.find(uid);
-    if (it == pod_states_.end()) continue;
-    const Pod& p = *it->second.pod;
+  for (const auto& [uid, st] : pod_states_) {
+    if (!st.assumed) continue;
+    const Pod& p = *st.pod;
     if (p.gpu_demand.kind != GpuDemand::Gpu) continue;
     auto r = row.find(p.node_name);
     if (r != row.end()) out[r->second].assumed_whole += static_cast<int>(p.gpu_demand.amount);
@@ -569,7 +644,7 @@ Json SchedulerCache::check(const std::vector<PodPtr>& assigned, const std::vecto
   size_t assumed_n = 0;
   for (const auto& [uid, st] : pod_states_) {
     auto it = truth.find(uid);
-    if (assumed_.count(uid)) {
+    if (st.assumed) {
       ++assumed_n;  // not bound yet, or bound and not confirmed: either is fine
       if (it != truth.end() && it->second->node_name != st.pod->node_name)
         wrong.push_back(st.pod->key() + ": cache " + st.pod->node_name + ", listers " + it->second->node_name);
@@ -644,7 +719,7 @@ Json SchedulerCache::dump() const {
     Json n = Json::object();
     n.set("name", Json(name));
     Json pods = Json::array();
-    for (const auto& p : ni.pods) pods.push_back(Json(p->key() + (assumed_.count(p->uid()) ? " (assumed)" : "")));
+    for (const auto& p : ni.pods) pods.push_back(Json(p->key() + (assumed_locked(p->uid()) ? " (assumed)" : "")));
     n.set("pods", std::move(pods));
     Json req = Json::object();
     for (uint64_t m = ni.requested.mask; m; m &= m - 1) {
@@ -665,7 +740,7 @@ Json SchedulerCache::dump() const {
   }
   out.set("nodes", std::move(ns));
   out.set("pods", Json(static_cast<int64_t>(pod_states_.size())));
-  out.set("assumed", Json(static_cast<int64_t>(assumed_.size())));
+  out.set("assumed", Json(static_cast<int64_t>(assumed_n_)));
   return out;
 }
 

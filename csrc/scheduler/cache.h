@@ -69,7 +69,14 @@ class SchedulerCache {
   // mutate_pod for pods that are not (or no longer) assumed.
   // `fn` edits the assumed pod's annotations in place; with `recompute` the
   // GPU assignment is then re-derived from them (false: fn set it).
-  PodPtr annotate_assumed_pod(const std::string& uid, const std::function<void(Pod&)>& fn, bool recompute = true);
+  // `fn` is called in place (no std::function: Reserve calls this per pod).
+  template <class F>
+  PodPtr annotate_assumed_pod(const std::string& uid, F&& fn, bool recompute = true) {
+    using Fn = std::remove_reference_t<F>;
+    return annotate_assumed_pod_impl(
+        uid, [](Pod& p, void* ctx) { (*static_cast<Fn*>(ctx))(p); },
+        const_cast<void*>(static_cast<const void*>(&fn)), recompute);
+  }
 
   // Returns the number of NodeInfo versions refreshed (shared, not cloned:
   // the cache copies on write); replaced versions go to `s.retired`; `lock_wait_us` (optional)
@@ -119,11 +126,20 @@ class SchedulerCache {
     PodPtr pod;
     int64_t deadline_us = 0;
     bool binding_finished = false;
+    bool assumed = false;  // counted in assumed_n_ (set_assumed)
   };
+  using PodStates = std::unordered_map<std::string, PodState>;
+  PodPtr annotate_assumed_pod_impl(const std::string& uid, void (*fn)(Pod&, void*), void* ctx, bool recompute);
+  void set_assumed(PodState& st, bool assumed);
+  void insert_state_locked(const PodPtr& p, bool assumed);
+  void erase_state_locked(PodStates::iterator it);
+  bool assumed_locked(const std::string& uid) const;
+  void dirty_insert(const std::string& node);
+  void dirty_clear();
   // Bind confirmation of an assumed pod whose informer object accounts the
   // same on its node: records it without touching the NodeInfo (no copy, no
   // generation bump). False when the node must be re-accounted.
-  bool confirm_assumed_locked(std::unordered_map<std::string, PodState>::iterator it, const PodPtr& p);
+  bool confirm_assumed_locked(PodStates::iterator it, const PodPtr& p);
   NodeInfoPtr& info_for(const std::string& node);  // creates a ghost entry
   NodeInfo& writable(NodeInfoPtr& slot);            // copy-on-write before mutating
   bool in_place_ = false;  // assume/annotate on the scheduling thread (under mu_)
@@ -143,9 +159,13 @@ class SchedulerCache {
   mutable AdaptiveMutex mu_;
   std::unordered_map<std::string, NodeInfoPtr> nodes_;
   std::vector<std::string> order_;  // node names with a Node object, insertion order
-  std::unordered_map<std::string, PodState> pod_states_;
+  PodStates pod_states_;
+  size_t assumed_n_ = 0;  // entries of pod_states_ with `assumed`
+  // Map nodes of erased entries, reused by the next insert (under mu_).
+  static constexpr size_t kSpareNodes = 4096;
+  std::vector<PodStates::node_type> spare_states_;
+  std::vector<std::unordered_set<std::string>::node_type> spare_dirty_;
   std::atomic<size_t> pod_count_{0};  // pod_states_.size(), readable without mu_
-  std::unordered_set<std::string> assumed_;
   // Written under mu_ + group_mu_, read under group_mu_ only: Permit and
   // PreScore read a gang's count without waiting behind NodeInfo copies.
   mutable AdaptiveMutex group_mu_;
@@ -153,6 +173,9 @@ class SchedulerCache {
   // PodGroup key -> (node, members on it): where a gang's assumed or bound
   // members sit (XGMIGangAffinity's co-location test without a per-node look).
   std::unordered_map<uint64_t, std::vector<std::pair<std::string, int>>> group_nodes_;
+  // Spare map nodes of the two (under group_mu_).
+  std::vector<std::unordered_map<uint64_t, int>::node_type> spare_group_assigned_;
+  std::vector<std::unordered_map<uint64_t, std::vector<std::pair<std::string, int>>>::node_type> spare_group_nodes_;
   std::unordered_set<std::string> dirty_;
   bool structure_changed_ = true;
   int64_t generation_ = 0;

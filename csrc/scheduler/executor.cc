@@ -92,10 +92,24 @@ namespace {
 thread_local Executor::Batch* tl_batch = nullptr;
 }  // namespace
 
-Executor::Batch::Batch(Executor& e) : e_(e), prev_(tl_batch) { tl_batch = this; }
+// A batch per scheduling cycle: its (emptied) task buffer is kept per thread
+// for the next one instead of growing a new vector every cycle.
+thread_local std::vector<std::function<void()>> tl_batch_spare;
+
+Executor::Batch::Batch(Executor& e) : e_(e), prev_(tl_batch) {
+  tl_batch = this;
+  fns_.swap(tl_batch_spare);
+}
 
 Executor::Batch::~Batch() {
   tl_batch = prev_;
+  struct KeepBuffer {
+    std::vector<std::function<void()>>& v;
+    ~KeepBuffer() {
+      v.clear();
+      if (v.capacity() > tl_batch_spare.capacity()) v.swap(tl_batch_spare);
+    }
+  } keep{fns_};
   if (fns_.empty()) return;
   bool wake = false;
   {

@@ -72,26 +72,19 @@ void GangPlacement::reservations_locked(const Snapshot& s, uint64_t self, GpuDem
   }
 }
 
-std::shared_ptr<NodeRestriction> GangPlacement::take_restriction(size_t nodes) {
-  // A small ring of restriction objects reused once no cycle holds them (a
-  // binding cycle keeps its CycleState, and so the restriction, alive until
-  // the bind): no allocation per gang rank in steady state.
-  for (size_t k = 0; k < pool_.size(); ++k) {
-    auto& r = pool_[(pool_next_ + k) % pool_.size()];
-    if (r && r.use_count() == 1) {
-      pool_next_ = (pool_next_ + k + 1) % pool_.size();
-      r->list.clear();
-      r->mask.clear();
-      r->nodes = nodes;
-      r->fallback = true;
-      return r;
-    }
-  }
-  auto r = std::make_shared<NodeRestriction>();
-  r->list.reserve(kList);
+std::shared_ptr<NodeRestriction> GangPlacement::take_restriction(size_t nodes, CycleState* cs) {
+  // The restriction is written into the cycle's state and lives as long as
+  // that state does (through the binding cycle). A recycled state hands its
+  // last one back through reuse(), with its buffers: no allocation per gang
+  // rank in steady state, and no guess from a reference count about who
+  // still reads the object.
+  auto r = cs ? cs->reuse<NodeRestriction>(kNodeRestrictionKey) : std::make_shared<NodeRestriction>();
+  r->list.clear();
+  r->mask.clear();
+  if (r->list.capacity() < kList) r->list.reserve(kList);
   r->nodes = nodes;
-  if (pool_.size() < kPool) pool_.push_back(r);
-  else pool_[pool_next_++ % kPool] = r;
+  r->fallback = true;
+  r->excluded = Status();
   return r;
 }
 
@@ -152,7 +145,7 @@ int GangPlacement::scan(const Snapshot& s, const GpuDemand& d, int64_t members,
   return count;
 }
 
-GangPlacement::Plan GangPlacement::plan(const Snapshot& s, const Pod& p, int min_member) {
+GangPlacement::Plan GangPlacement::plan(const Snapshot& s, const Pod& p, int min_member, CycleState* cs) {
   Plan out;
   const GpuDemand& d = p.gpu_demand;
   if (mode_ == Mode::Off || !gang_demand(d) || min_member <= 1 || p.pg_key == 0) return out;
@@ -201,7 +194,7 @@ GangPlacement::Plan GangPlacement::plan(const Snapshot& s, const Pod& p, int min
     }
     out.hostable = na > 0;
     if (na > 0 || no > 0) {
-      auto r = take_restriction(n);
+      auto r = take_restriction(n, cs);
       const int* src = na > 0 ? all_fit : one_fit;
       r->list.assign(src, src + (na > 0 ? na : no));
       std::sort(r->list.begin(), r->list.end());
@@ -213,7 +206,7 @@ GangPlacement::Plan GangPlacement::plan(const Snapshot& s, const Pod& p, int min
     }
   }
   // Nodes that take every remaining rank.
-  auto r = take_restriction(n);
+  auto r = take_restriction(n, cs);
   r->fallback = !required;
   const int count = scan(s, d, out.remaining, res, &r->mask, &r->list);
   if (!out.started) out.hostable = count > 0;

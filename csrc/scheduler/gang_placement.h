@@ -62,8 +62,10 @@ class GangPlacement {
     std::shared_ptr<NodeRestriction> restriction;  // null: no restriction
   };
   // PreFilter (scheduling thread, `s` refreshed for the cycle). Registers
-  // p's gang as in flight.
-  Plan plan(const Snapshot& s, const Pod& p, int min_member);
+  // p's gang as in flight. `cs`: the cycle's state, which the caller writes
+  // the restriction into; a recycled state's previous restriction object is
+  // reused (null: a new one).
+  Plan plan(const Snapshot& s, const Pod& p, int min_member, CycleState* cs = nullptr);
   // Can one node take `remaining` ranks of p's kind now, counting the ranks
   // owed to anchored gangs (Coscheduling's gate in Required mode)?
   bool hostable(const Snapshot& s, const Pod& p, int64_t remaining);
@@ -88,14 +90,11 @@ class GangPlacement {
   int scan(const Snapshot& s, const GpuDemand& d, int64_t members, const std::vector<std::pair<int, int64_t>>& res,
            std::vector<char>* out_mask, std::vector<int>* out_list) const;
 
-  // A restriction object from pool_ that no cycle holds any more (caller
-  // holds mu_).
-  std::shared_ptr<NodeRestriction> take_restriction(size_t nodes);
+  // An empty restriction for `nodes` nodes: the one `cs` set aside for
+  // reuse, else a new object.
+  static std::shared_ptr<NodeRestriction> take_restriction(size_t nodes, CycleState* cs);
 
   static constexpr size_t kList = 16;  // restrictions up to this size are position lists
-  static constexpr size_t kPool = 64;
-  std::vector<std::shared_ptr<NodeRestriction>> pool_;
-  size_t pool_next_ = 0;
 
   SchedulerCache* cache_;
   std::shared_ptr<Clock> clock_;

@@ -57,12 +57,81 @@ Scheduler::CycleMetrics& Scheduler::cycle_metrics(const Framework& fw) {
 
 // Activates the siblings plugins stashed in the cycle state (scheduler.go:543-548).
 void Scheduler::activate_stashed(PodsToActivate& stash) {
-  std::vector<PodPtr> act;
+  // The stash's buffer goes back to it afterwards (a recycled frame's stash
+  // keeps its capacity); `act` is per thread: scheduling and binder threads
+  // both come here.
+  thread_local std::vector<PodPtr> act;
+  act.clear();
   {
     std::lock_guard<std::mutex> g(stash.mu);
     act.swap(stash.pods);
   }
   if (!act.empty()) queue_->activate(act);
+  act.clear();
+  std::lock_guard<std::mutex> g(stash.mu);
+  if (stash.pods.capacity() < act.capacity() && stash.pods.empty()) act.swap(stash.pods);
+}
+
+Scheduler::CycleFrame* Scheduler::take_frame() {
+  if (!idle_frames_) {
+    idle_frames_ = returned_frames_.exchange(nullptr, std::memory_order_acquire);
+    idle_frame_count_ = 0;
+    // Keep at most kMaxIdleFrames of them: a burst of parked gangs must not
+    // pin its peak number of frames for good.
+    for (CycleFrame* f = idle_frames_; f; f = f->next) {
+      if (++idle_frame_count_ < kMaxIdleFrames) continue;
+      CycleFrame* rest = f->next;
+      f->next = nullptr;
+      while (rest) {
+        CycleFrame* n = rest->next;
+        delete rest;
+        rest = n;
+      }
+    }
+  }
+  CycleFrame* f = idle_frames_;
+  if (!f) return new CycleFrame();
+  idle_frames_ = f->next;
+  --idle_frame_count_;
+  f->next = nullptr;
+  f->state.reset();
+  {
+    std::lock_guard<std::mutex> g(f->to_activate->mu);
+    f->to_activate->pods.clear();
+  }
+  return f;
+}
+
+void Scheduler::keep_idle(CycleFrame* f) {
+  f->task.qpi.reset();
+  f->task.assumed.reset();
+  if (idle_frame_count_ >= kMaxIdleFrames) {
+    delete f;
+    return;
+  }
+  f->next = idle_frames_;
+  idle_frames_ = f;
+  ++idle_frame_count_;
+}
+
+void Scheduler::hand_back_frame(CycleFrame* f) {
+  f->task.qpi.reset();
+  f->task.assumed.reset();
+  CycleFrame* head = returned_frames_.load(std::memory_order_relaxed);
+  do {
+    f->next = head;
+  } while (!returned_frames_.compare_exchange_weak(head, f, std::memory_order_release, std::memory_order_relaxed));
+}
+
+void Scheduler::free_frames() {
+  for (CycleFrame* f : {idle_frames_, returned_frames_.exchange(nullptr, std::memory_order_acquire)})
+    while (f) {
+      CycleFrame* n = f->next;
+      delete f;
+      f = n;
+    }
+  idle_frames_ = nullptr;
+  idle_frame_count_ = 0;
 }
 
 Status Scheduler::score_feasible(Framework& fw, CycleState& s, const Pod& p, const NodeList& feasible,
@@ -92,11 +161,23 @@ void Scheduler::schedule_cycle(const QueuedPodInfoPtr& qpi) {
   }
 
   int64_t cycle_start = clock_->now_us();
-  auto state = std::make_shared<CycleState>();
+  // The cycle's frame goes back to the idle list on every return below,
+  // unless the binding cycle took it over.
+  struct FrameLease {
+    Scheduler* self;
+    CycleFrame* frame;
+    ~FrameLease() {
+      if (frame) self->keep_idle(frame);
+    }
+  } lease{this, take_frame()};
+  CycleFrame* frame = lease.frame;
+  CycleState* state = &frame->state;
   state->record_metrics = std::uniform_real_distribution<double>(0, 1)(rng_) < opts_.metrics_sample_rate;
   nom_changed_.clear();
   if (!nominator_->empty()) state->nominated = nominator_->view(&nom_changed_);
-  auto to_activate = std::make_shared<PodsToActivate>();
+  // A reference of the cycle's own: the tail below still stashes and
+  // activates after the binding cycle may have handed the frame back.
+  std::shared_ptr<PodsToActivate> to_activate = frame->to_activate;
   state->write(kPodsToActivateKey, to_activate);
   int64_t cycle = queue_->scheduling_cycle();
   if (tracer_.enabled())
@@ -204,19 +285,21 @@ void Scheduler::schedule_cycle(const QueuedPodInfoPtr& qpi) {
   // Permit.
   int64_t permit_start = clock_->now_us();
   inflight_.fetch_add(1);
-  auto task = std::make_shared<BindTask>();
+  BindTask* task = &frame->task;
   task->self = this;
   task->fw = fw;
-  task->state = state;
+  task->frame = frame;
   task->qpi = qpi;
   task->assumed = assumed;
-  task->host = host;
+  task->host.assign(host);
   task->cycle = cycle;
   task->permit_start_us = permit_start;
-  task->to_activate = to_activate;
   task->e2e = cycle_metrics(*fw).e2e;
-  task->keep = task;
-  BindTask* tp = task.get();
+  task->permit_status = Status();
+  BindTask* tp = task;
+  // From here the frame belongs to the binding cycle (run_bind_task hands it
+  // back), unless Permit rejects the pod before any waiting.
+  lease.frame = nullptr;
   // The binding cycles this Permit releases (the gang's waiting members and
   // this pod) reach the binder pool in one hand-over.
   std::optional<Executor::Batch> batch(std::in_place, *binder_);
@@ -225,7 +308,7 @@ void Scheduler::schedule_cycle(const QueuedPodInfoPtr& qpi) {
     tp->self->binder_->submit([tp] { run_bind_task(tp); });
   });
   if (!pst.is_success() && !pst.is_wait()) {
-    task->keep.reset();  // rejected before waiting: the callback never runs
+    lease.frame = frame;  // rejected before waiting: the callback never runs
     inflight_.fetch_sub(1);
     fail_assumed(*fw, *state, qpi, assumed, pst, pst.is_unschedulable() ? "Unschedulable" : "SchedulerError", cycle,
                  cnt_.unschedulable, false);
@@ -250,8 +333,9 @@ void Scheduler::schedule_cycle(const QueuedPodInfoPtr& qpi) {
 }
 
 void Scheduler::run_bind_task(BindTask* t) {
-  std::shared_ptr<BindTask> hold = std::move(t->keep);
-  t->self->binding_cycle(*t, t->permit_status);
+  Scheduler* self = t->self;
+  self->binding_cycle(*t, t->permit_status);
+  self->hand_back_frame(t->frame);  // the frame's last user
 }
 
 // Replaced snapshot versions may hold the last reference to deleted pods;
@@ -303,12 +387,12 @@ Scheduler::BindMetrics& Scheduler::bind_metrics() {
 
 void Scheduler::binding_cycle(const BindTask& t, const Status& permit_status) {
   Framework* fw = t.fw;
-  const CycleStatePtr& s = t.state;
+  CycleState* s = &t.frame->state;
   const QueuedPodInfoPtr& qpi = t.qpi;
   const PodPtr& assumed = t.assumed;
   const std::string& host = t.host;
   const int64_t cycle = t.cycle, wait_start_us = t.permit_start_us;
-  const std::shared_ptr<PodsToActivate>& to_activate = t.to_activate;
+  const std::shared_ptr<PodsToActivate>& to_activate = t.frame->to_activate;
   int64_t t0 = clock_->now_us();
   auto fail = [&](const Status& st, const std::string& reason) {
     fail_assumed(*fw, *s, qpi, assumed, st, reason, cycle, cnt_.bind_failures, true);

@@ -174,7 +174,10 @@ Scheduler::Scheduler(std::shared_ptr<ObjectStore> store, const Json& config, std
   for (const auto& ev : initial) handle_event(ev);
 }
 
-Scheduler::~Scheduler() { stop(); }
+Scheduler::~Scheduler() {
+  stop();
+  free_frames();
+}
 
 void Scheduler::start() {
   if (running_.exchange(true)) return;

@@ -408,26 +408,50 @@ class Scheduler {
   BindMetrics bind_metrics_;
   std::mutex bind_metrics_mu_;
   BindMetrics& bind_metrics();
-  // Everything the binding cycle of one assumed pod needs, in one heap
-  // object: the Permit continuation and the binder task capture only this
-  // pointer (fits std::function's inline buffer, no per-closure allocation).
+  // Everything the binding cycle of one assumed pod needs. It lives in the
+  // cycle's frame: the Permit continuation and the binder task capture only
+  // this pointer (fits std::function's inline buffer, no per-closure
+  // allocation).
+  struct CycleFrame;
   struct BindTask {
     Scheduler* self = nullptr;
     Framework* fw = nullptr;
-    CycleStatePtr state;
+    CycleFrame* frame = nullptr;  // holds this task, the CycleState and the PodsToActivate
     QueuedPodInfoPtr qpi;
     PodPtr assumed;
     std::string host;
     int64_t cycle = 0;
     int64_t permit_start_us = 0;
-    std::shared_ptr<PodsToActivate> to_activate;
     Histogram* e2e = nullptr;  // scheduler_e2e_scheduling_duration_seconds{profile}
     Status permit_status;      // set by the Permit waiter before the task is queued
-    // The task owns itself until its binding cycle starts, so the Permit
-    // callback and the binder queue hold a raw pointer: a one-pointer capture
-    // is stored inside std::function, without a heap block per pod.
-    std::shared_ptr<BindTask> keep;
   };
+  // What one scheduling cycle and its binding cycle work on, recycled: taken
+  // at the top of schedule_cycle, handed back by its last user (the cycle
+  // itself when it ends before Permit passes, else the binder thread after
+  // the binding cycle), and then reused with the capacity of everything
+  // inside. Nothing outside the two cycles keeps a pointer into a frame: the
+  // assumed Pod is an object of its own (the cache holds it until the
+  // informer confirms it), a WaitingPod's continuation is gone once it ran,
+  // and tracer and gang records copy what they keep.
+  struct CycleFrame {
+    CycleState state;
+    std::shared_ptr<PodsToActivate> to_activate = std::make_shared<PodsToActivate>();
+    BindTask task;
+    CycleFrame* next = nullptr;  // free-list link
+  };
+  // Idle frames. Only the thread in a scheduling cycle (under sched_mu_)
+  // takes frames, from idle_frames_; when that is empty it takes over
+  // everything handed back so far. Binder threads push onto returned_frames_
+  // (release; the take-over is an acquire exchange of the whole list, so
+  // there is no ABA window).
+  CycleFrame* idle_frames_ = nullptr;
+  size_t idle_frame_count_ = 0;
+  std::atomic<CycleFrame*> returned_frames_{nullptr};
+  static constexpr size_t kMaxIdleFrames = 4096;
+  CycleFrame* take_frame();              // under sched_mu_
+  void keep_idle(CycleFrame* f);         // under sched_mu_
+  void hand_back_frame(CycleFrame* f);   // any thread
+  void free_frames();                    // destructor
   static void run_bind_task(BindTask* t);
   void binding_cycle(const BindTask& t, const Status& permit_status);
   // An assumed pod fails after Reserve: Unreserve, forget it in the cache,

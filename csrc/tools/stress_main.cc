@@ -24,6 +24,7 @@
 #include "rest/kube.h"
 #include "scheduler/openloop.h"
 #include "scheduler/scheduler.h"
+#include "tools/alloc_count.h"
 #include "tools/sampler.h"
 
 using namespace xsched;
@@ -186,6 +187,10 @@ int main(int argc, char** argv) {
   double total_s = 0;
   size_t total_pods = 0;
   const bool has_init = std::filesystem::exists(dir + "/init.json");
+  // The counting flavour (build_ext --stress-count, tools/alloc_count.cc)
+  // counts operator new/delete per thread after XSCHED_ALLOC_WARMUP waves.
+  const int count_after = std::getenv("XSCHED_ALLOC_WARMUP") ? std::atoi(std::getenv("XSCHED_ALLOC_WARMUP")) : 4;
+  uint64_t counted_pods = 0;
   auto wait_bound = [&](uint64_t target, const char* what, int w) {
     auto deadline = std::chrono::steady_clock::now() + std::chrono::seconds(120);
     while (sched.stats().bound < target) {
@@ -199,6 +204,7 @@ int main(int argc, char** argv) {
     return true;
   };
   for (int w = 0; w < waves; ++w) {
+    if (alloc_count::enable && w == count_after) alloc_count::enable(true);
     if (has_init) {
       if (sample_path) sampler::pause(true);
       Json init = Json::parse(slurp(dir + "/init.json"));
@@ -256,6 +262,7 @@ int main(int argc, char** argv) {
     }
     auto t_bound = std::chrono::steady_clock::now();
     bound += expect;
+    if (w >= count_after) counted_pods += expect;
     std::string ns = wave["namespace"].str_or("bench");
     store->delete_all("pods", has_init ? std::string() : ns);  // init pods may live in other namespaces
     store->delete_all("podgroups", ns);
@@ -269,7 +276,9 @@ int main(int argc, char** argv) {
                 s, n / s, ms(t_created - t0), ms(t_bound - t_created), ms(t_end - t_bound));
   }
   if (sample_path) sampler::dump(sample_path);
+  if (alloc_count::enable) alloc_count::enable(false);
   sched.stop();
+  if (alloc_count::report) alloc_count::report(stdout, counted_pods);
   std::printf("total: %zu pods in %.4fs (%.0f pods/s)\n", total_pods, total_s, total_pods / total_s);
   return 0;
 }

@@ -10,6 +10,7 @@ Usage:
     python -m flex_gpu_scheduler_amd.build_ext            # core + hip
     python -m flex_gpu_scheduler_amd.build_ext --core     # C++ core only
     python -m flex_gpu_scheduler_amd.build_ext --tsan     # ThreadSanitizer stress driver
+    python -m flex_gpu_scheduler_amd.build_ext --stress-count  # allocation-counting stress driver
 """
 from __future__ import annotations
 
@@ -218,6 +219,30 @@ def build_prof(verbose: bool = True, gprof: bool = True, debuginfo: bool = False
     return out
 
 
+def build_stress_count(verbose: bool = True, debuginfo: bool = False) -> Path:
+    """The stress driver linked with the counting operator new/delete
+    (csrc/tools/alloc_count.cc): allocations per thread and per bound pod.
+    Same flags as the extension's objects, so the core objects are shared with
+    build/core (no second compile of the core); `debuginfo` compiles its own
+    with line tables, for the optional call stacks (XSCHED_ALLOC_STACKS=1,
+    scripts/alloc_stacks.py)."""
+    includes = [str(CSRC)]
+    extra = ["-g1", "-fno-omit-frame-pointer"] if debuginfo else []
+    srcs = core_sources() + [CSRC / "tools" / "stress_main.cc", CSRC / "tools" / "alloc_count.cc"]
+    objs = build_objects(srcs, BUILD / ("stress_count_g" if debuginfo else "core"), extra, includes)
+    out = BUILD / ("xsched_stress_count_g" if debuginfo else "xsched_stress_count")
+    newest = max(o.stat().st_mtime for o in objs)
+    if out.exists() and out.stat().st_mtime >= newest:
+        return out
+    cmd = ["g++", "-pthread", *[str(o) for o in objs], *LINK_LIBS, "-ldl", "-o", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"stress-count link failed:\n{r.stderr[-8000:]}")
+    if verbose:
+        print(f"[build_ext] built {out.relative_to(ROOT)}")
+    return out
+
+
 def build_tests(verbose: bool = True) -> Path:
     """Native unit-test binary (csrc/tests/native_tests.cc)."""
     # Same flags as the extension's objects, so the core objects are shared
@@ -246,6 +271,9 @@ def main(argv: list[str] | None = None) -> int:
     ap.add_argument("--prof", action="store_true")
     ap.add_argument("--stress", action="store_true")
     ap.add_argument("--stress-g", action="store_true", help="stress driver with -g (sample_report --lines)")
+    ap.add_argument("--stress-count", action="store_true",
+                    help="stress driver with the counting operator new/delete (allocations per thread)")
+    ap.add_argument("--stress-count-g", action="store_true", help="the same with line tables (call stacks)")
     ap.add_argument("--tests", action="store_true")
     ap.add_argument("--core-g", action="store_true", help="the extension with -g into dbg/ (sampling runs)")
     a = ap.parse_args(argv)
@@ -254,6 +282,9 @@ def main(argv: list[str] | None = None) -> int:
         return 0
     if a.tests:
         build_tests()
+        return 0
+    if a.stress_count or a.stress_count_g:
+        build_stress_count(debuginfo=a.stress_count_g)
         return 0
     if a.prof or a.stress or a.stress_g:
         build_prof(gprof=a.prof, debuginfo=a.stress_g)
