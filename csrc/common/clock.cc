@@ -21,38 +21,6 @@ void TimerService::stop() {
   if (th_.joinable() && std::this_thread::get_id() != th_.get_id()) th_.join();
 }
 
-std::multimap<int64_t, uint64_t>::iterator TimerService::heap_insert(int64_t deadline_us, uint64_t id) {
-  if (spare_heap_.empty()) return heap_.emplace(deadline_us, id);
-  auto nh = std::move(spare_heap_.back());
-  spare_heap_.pop_back();
-  nh.key() = deadline_us;
-  nh.mapped() = id;
-  return heap_.insert(std::move(nh));
-}
-
-void TimerService::heap_erase(std::multimap<int64_t, uint64_t>::iterator it) {
-  auto nh = heap_.extract(it);
-  if (spare_heap_.size() < kSpareNodes) spare_heap_.push_back(std::move(nh));
-}
-
-void TimerService::timer_insert(uint64_t id, Timer&& t) {
-  if (spare_timers_.empty()) {
-    timers_.emplace(id, std::move(t));
-    return;
-  }
-  auto nh = std::move(spare_timers_.back());
-  spare_timers_.pop_back();
-  nh.key() = id;
-  nh.mapped() = std::move(t);
-  timers_.insert(std::move(nh));
-}
-
-void TimerService::timer_erase(std::unordered_map<uint64_t, Timer>::iterator it) {
-  auto nh = timers_.extract(it);
-  nh.mapped() = Timer{};  // drops the callable and the target reference
-  if (spare_timers_.size() < kSpareNodes) spare_timers_.push_back(std::move(nh));
-}
-
 uint64_t TimerService::schedule_at(int64_t deadline_us, Fn fn) {
   Timer t;
   t.fn = std::move(fn);
@@ -73,12 +41,12 @@ uint64_t TimerService::arm(int64_t deadline_us, Timer&& t) {
   {
     std::lock_guard<AdaptiveMutex> g(mu_);
     id = next_id_++;
-    t.pos = heap_insert(deadline_us, id);
+    t.pos = heap_.acquire(deadline_us, id);
     // The loop sleeps until the earliest deadline; a later one needs no
     // wake-up (Permit timeouts arrive in deadline order, so this skips a
     // futex wake per waiting gang member).
     earliest = t.pos == heap_.begin();
-    timer_insert(id, std::move(t));
+    timers_.acquire(id).first->second = std::move(t);
     if (earliest) ++change_gen_;
   }
   if (earliest) cv_.notify_one();
@@ -93,8 +61,8 @@ uint64_t TimerService::every(int64_t period_us, Fn fn) {
     Timer t;
     t.fn = std::move(fn);
     t.period_us = period_us;
-    t.pos = heap_insert(clock_->now_us() + period_us, id);
-    timer_insert(id, std::move(t));
+    t.pos = heap_.acquire(clock_->now_us() + period_us, id);
+    timers_.acquire(id).first->second = std::move(t);
     ++change_gen_;
   }
   cv_.notify_one();
@@ -105,8 +73,8 @@ bool TimerService::cancel(uint64_t id) {
   std::lock_guard<AdaptiveMutex> g(mu_);
   auto it = timers_.find(id);
   if (it == timers_.end()) return false;
-  if (it->second.pos != heap_.end()) heap_erase(it->second.pos);
-  timer_erase(it);
+  if (it->second.pos != heap_.end()) heap_.release(it->second.pos);
+  timers_.release(it);
   return true;
 }
 
@@ -125,7 +93,7 @@ void TimerService::loop() {
     if (!heap_.empty() && heap_.begin()->first <= now) {
       auto hit = heap_.begin();
       uint64_t id = hit->second;
-      heap_erase(hit);
+      heap_.release(hit);
       auto tit = timers_.find(id);
       if (tit == timers_.end()) continue;
       Fn fn;
@@ -134,11 +102,11 @@ void TimerService::loop() {
       int arg = tit->second.arg;
       if (tit->second.period_us > 0) {
         fn = tit->second.fn;
-        tit->second.pos = heap_insert(now + tit->second.period_us, id);
+        tit->second.pos = heap_.acquire(now + tit->second.period_us, id);
       } else {
         fn = std::move(tit->second.fn);
         target = std::move(tit->second.target);
-        timer_erase(tit);
+        timers_.release(tit);
       }
       running_cb_ = true;
       lk.unlock();

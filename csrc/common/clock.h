@@ -9,6 +9,7 @@
 #pragma once
 
 #include "common/adaptive_mutex.h"
+#include "common/recycled_map.h"
 
 #include <atomic>
 #include <chrono>
@@ -95,22 +96,14 @@ class TimerService {
     std::multimap<int64_t, uint64_t>::iterator pos;
   };
   void loop();
-  // Under mu_. Erased map nodes go to the spare lists and come back on the
-  // next insert.
-  std::multimap<int64_t, uint64_t>::iterator heap_insert(int64_t deadline_us, uint64_t id);
-  void heap_erase(std::multimap<int64_t, uint64_t>::iterator it);
-  void timer_insert(uint64_t id, Timer&& t);
-  void timer_erase(std::unordered_map<uint64_t, Timer>::iterator it);
   uint64_t arm(int64_t deadline_us, Timer&& t);
 
   std::shared_ptr<Clock> clock_;
   AdaptiveMutex mu_;  // schedule/cancel per waiting pod, from the scheduling and binder threads
   std::condition_variable_any cv_, drained_cv_;
-  std::multimap<int64_t, uint64_t> heap_;
-  std::unordered_map<uint64_t, Timer> timers_;
-  static constexpr size_t kSpareNodes = 4096;
-  std::vector<std::multimap<int64_t, uint64_t>::node_type> spare_heap_;
-  std::vector<std::unordered_map<uint64_t, Timer>::node_type> spare_timers_;
+  // A node of each per armed timer: recycled, under mu_.
+  RecycledMap<std::multimap<int64_t, uint64_t>> heap_;  // deadline -> id
+  RecycledMap<std::unordered_map<uint64_t, Timer>> timers_;
   uint64_t next_id_ = 1;
   bool stop_ = false;
   bool running_cb_ = false;

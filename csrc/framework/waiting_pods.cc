@@ -111,31 +111,8 @@ WaitingPodPtr WaitingPods::add(const PodPtr& pod, const std::string& node, const
   wp->created_us_ = timers_->clock().now_us();
   {
     std::lock_guard<AdaptiveMutex> g(mu_);
-    if (auto it = pods_.find(pod->uid()); it != pods_.end()) {
-      it->second = wp;
-    } else if (spare_pods_.empty()) {
-      pods_.emplace(pod->uid(), wp);
-    } else {
-      auto nh = std::move(spare_pods_.back());
-      spare_pods_.pop_back();
-      nh.key().assign(pod->uid());
-      nh.mapped() = wp;
-      pods_.insert(std::move(nh));
-    }
-    if (pod->pg_key) {
-      auto git = by_group_.find(pod->pg_key);
-      if (git == by_group_.end()) {
-        if (spare_groups_.empty()) {
-          git = by_group_.try_emplace(pod->pg_key).first;
-        } else {
-          auto nh = std::move(spare_groups_.back());
-          spare_groups_.pop_back();
-          nh.key() = pod->pg_key;
-          git = by_group_.insert(std::move(nh)).position;
-        }
-      }
-      git->second.push_back(wp);
-    }
+    pods_.acquire(pod->uid()).first->second = wp;
+    if (pod->pg_key) by_group_.acquire(pod->pg_key).first->second.push_back(wp);
   }
   // Arm timers after registration so a zero timeout cannot fire before the
   // pod is visible to IterateOverWaitingPods.
@@ -211,15 +188,10 @@ void WaitingPods::remove(const std::string& uid) {
           v.pop_back();
           break;
         }
-      if (v.empty()) {
-        auto nh = by_group_.extract(git);
-        if (spare_groups_.size() < kSpareNodes) spare_groups_.push_back(std::move(nh));
-      }
+      if (v.empty()) by_group_.release(git);
     }
   }
-  auto nh = pods_.extract(it);
-  nh.mapped().reset();
-  if (spare_pods_.size() < kSpareNodes) spare_pods_.push_back(std::move(nh));
+  pods_.release(it);
 }
 
 void WaitingPods::reject_all(const std::string& msg) {

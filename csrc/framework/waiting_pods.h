@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "common/clock.h"
+#include "common/recycled_map.h"
 #include "framework/types.h"
 
 namespace xsched {
@@ -95,15 +96,10 @@ class WaitingPods {
   void remove(const std::string& uid);
   TimerService* timers_;
   mutable AdaptiveMutex mu_;
-  using Pods = std::unordered_map<std::string, WaitingPodPtr>;
-  using Groups = std::unordered_map<uint64_t, std::vector<WaitingPodPtr>>;
-  Pods pods_;
-  Groups by_group_;
-  // Map nodes of removed entries (a pod's uid buffer, a group's vector
-  // capacity), reused by the next add(); under mu_.
-  static constexpr size_t kSpareNodes = 4096;
-  std::vector<Pods::node_type> spare_pods_;
-  std::vector<Groups::node_type> spare_groups_;
+  // An entry per waiting pod and per waiting gang comes and goes: recycled
+  // (a pod's uid buffer, a group's vector capacity), under mu_.
+  RecycledMap<std::unordered_map<std::string, WaitingPodPtr>> pods_;
+  RecycledMap<std::unordered_map<uint64_t, std::vector<WaitingPodPtr>>> by_group_;
 };
 
 }  // namespace xsched

@@ -24,58 +24,22 @@ NodeInfo& SchedulerCache::writable(NodeInfoPtr& slot) {
   return *slot;
 }
 
-// dirty_ and pod_states_ gain and lose one node per scheduled pod: their map
-// nodes (and the key strings' buffers) go round through spare lists instead
-// of the allocator.
-void SchedulerCache::dirty_insert(const std::string& node) {
-  if (dirty_.count(node)) return;
-  if (spare_dirty_.empty()) {
-    dirty_.insert(node);
-    return;
-  }
-  auto nh = std::move(spare_dirty_.back());
-  spare_dirty_.pop_back();
-  nh.value().assign(node);
-  dirty_.insert(std::move(nh));
-}
-
-void SchedulerCache::dirty_clear() {
-  while (!dirty_.empty()) {
-    auto nh = dirty_.extract(dirty_.begin());
-    if (spare_dirty_.size() < kSpareNodes) spare_dirty_.push_back(std::move(nh));
-  }
-}
-
 void SchedulerCache::set_assumed(PodState& st, bool assumed) {
   if (st.assumed != assumed) assumed_n_ += assumed ? 1 : -1;
   st.assumed = assumed;
 }
 
 void SchedulerCache::insert_state_locked(const PodPtr& p, bool assumed) {
-  PodStates::iterator it;
-  if (spare_states_.empty()) {
-    it = pod_states_.insert_or_assign(p->uid(), PodState{p, 0, false, false}).first;
-  } else {
-    auto nh = std::move(spare_states_.back());
-    spare_states_.pop_back();
-    nh.key().assign(p->uid());
-    nh.mapped() = PodState{p, 0, false, false};
-    auto r = pod_states_.insert(std::move(nh));
-    it = r.position;
-    if (!r.inserted) {  // callers look the uid up first; kept for safety
-      set_assumed(it->second, false);
-      it->second = PodState{p, 0, false, false};
-    }
-  }
+  auto [it, inserted] = pod_states_.acquire(p->uid());
+  if (!inserted) set_assumed(it->second, false);  // callers look the uid up first; kept for safety
+  it->second = PodState{p, 0, false, false};
   set_assumed(it->second, assumed);
   pod_count_.store(pod_states_.size(), std::memory_order_relaxed);
 }
 
 void SchedulerCache::erase_state_locked(PodStates::iterator it) {
   set_assumed(it->second, false);
-  auto nh = pod_states_.extract(it);
-  nh.mapped() = PodState{};
-  if (spare_states_.size() < kSpareNodes) spare_states_.push_back(std::move(nh));
+  pod_states_.release(it);
   pod_count_.store(pod_states_.size(), std::memory_order_relaxed);
 }
 
@@ -85,7 +49,7 @@ bool SchedulerCache::assumed_locked(const std::string& uid) const {
 }
 
 void SchedulerCache::mark_dirty(const std::string& node) {
-  dirty_insert(node);
+  dirty_.acquire(node);
   auto it = nodes_.find(node);
   if (it != nodes_.end()) writable(it->second).generation = ++generation_;
 }
@@ -93,37 +57,10 @@ void SchedulerCache::mark_dirty(const std::string& node) {
 void SchedulerCache::group_delta(const Pod& p, int d) {
   if (!p.pg_key) return;
   std::lock_guard<AdaptiveMutex> g(group_mu_);
-  // A gang's entries come and go with it: the two maps' nodes (and a host
-  // list's capacity) are reused by the next gang.
-  auto it = group_assigned_.find(p.pg_key);
-  if (it == group_assigned_.end()) {
-    if (spare_group_assigned_.empty()) {
-      it = group_assigned_.try_emplace(p.pg_key, 0).first;
-    } else {
-      auto nh = std::move(spare_group_assigned_.back());
-      spare_group_assigned_.pop_back();
-      nh.key() = p.pg_key;
-      nh.mapped() = 0;
-      it = group_assigned_.insert(std::move(nh)).position;
-    }
-  }
+  auto it = group_assigned_.acquire(p.pg_key).first;
   it->second += d;
-  if (it->second <= 0) {
-    auto nh = group_assigned_.extract(it);
-    if (spare_group_assigned_.size() < kSpareNodes) spare_group_assigned_.push_back(std::move(nh));
-  }
-  auto git = group_nodes_.find(p.pg_key);
-  if (git == group_nodes_.end()) {
-    if (spare_group_nodes_.empty()) {
-      git = group_nodes_.try_emplace(p.pg_key).first;
-    } else {
-      auto nh = std::move(spare_group_nodes_.back());
-      spare_group_nodes_.pop_back();
-      nh.key() = p.pg_key;
-      nh.mapped().clear();
-      git = group_nodes_.insert(std::move(nh)).position;
-    }
-  }
+  if (it->second <= 0) group_assigned_.release(it);
+  auto git = group_nodes_.acquire(p.pg_key).first;
   auto& hosts = git->second;
   auto h = std::find_if(hosts.begin(), hosts.end(), [&](const auto& e) { return e.first == p.node_name; });
   if (h == hosts.end()) {
@@ -131,10 +68,7 @@ void SchedulerCache::group_delta(const Pod& p, int d) {
   } else if ((h->second += d) <= 0) {
     hosts.erase(h);
   }
-  if (hosts.empty()) {
-    auto nh = group_nodes_.extract(git);
-    if (spare_group_nodes_.size() < kSpareNodes) spare_group_nodes_.push_back(std::move(nh));
-  }
+  if (hosts.empty()) group_nodes_.release(git);
 }
 
 int SchedulerCache::group_placement(uint64_t pg_key, std::vector<std::string>& hosts) const {
@@ -225,7 +159,7 @@ void SchedulerCache::remove_node(const std::string& name) {
   } else {
     writable(it->second).node = nullptr;  // ghost until its pods are deleted
   }
-  dirty_insert(name);
+  dirty_.acquire(name);
 }
 
 void SchedulerCache::set_nrt(const std::string& node, const NRTPtr& nrt) {
@@ -269,7 +203,7 @@ void SchedulerCache::remove_pod_locked(const PodPtr& p) {
     if (pit != prio_count_.end() && --pit->second <= 0) prio_count_.erase(pit);
   }
   // mark_dirty, with the node already found and writable.
-  dirty_insert(p->node_name);
+  dirty_.acquire(p->node_name);
   ni.generation = ++generation_;
   if (ni.node == nullptr && ni.pods.empty()) nodes_.erase(it);
 }
@@ -532,7 +466,7 @@ int SchedulerCache::update_snapshot(Snapshot& s, int64_t* lock_wait_us, const st
       sync_affinity_lists(s, i);
     }
   }
-  dirty_clear();
+  dirty_.release_all();
   if (s.deltas_wanted && !track_deltas_) {
     // Events were not recorded so far: jump the sequence past the log so
     // no state memoized before now can be replayed.

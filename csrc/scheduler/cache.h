@@ -27,6 +27,7 @@
 
 #include "common/clock.h"
 #include "common/json.h"
+#include "common/recycled_map.h"
 #include "framework/types.h"
 
 namespace xsched {
@@ -128,14 +129,12 @@ class SchedulerCache {
     bool binding_finished = false;
     bool assumed = false;  // counted in assumed_n_ (set_assumed)
   };
-  using PodStates = std::unordered_map<std::string, PodState>;
+  using PodStates = RecycledMap<std::unordered_map<std::string, PodState>>;
   PodPtr annotate_assumed_pod_impl(const std::string& uid, void (*fn)(Pod&, void*), void* ctx, bool recompute);
   void set_assumed(PodState& st, bool assumed);
   void insert_state_locked(const PodPtr& p, bool assumed);
   void erase_state_locked(PodStates::iterator it);
   bool assumed_locked(const std::string& uid) const;
-  void dirty_insert(const std::string& node);
-  void dirty_clear();
   // Bind confirmation of an assumed pod whose informer object accounts the
   // same on its node: records it without touching the NodeInfo (no copy, no
   // generation bump). False when the node must be re-accounted.
@@ -159,24 +158,19 @@ class SchedulerCache {
   mutable AdaptiveMutex mu_;
   std::unordered_map<std::string, NodeInfoPtr> nodes_;
   std::vector<std::string> order_;  // node names with a Node object, insertion order
-  PodStates pod_states_;
+  PodStates pod_states_;  // an entry per pod comes and goes: recycled, under mu_
   size_t assumed_n_ = 0;  // entries of pod_states_ with `assumed`
-  // Map nodes of erased entries, reused by the next insert (under mu_).
-  static constexpr size_t kSpareNodes = 4096;
-  std::vector<PodStates::node_type> spare_states_;
-  std::vector<std::unordered_set<std::string>::node_type> spare_dirty_;
   std::atomic<size_t> pod_count_{0};  // pod_states_.size(), readable without mu_
   // Written under mu_ + group_mu_, read under group_mu_ only: Permit and
   // PreScore read a gang's count without waiting behind NodeInfo copies.
   mutable AdaptiveMutex group_mu_;
-  std::unordered_map<uint64_t, int> group_assigned_;
+  // A gang's entries in the two come and go with it: recycled, under group_mu_.
+  RecycledMap<std::unordered_map<uint64_t, int>> group_assigned_;
   // PodGroup key -> (node, members on it): where a gang's assumed or bound
   // members sit (XGMIGangAffinity's co-location test without a per-node look).
-  std::unordered_map<uint64_t, std::vector<std::pair<std::string, int>>> group_nodes_;
-  // Spare map nodes of the two (under group_mu_).
-  std::vector<std::unordered_map<uint64_t, int>::node_type> spare_group_assigned_;
-  std::vector<std::unordered_map<uint64_t, std::vector<std::pair<std::string, int>>>::node_type> spare_group_nodes_;
-  std::unordered_set<std::string> dirty_;
+  RecycledMap<std::unordered_map<uint64_t, std::vector<std::pair<std::string, int>>>> group_nodes_;
+  // Nodes touched since the last snapshot refresh: recycled, under mu_.
+  RecycledMap<std::unordered_set<std::string>> dirty_;
   bool structure_changed_ = true;
   int64_t generation_ = 0;
   uint64_t node_epoch_ = 1;

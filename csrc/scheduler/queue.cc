@@ -225,7 +225,7 @@ void SchedulingQueue::add(const PodPtr& p) {
     unschedulable_.erase(p->uid());
     parked_.erase(p->uid());
     backoff_.erase(p->uid());
-    in_flight_erase(p->uid());
+    in_flight_.release(p->uid());
     active_.push(q);
   }
   nominator_->add(p, "");
@@ -300,7 +300,7 @@ bool SchedulingQueue::add_unschedulable_if_not_present(const QueuedPodInfoPtr& p
     uint8_t mark = kNoMark;
     if (auto f = in_flight_.find(uid); f != in_flight_.end()) {
       mark = f->second;
-      in_flight_erase(f);
+      in_flight_.release(f);
     }
     if (mark == kActivate) {
       active_.push(p);  // activated while in flight; Activate skips backoff
@@ -344,17 +344,7 @@ QueuedPodInfoPtr SchedulingQueue::pop(int timeout_ms) {
     return nullptr;
   if (closed_ && active_.empty()) return nullptr;
   QueuedPodInfoPtr q = active_.pop();
-  if (auto f = in_flight_.find(q->pod->uid()); f != in_flight_.end()) {
-    f->second = kNoMark;
-  } else if (in_flight_spare_.empty()) {
-    in_flight_.emplace(q->pod->uid(), kNoMark);
-  } else {
-    auto nh = std::move(in_flight_spare_.back());
-    in_flight_spare_.pop_back();
-    nh.key().assign(q->pod->uid());  // into the node's old buffer
-    nh.mapped() = kNoMark;
-    in_flight_.insert(std::move(nh));
-  }
+  in_flight_.acquire(q->pod->uid()).first->second = kNoMark;
   q->attempts++;
   scheduling_cycle_++;
   return q;
@@ -427,7 +417,7 @@ void SchedulingQueue::update(const PodPtr& old_p, const PodPtr& new_p) {
       }
     } else {
       // Not queued anywhere: add to activeQ (it may have been in flight).
-      in_flight_erase(uid);
+      in_flight_.release(uid);
       auto q = new_info(new_p);
       q->enqueue_seq = ++seq_;
       active_.push(q);
@@ -447,7 +437,7 @@ void SchedulingQueue::remove(const Pod& p) {
   backoff_.erase(p.uid());
   unschedulable_.erase(p.uid());
   parked_.erase(p.uid());
-  in_flight_erase(p.uid());
+  in_flight_.release(p.uid());
 }
 
 bool SchedulingQueue::affinity_term_matches(const Pod& waiting, const Pod& assigned) {
@@ -461,7 +451,7 @@ bool SchedulingQueue::affinity_term_matches(const Pod& waiting, const Pod& assig
 
 void SchedulingQueue::assigned_pod_added(const Pod& p) {
   std::lock_guard<AdaptiveMutex> g(mu_);
-  in_flight_erase(p.uid());  // bound: its cycles are over
+  in_flight_.release(p.uid());  // bound: its cycles are over
   std::vector<QueuedPodInfoPtr> match;
   for (const auto& kv : unschedulable_)
     if (affinity_term_matches(*kv.second->pod, p)) match.push_back(kv.second);

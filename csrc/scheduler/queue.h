@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "common/clock.h"
+#include "common/recycled_map.h"
 #include "framework/types.h"
 
 namespace xsched {
@@ -175,22 +176,9 @@ class SchedulingQueue {
   // assigned (every pod ends in one of those), so the map is bounded by the
   // pods that exist.
   enum : uint8_t { kNoMark = 0, kActivate = 1, kPark = 2 };
-  std::unordered_map<std::string, uint8_t> in_flight_;
-  // An entry per pod comes and goes with its scheduling cycle: erased map
-  // nodes (with their uid buffer) are kept for the next pop. Under mu_.
-  std::vector<std::unordered_map<std::string, uint8_t>::node_type> in_flight_spare_;
-  template <class K>
-  void in_flight_erase(const K& k) {
-    if constexpr (std::is_convertible_v<const K&, const std::string&>) {
-      auto it = in_flight_.find(k);
-      if (it == in_flight_.end()) return;
-      auto nh = in_flight_.extract(it);
-      if (in_flight_spare_.size() < 4096) in_flight_spare_.push_back(std::move(nh));
-    } else {
-      auto nh = in_flight_.extract(k);  // an iterator
-      if (in_flight_spare_.size() < 4096) in_flight_spare_.push_back(std::move(nh));
-    }
-  }
+  // An entry per pod comes and goes with its scheduling cycle: recycled
+  // (with its uid buffer), under mu_.
+  RecycledMap<std::unordered_map<std::string, uint8_t>> in_flight_;
   std::vector<std::pair<ClusterEvent, std::set<std::string>>> event_map_;
   int64_t scheduling_cycle_ = 0;
   int64_t move_request_cycle_ = -1;

@@ -1,5 +1,6 @@
 // Native unit tests for the C++ core (no Python in the loop): Quantity, JSON,
-// the GPU ledger's incremental aggregates (checked against a brute-force
+// RecycledMap against the std containers and a counting allocator, the GPU
+// ledger's incremental aggregates (checked against a brute-force
 // recomputation over random assignment sequences), the pod heap and
 // scheduling-queue backoff under a fake clock, the timer service, CycleState
 // memo invalidation, store watch replay/expiry, PodGroup-aligned chunked
@@ -7,14 +8,20 @@
 //
 // Built by `python -m flex_gpu_scheduler_amd.build_ext --tests` into
 // build/xsched_native_tests and run by tests/test_native_unit.py.
+#include <algorithm>
 #include <cstdio>
 #include <chrono>
 #include <functional>
+#include <iterator>
+#include <map>
+#include <memory>
 #include <mutex>
 #include <set>
 #include <thread>
 #include <random>
 #include <string>
+#include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "api/types.h"
@@ -23,6 +30,7 @@
 #include "common/json.h"
 #include "common/parallel.h"
 #include "common/quantity.h"
+#include "common/recycled_map.h"
 #include "framework/types.h"
 #include "scheduler/cache.h"
 #include "scheduler/queue.h"
@@ -104,6 +112,251 @@ TEST(node_status_map_matches_unordered_map) {
   CHECK_EQ(seen, m.size());
   m.clear();
   CHECK(m.empty() && m.find("node-0") == m.end());
+}
+
+// --------------------------------------------------------------- RecycledMap
+// Keys for the model checks: a small pool so that keys repeat; every third one
+// is longer than the small-string buffer.
+std::string pool_key(uint32_t i) { return (i % 3 ? "k" : std::string(40, 'x')) + std::to_string(i); }
+
+template <class R, class Ref>
+void check_same_unique(const R& m, const Ref& ref) {
+  CHECK_EQ(m.size(), ref.size());
+  CHECK_EQ(m.empty(), ref.empty());
+  CHECK(m.container() == ref);
+  size_t seen = 0;
+  for (auto it = m.begin(); it != m.end(); ++it) ++seen;
+  CHECK_EQ(seen, ref.size());
+}
+
+TEST(recycled_map_matches_std_containers) {
+  std::mt19937 rng(7);
+  {  // string -> int, keys short and long
+    using C = std::unordered_map<std::string, int>;
+    RecycledMap<C> m;
+    C ref;
+    for (int step = 0; step < 4000; ++step) {
+      std::string k = pool_key(rng() % 48);
+      uint32_t op = rng() % 100;
+      if (op < 50) {  // acquire, also of a key that is present
+        auto [it, fresh] = m.acquire(k);
+        auto [rit, rfresh] = ref.try_emplace(k);
+        CHECK_EQ(fresh, rfresh);
+        CHECK(it->first == k);
+        if (fresh) CHECK_EQ(it->second, 0);  // scrubbed or value-initialised
+        else CHECK_EQ(it->second, rit->second);  // a present entry is left alone
+        it->second = rit->second = static_cast<int>(rng() % 1000) + 1;
+      } else if (op < 75) {
+        CHECK_EQ(m.release(k), ref.erase(k) > 0);
+      } else if (op < 98) {
+        auto it = m.find(k);
+        CHECK_EQ(it != m.end(), ref.count(k) > 0);
+        CHECK_EQ(m.count(k), ref.count(k));
+        CHECK_EQ(m.contains(k), ref.count(k) > 0);
+        if (it != m.end()) {
+          m.release(it);
+          ref.erase(k);
+        }
+      } else {
+        m.release_all();
+        ref.clear();
+      }
+      check_same_unique(m, ref);
+    }
+  }
+  {  // uint64_t -> vector
+    using C = std::unordered_map<uint64_t, std::vector<int>>;
+    RecycledMap<C> m;
+    C ref;
+    for (int step = 0; step < 4000; ++step) {
+      uint64_t k = rng() % 48 * 0x9E3779B97F4A7C15ull;
+      uint32_t op = rng() % 100;
+      if (op < 60) {
+        auto [it, fresh] = m.acquire(k);
+        auto [rit, rfresh] = ref.try_emplace(k);
+        CHECK_EQ(fresh, rfresh);
+        if (fresh) CHECK(it->second.empty());
+        int v = static_cast<int>(rng() % 1000);
+        it->second.push_back(v);
+        rit->second.push_back(v);
+      } else if (op < 98) {
+        CHECK_EQ(m.release(k), ref.erase(k) > 0);
+      } else {
+        m.release_all();
+        ref.clear();
+      }
+      check_same_unique(m, ref);
+    }
+  }
+  {  // set of strings
+    using C = std::unordered_set<std::string>;
+    RecycledMap<C> m;
+    C ref;
+    for (int step = 0; step < 4000; ++step) {
+      std::string k = pool_key(rng() % 48);
+      uint32_t op = rng() % 100;
+      if (op < 55) {
+        auto [it, fresh] = m.acquire(k);
+        CHECK_EQ(fresh, ref.insert(k).second);
+        CHECK(*it == k);
+      } else if (op < 97) {
+        CHECK_EQ(m.release(k), ref.erase(k) > 0);
+      } else {
+        m.release_all();
+        ref.clear();
+      }
+      check_same_unique(m, ref);
+    }
+  }
+  {  // multimap: equal keys keep insertion order, as std::multimap's emplace
+    using C = std::multimap<int64_t, uint64_t>;
+    RecycledMap<C> m;
+    C ref;
+    uint64_t next = 1;
+    for (int step = 0; step < 4000; ++step) {
+      uint32_t op = rng() % 100;
+      if (op < 55 || ref.empty()) {
+        int64_t k = rng() % 16;
+        auto it = m.acquire(k, next);
+        auto rit = ref.emplace(k, next);
+        ++next;
+        CHECK(*it == *rit);
+        CHECK_EQ(std::distance(m.begin(), it), std::distance(ref.begin(), rit));
+      } else if (op < 98) {
+        size_t n = rng() % ref.size();
+        m.release(std::next(m.begin(), n));
+        ref.erase(std::next(ref.begin(), n));
+      } else {
+        m.release_all();
+        ref.clear();
+      }
+      CHECK_EQ(m.size(), ref.size());
+      CHECK_EQ(m.empty(), ref.empty());
+      CHECK(std::equal(m.begin(), m.end(), ref.begin(), ref.end()));  // contents and order
+    }
+  }
+}
+
+TEST(recycled_map_release_drops_references) {
+  auto target = std::make_shared<int>(1);
+  const long before = target.use_count();
+  struct Holder {
+    std::shared_ptr<int> p;
+    int extra = 0;
+  };
+  RecycledMap<std::unordered_map<std::string, std::shared_ptr<int>>> direct;
+  RecycledMap<std::unordered_map<uint64_t, Holder>> held;
+  RecycledMap<std::unordered_map<uint64_t, std::vector<std::shared_ptr<int>>>> listed;
+  RecycledMap<std::multimap<int64_t, std::shared_ptr<int>>> ordered;
+  for (int round = 0; round < 2; ++round) {
+    for (uint64_t i = 0; i < 3; ++i) {
+      direct.acquire(pool_key(i)).first->second = target;
+      held.acquire(i).first->second = Holder{target, 1};
+      listed.acquire(i).first->second.push_back(target);
+      ordered.acquire(5, target);
+    }
+    CHECK_EQ(target.use_count(), before + 12);
+    if (round == 0) {
+      for (uint64_t i = 0; i < 3; ++i) {
+        direct.release(pool_key(i));
+        held.release(held.find(i));
+        listed.release(i);
+        ordered.release(ordered.begin());
+      }
+    } else {
+      direct.release_all();
+      held.release_all();
+      listed.release_all();
+      ordered.release_all();
+    }
+    CHECK_EQ(target.use_count(), before);  // parked nodes hold nothing
+    CHECK_EQ(direct.parked(), 3u);
+  }
+  // A reused node comes back scrubbed.
+  auto [it, fresh] = held.acquire(9);
+  CHECK(fresh && !it->second.p && it->second.extra == 0);
+}
+
+size_t g_counted_allocs = 0;
+template <class T>
+struct CountingAlloc {
+  using value_type = T;
+  CountingAlloc() = default;
+  template <class U>
+  CountingAlloc(const CountingAlloc<U>&) {}
+  T* allocate(size_t n) {
+    ++g_counted_allocs;
+    return std::allocator<T>().allocate(n);
+  }
+  void deallocate(T* p, size_t n) { std::allocator<T>().deallocate(p, n); }
+  template <class U>
+  bool operator==(const CountingAlloc<U>&) const { return true; }
+  template <class U>
+  bool operator!=(const CountingAlloc<U>&) const { return false; }
+};
+template <class K, class V>
+using CountedMap = std::unordered_map<K, V, std::hash<K>, std::equal_to<K>, CountingAlloc<std::pair<const K, V>>>;
+
+TEST(recycled_map_steady_state_allocates_nothing) {
+  constexpr int N = 64;
+  using IntVec = std::vector<int, CountingAlloc<int>>;
+  RecycledMap<CountedMap<std::string, int>> by_name;  // keys fit the small-string buffer
+  RecycledMap<CountedMap<uint64_t, IntVec>> lists;
+  using Str = std::string;
+  RecycledMap<std::unordered_set<Str, std::hash<Str>, std::equal_to<Str>, CountingAlloc<Str>>> names;
+  using HeapAlloc = CountingAlloc<std::pair<const int64_t, uint64_t>>;
+  RecycledMap<std::multimap<int64_t, uint64_t, std::less<int64_t>, HeapAlloc>> heap;
+  auto name = [](int i) { return "p-" + std::to_string(i); };
+  auto fill = [&](int shift) {
+    for (int i = 0; i < N; ++i) {
+      by_name.acquire(name(i + shift)).first->second = i;
+      auto& v = lists.acquire(static_cast<uint64_t>(i + shift)).first->second;
+      if (shift) {
+        CHECK(v.empty());
+        CHECK_EQ(v.capacity(), 8u);  // the capacity it was released with
+      } else {
+        v.reserve(8);
+      }
+      v.assign(8, i);
+      names.acquire(name(i + shift));
+      heap.acquire(i % 7, static_cast<uint64_t>(i));
+    }
+  };
+  auto drain = [&](bool all) {
+    if (all) {
+      by_name.release_all();
+      lists.release_all();
+      names.release_all();
+      heap.release_all();
+      return;
+    }
+    while (!by_name.empty()) by_name.release(by_name.begin());
+    while (!lists.empty()) lists.release(lists.begin()->first);
+    while (!names.empty()) names.release(*names.begin());
+    while (!heap.empty()) heap.release(heap.begin());
+  };
+  fill(0);  // warm-up: nodes, bucket arrays and vector buffers are made here
+  drain(false);
+  CHECK(g_counted_allocs > 0);
+  const size_t warm = g_counted_allocs;
+  for (int round = 1; round <= N; ++round) {
+    fill(round);
+    CHECK_EQ(by_name.size(), size_t(N));
+    drain(round % 2 == 0);
+  }
+  CHECK_EQ(g_counted_allocs, warm);
+}
+
+TEST(recycled_map_cap_bounds_parked_nodes) {
+  RecycledMap<CountedMap<uint64_t, int>> m(/*cap=*/4);
+  for (uint64_t i = 0; i < 10; ++i) m.acquire(i);
+  for (uint64_t i = 0; i < 10; ++i) m.release(i);
+  CHECK_EQ(m.parked(), 4u);
+  const size_t before = g_counted_allocs;
+  for (uint64_t i = 0; i < 10; ++i) CHECK(m.acquire(i + 100).second);
+  CHECK_EQ(g_counted_allocs - before, 6u);  // 4 came from the parked nodes
+  CHECK_EQ(m.parked(), 0u);
+  CHECK_EQ(m.size(), 10u);
 }
 
 // ---------------------------------------------------------------------- JSON
