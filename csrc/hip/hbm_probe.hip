@@ -24,7 +24,13 @@
 //                       atomic chunk counter, so every launched workgroup
 //                       exits): the HBM bandwidth one CPX partition (one XCD,
 //                       32 CUs) or a QPX/DPX partition can pull, measured on
-//                       an SPX device.
+//                       an SPX device. A launch in which a selected XCD got
+//                       no workgroup fails with -1002 instead of a rate.
+//  * xs_stream_op_g, xs_pinned_op_g, xs_segment_op, xs_checksum_op  one
+//                       launch of the same kernels over caller-owned buffers,
+//                       for the GPU tests; the read paths run as checked
+//                       instantiations (k_*_fold) that report the XOR of the
+//                       words read and the number of 16-B loads issued.
 //  * xs_xcd_census      every workgroup records s_getreg(HW_REG_XCC_ID):
 //                       counts XCDs visible to this device — verifies the
 //                       compute-partition mode the node advertises (SPX -> 8
@@ -77,25 +83,58 @@ __device__ __forceinline__ void st(T v, T* p) {
   else *p = v;
 }
 
+// Checked instantiations (FOLD) make a read path observable: the XOR of every
+// lane's acc goes to fold[0] and the number of 16-B loads issued to fold[1],
+// reduced per wave first, then one atomic each from the wave's first lane.
+// Every lane of the wave must arrive. The timed kernels instantiate the same
+// loop source with FOLD = false and keep their DCE sink.
+__device__ __forceinline__ void fold_wave(uint32_t acc, unsigned long long loads, unsigned long long* __restrict__ fold) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    acc ^= __shfl_down(acc, off, 64);
+    loads += __shfl_down(loads, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0 && loads != 0) {
+    atomicXor(&fold[0], static_cast<unsigned long long>(acc));
+    atomicAdd(&fold[1], loads);
+  }
+}
+
 // Grid-stride walk in rows of U*grid lanes: one wave-instruction touches
 // 1 KiB contiguous, U independent 16-B accesses per lane in flight.
-template <int U, bool NT>
-__global__ __launch_bounds__(kBlock) void k_read(const vec4* __restrict__ src, size_t n, uint32_t* __restrict__ sink) {
+template <int U, bool NT, bool FOLD>
+__device__ __forceinline__ void read_lanes(const vec4* __restrict__ src, size_t n, uint32_t* __restrict__ sink,
+                                           unsigned long long* __restrict__ fold) {
   const size_t stride = static_cast<size_t>(gridDim.x) * kBlock;
   size_t i = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
   uint32_t acc = 0;
+  [[maybe_unused]] unsigned long long loads = 0;
   for (; i + (U - 1) * stride < n; i += U * stride) {
     vec4 v[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) v[u] = ld<NT>(&src[i + u * stride]);
 #pragma unroll
     for (int u = 0; u < U; ++u) acc ^= v[u].x ^ v[u].y ^ v[u].z ^ v[u].w;
+    if constexpr (FOLD) loads += U;
   }
   for (; i < n; i += stride) {
     vec4 v = ld<NT>(&src[i]);
     acc ^= v.x ^ v.y ^ v.z ^ v.w;
+    if constexpr (FOLD) ++loads;
   }
-  if (acc == 0x9e3779b9u) sink[0] = acc;  // defeats DCE without a store per lane
+  if constexpr (FOLD) fold_wave(acc, loads, fold);
+  else if (acc == 0x9e3779b9u) sink[0] = acc;  // defeats DCE without a store per lane
+}
+
+template <int U, bool NT>
+__global__ __launch_bounds__(kBlock) void k_read(const vec4* __restrict__ src, size_t n, uint32_t* __restrict__ sink) {
+  read_lanes<U, NT, false>(src, n, sink, nullptr);
+}
+
+template <int U, bool NT>
+__global__ __launch_bounds__(kBlock) void k_read_fold(const vec4* __restrict__ src, size_t n,
+                                                      unsigned long long* __restrict__ fold) {
+  read_lanes<U, NT, true>(src, n, nullptr, fold);
 }
 
 template <int U, bool NT>
@@ -158,16 +197,20 @@ __device__ __forceinline__ uint32_t hw_cu_id() {
 // XCD-pinned streaming: workgroups off the selected XCDs exit at once. The
 // selected XCDs split the buffer into equal contiguous slices (by their rank
 // in xcd_mask) and the workgroups of each XCD pull 256 KiB chunks of their
-// slice from that XCD's own counter, so the launch always drains and no
+// slice from that XCD's own counter, so the launch always ends and no
 // atomic is shared across XCDs (one counter per 128-B line: a single
 // device-wide counter serialized the 8-XCD case at ~2 TB/s, round-3 pmc
-// run). mode 0 read, 1 write, 2 copy.
+// run). mode 0 read, 1 write, 2 copy. Where workgroups land is the
+// dispatcher's choice: a selected XCD that gets none leaves its slice
+// untouched, which the host detects from that XCD's counter (undrained_xcds)
+// and reports as an error, never as a rate.
 constexpr int kCounterStride = 32;  // unsigned per XCD counter (128 B)
 constexpr int kMaxXcds = 8;
 
-__global__ __launch_bounds__(kBlock) void k_pinned(const vec4* __restrict__ src, vec4* __restrict__ dst, size_t n,
-                                                   uint32_t xcd_mask, unsigned* __restrict__ counters, int mode,
-                                                   uint32_t* __restrict__ sink) {
+template <bool FOLD>
+__device__ __forceinline__ void pinned_lanes(const vec4* __restrict__ src, vec4* __restrict__ dst, size_t n,
+                                             uint32_t xcd_mask, unsigned* __restrict__ counters, int mode,
+                                             uint32_t* __restrict__ sink, unsigned long long* __restrict__ fold) {
   const uint32_t x = xcc_id();
   if (x >= kMaxXcds || !((xcd_mask >> x) & 1u)) return;
   constexpr size_t kChunk = 16384;  // vec4s = 256 KiB
@@ -179,6 +222,7 @@ __global__ __launch_bounds__(kBlock) void k_pinned(const vec4* __restrict__ src,
   unsigned* ctr = counters + x * kCounterStride;
   __shared__ unsigned chunk;
   uint32_t acc = 0;
+  [[maybe_unused]] unsigned long long loads = 0;
   const vec4 fill = {1u, 2u, 3u, 4u};
   for (;;) {
     if (threadIdx.x == 0) chunk = atomicAdd(ctr, 1u);
@@ -203,6 +247,7 @@ __global__ __launch_bounds__(kBlock) void k_pinned(const vec4* __restrict__ src,
         } else {
 #pragma unroll
           for (int u = 0; u < 4; ++u) acc ^= v[u].x ^ v[u].y ^ v[u].z ^ v[u].w;
+          if constexpr (FOLD) loads += 4;
         }
       }
     }
@@ -212,11 +257,27 @@ __global__ __launch_bounds__(kBlock) void k_pinned(const vec4* __restrict__ src,
       } else {
         vec4 v = __builtin_nontemporal_load(&src[i]);
         if (mode == 2) __builtin_nontemporal_store(v, &dst[i]);
-        else acc ^= v.x ^ v.y ^ v.z ^ v.w;
+        else {
+          acc ^= v.x ^ v.y ^ v.z ^ v.w;
+          if constexpr (FOLD) ++loads;
+        }
       }
     }
   }
-  if (acc == 0x9e3779b9u) sink[0] = acc;
+  if constexpr (FOLD) fold_wave(acc, loads, fold);  // a workgroup leaves the loop as one
+  else if (acc == 0x9e3779b9u) sink[0] = acc;
+}
+
+__global__ __launch_bounds__(kBlock) void k_pinned(const vec4* __restrict__ src, vec4* __restrict__ dst, size_t n,
+                                                   uint32_t xcd_mask, unsigned* __restrict__ counters, int mode,
+                                                   uint32_t* __restrict__ sink) {
+  pinned_lanes<false>(src, dst, n, xcd_mask, counters, mode, sink, nullptr);
+}
+
+__global__ __launch_bounds__(kBlock) void k_pinned_fold(const vec4* __restrict__ src, size_t n, uint32_t xcd_mask,
+                                                        unsigned* __restrict__ counters,
+                                                        unsigned long long* __restrict__ fold) {
+  pinned_lanes<true>(src, nullptr, n, xcd_mask, counters, 0, nullptr, fold);
 }
 
 __global__ __launch_bounds__(64) void k_census(uint32_t* __restrict__ xcd_of_block, uint32_t* __restrict__ hwid_of_block) {
@@ -258,13 +319,14 @@ __global__ __launch_bounds__(kBlock) void k_checksum(const uint32_t* __restrict_
 // (touches x ceil(seg/128)); rocprofv3's L2 memory-side request counters are
 // read against that count (scripts/pmc_calibrate.sh). Lanes >= seg_lanes
 // idle; mode 0 reads, 1 writes.
-template <int MODE, bool NT>
-__global__ __launch_bounds__(kBlock) void k_segments(vec4* __restrict__ buf, size_t touches, size_t stride_vec,
-                                                     int seg_lanes, uint32_t* __restrict__ sink) {
+template <int MODE, bool NT, bool FOLD>
+__device__ __forceinline__ void segment_lanes(vec4* __restrict__ buf, size_t touches, size_t stride_vec, int seg_lanes,
+                                              uint32_t* __restrict__ sink, unsigned long long* __restrict__ fold) {
   const size_t wave = (static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x) >> 6;
   const size_t nwaves = (static_cast<size_t>(gridDim.x) * kBlock) >> 6;
   const int lane = threadIdx.x & 63;
   uint32_t acc = 0;
+  [[maybe_unused]] unsigned long long loads = 0;
   const vec4 fill = {5u, 6u, 7u, 8u};
   if (lane < seg_lanes) {
     for (size_t t = wave; t < touches; t += nwaves) {
@@ -272,12 +334,26 @@ __global__ __launch_bounds__(kBlock) void k_segments(vec4* __restrict__ buf, siz
       if constexpr (MODE == 0) {
         vec4 v = ld<NT>(p);
         acc ^= v.x ^ v.y ^ v.z ^ v.w;
+        if constexpr (FOLD) ++loads;
       } else {
         st<NT>(fill, p);
       }
     }
   }
-  if (acc == 0x9e3779b9u) sink[0] = acc;
+  if constexpr (FOLD) fold_wave(acc, loads, fold);
+  else if (acc == 0x9e3779b9u) sink[0] = acc;
+}
+
+template <int MODE, bool NT>
+__global__ __launch_bounds__(kBlock) void k_segments(vec4* __restrict__ buf, size_t touches, size_t stride_vec,
+                                                     int seg_lanes, uint32_t* __restrict__ sink) {
+  segment_lanes<MODE, NT, false>(buf, touches, stride_vec, seg_lanes, sink, nullptr);
+}
+
+template <bool NT>
+__global__ __launch_bounds__(kBlock) void k_segments_fold(vec4* __restrict__ buf, size_t touches, size_t stride_vec,
+                                                          int seg_lanes, unsigned long long* __restrict__ fold) {
+  segment_lanes<0, NT, true>(buf, touches, stride_vec, seg_lanes, nullptr, fold);
 }
 
 // Per-launch timing: `launch(i)` enqueues launch i; every launch sits
@@ -374,6 +450,69 @@ void launch(const Variant& v, int mode, int grid, hipStream_t s, void* a, void* 
     else if (v.unroll == 8) launch_t<8, false>(mode, grid, s, a, b, c, n, sink, seed, scale);
     else launch_t<4, false>(mode, grid, s, a, b, c, n, sink, seed, scale);
   }
+}
+
+// The checked read (k_read_fold) of variant v: same unroll and cache policy.
+void launch_read_fold(const Variant& v, int grid, hipStream_t s, const void* a, size_t n, unsigned long long* fold) {
+  const vec4* p = static_cast<const vec4*>(a);
+  if (v.nt) {
+    if (v.unroll == 1) k_read_fold<1, true><<<grid, kBlock, 0, s>>>(p, n, fold);
+    else if (v.unroll == 8) k_read_fold<8, true><<<grid, kBlock, 0, s>>>(p, n, fold);
+    else k_read_fold<4, true><<<grid, kBlock, 0, s>>>(p, n, fold);
+  } else {
+    if (v.unroll == 1) k_read_fold<1, false><<<grid, kBlock, 0, s>>>(p, n, fold);
+    else if (v.unroll == 8) k_read_fold<8, false><<<grid, kBlock, 0, s>>>(p, n, fold);
+    else k_read_fold<4, false><<<grid, kBlock, 0, s>>>(p, n, fold);
+  }
+}
+
+constexpr int kMaxGrid = 1 << 22;  // grid_for's cap; an explicit grid obeys it too
+
+// Device-side fold of a checked read: [0] XOR of every lane's acc, [1] 16-B
+// loads issued. Zeroed here, copied to the caller's two words after the launch.
+struct Fold {
+  DevMem d;
+  int init() {
+    XS_CHECK(hipMalloc(&d.p, 2 * sizeof(unsigned long long)));
+    XS_CHECK(hipMemset(d.p, 0, 2 * sizeof(unsigned long long)));
+    return 0;
+  }
+  int fetch(unsigned long long* out) {
+    XS_CHECK(hipMemcpy(out, d.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return 0;
+  }
+};
+
+constexpr int kUndrained = -1002;
+
+// k_pinned's per-XCD counters of one completed launch (host copy). Every
+// workgroup on a selected XCD takes chunks from that XCD's counter until its
+// slice [c0, c1) is exhausted, so a selected XCD whose slice is not empty and
+// whose counter is still 0 received no workgroup: its slice was never
+// processed. Returns those XCDs as a mask (slice bounds as in the kernel).
+uint32_t undrained_xcds(const unsigned* ctr, size_t n, uint32_t xcd_mask) {
+  const uint32_t sel = xcd_mask & 0xffu;
+  const size_t nsel = static_cast<size_t>(__builtin_popcount(sel));
+  const size_t nchunks = (n + 16384 - 1) / 16384;
+  uint32_t missed = 0;
+  for (uint32_t x = 0; x < kMaxXcds; ++x) {
+    if (!((sel >> x) & 1u)) continue;
+    const size_t rank = static_cast<size_t>(__builtin_popcount(sel & ((1u << x) - 1u)));
+    const size_t c0 = nchunks * rank / nsel, c1 = nchunks * (rank + 1) / nsel;
+    if (c1 > c0 && ctr[x * kCounterStride] == 0) missed |= 1u << x;
+  }
+  return missed;
+}
+
+int fail_undrained(uint32_t missed, uint32_t xcd_mask, int launch) {
+  char list[32];
+  int k = 0;
+  for (int x = 0; x < kMaxXcds; ++x)
+    if ((missed >> x) & 1u) k += std::snprintf(list + k, sizeof list - k, "%s%d", k ? "," : "", x);
+  std::snprintf(g_err, sizeof g_err,
+                "k_pinned: no workgroup ran on XCD(s) %s of xcd_mask 0x%x (launch %d); their slices were not processed",
+                list, xcd_mask, launch);
+  return kUndrained;
 }
 
 Variant default_variant(int mode) {
@@ -474,33 +613,62 @@ int xs_hbm_bandwidth_v(int dev, size_t bytes, int iters, int cu_limit, int mode,
 }
 
 // One streaming kernel over caller-owned device buffers (e.g. torch tensors),
-// run to completion: the GPU tier checks the kernels' results against a plain
-// PyTorch fp32 reference. mode 1: a <- pattern(seed); 2: b <- a; 3: a <- b +
+// run to completion: the GPU tier checks the kernels' results against exact
+// references (a float64 bound for triad; subnormal operands and results are
+// kept, the library is built without a flush-to-zero flag). mode 1: a <- pattern(seed); 2: b <- a; 3: a <- b +
 // scale*c (float4 lanes). bytes must be a multiple of 16 and every pointer
 // 16-byte aligned. variant as in xs_hbm_bandwidth_v (0 = the tuned default).
-int xs_stream_op(int dev, int mode, void* a, void* b, void* c, size_t bytes, uint32_t seed, float scale,
-                 int variant) {
+// grid > 0 launches that many workgroups instead of the variant's own grid
+// (the tests reach the unrolled bodies and the grid-stride path with small
+// buffers that way). mode 0 (read a) needs `fold`, two host words: the
+// checked read kernel's XOR of all 32-bit words and its count of 16-B loads.
+int xs_stream_op_g(int dev, int mode, void* a, void* b, void* c, size_t bytes, uint32_t seed, float scale,
+                   int variant, int grid, unsigned long long* fold) {
   XS_CHECK(hipSetDevice(dev));
-  if (mode < 1 || mode > 3 || bytes == 0 || bytes % sizeof(vec4) != 0) return -1000;
+  if (mode < 0 || mode > 3 || (mode == 0) != (fold != nullptr) || bytes == 0 || bytes % sizeof(vec4) != 0 ||
+      grid < 0 || grid > kMaxGrid)
+    return -1000;
   const uintptr_t align = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) |
                           reinterpret_cast<uintptr_t>(c);
   if (!a || (mode >= 2 && !b) || (mode == 3 && !c) || (align & (sizeof(vec4) - 1))) return -1001;
   Variant v = variant == 0 ? default_variant(mode) : decode(variant);
-  int grid = grid_for(v, bytes / sizeof(vec4), cu_count(dev));
-  launch(v, mode, grid, nullptr, a, b, c, bytes / sizeof(vec4), nullptr, seed, scale);
+  const size_t n = bytes / sizeof(vec4);
+  if (grid == 0) grid = grid_for(v, n, cu_count(dev));
+  Fold f;
+  if (mode == 0) {
+    if (int rc = f.init()) return rc;
+    launch_read_fold(v, grid, nullptr, a, n, f.d.as<unsigned long long>());
+  } else {
+    launch(v, mode, grid, nullptr, a, b, c, n, nullptr, seed, scale);
+  }
   XS_CHECK(hipGetLastError());
   XS_CHECK(hipDeviceSynchronize());
-  return 0;
+  return mode == 0 ? f.fetch(fold) : 0;
+}
+
+int xs_stream_op(int dev, int mode, void* a, void* b, void* c, size_t bytes, uint32_t seed, float scale,
+                 int variant) {
+  if (mode == 0) return -1000;
+  return xs_stream_op_g(dev, mode, a, b, c, bytes, seed, scale, variant, 0, nullptr);
 }
 
 // XCD-pinned streaming over caller-owned buffers (mode 1 write dst, 2 copy
-// src -> dst): only workgroups on the XCDs in xcd_mask do the work.
-int xs_pinned_op(int dev, int mode, const void* src, void* dst, size_t bytes, uint32_t xcd_mask) {
+// src -> dst): only workgroups on the XCDs in xcd_mask do the work. Which XCD
+// a workgroup lands on is the dispatcher's choice, so the per-XCD counters are
+// read back after the launch: -1002 when a selected XCD with a non-empty slice
+// received no workgroup (xs_last_error names it); what the other XCDs wrote
+// stays. xcd_mask bits above the 8 XCDs are refused. grid > 0 launches that
+// many workgroups instead of 8 per CU. mode 0 (read src) needs `fold`, two
+// host words as in xs_stream_op_g.
+int xs_pinned_op_g(int dev, int mode, const void* src, void* dst, size_t bytes, uint32_t xcd_mask, int grid,
+                   unsigned long long* fold) {
   XS_CHECK(hipSetDevice(dev));
-  if (mode < 1 || mode > 2 || xcd_mask == 0 || bytes == 0 || bytes % sizeof(vec4) != 0) return -1000;
+  if (mode < 0 || mode > 2 || (mode == 0) != (fold != nullptr) || xcd_mask == 0 || (xcd_mask & ~0xffu) ||
+      bytes == 0 || bytes % sizeof(vec4) != 0 || grid < 0 || grid > kMaxGrid)
+    return -1000;
   const size_t n = bytes / sizeof(vec4);
   if (n / 16384 >= 0xffffff00ull) return -1000;
-  if (!dst || (mode == 2 && !src) ||
+  if ((mode != 0 && !dst) || (mode != 1 && !src) ||
       ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & (sizeof(vec4) - 1)))
     return -1001;
   DevMem counter, sink;
@@ -508,11 +676,27 @@ int xs_pinned_op(int dev, int mode, const void* src, void* dst, size_t bytes, ui
   XS_CHECK(hipMalloc(&counter.p, ctr_bytes));
   XS_CHECK(hipMalloc(&sink.p, sizeof(uint32_t)));
   XS_CHECK(hipMemset(counter.p, 0, ctr_bytes));
-  k_pinned<<<cu_count(dev) * 8, kBlock>>>(static_cast<const vec4*>(src), static_cast<vec4*>(dst), n, xcd_mask,
-                                         counter.as<unsigned>(), mode, sink.as<uint32_t>());
+  if (grid == 0) grid = cu_count(dev) * 8;
+  Fold f;
+  if (mode == 0) {
+    if (int rc = f.init()) return rc;
+    k_pinned_fold<<<grid, kBlock>>>(static_cast<const vec4*>(src), n, xcd_mask, counter.as<unsigned>(),
+                                    f.d.as<unsigned long long>());
+  } else {
+    k_pinned<<<grid, kBlock>>>(static_cast<const vec4*>(src), static_cast<vec4*>(dst), n, xcd_mask,
+                               counter.as<unsigned>(), mode, sink.as<uint32_t>());
+  }
   XS_CHECK(hipGetLastError());
   XS_CHECK(hipDeviceSynchronize());
-  return 0;
+  unsigned ctr[kMaxXcds * kCounterStride];
+  XS_CHECK(hipMemcpy(ctr, counter.p, ctr_bytes, hipMemcpyDeviceToHost));
+  if (uint32_t missed = undrained_xcds(ctr, n, xcd_mask)) return fail_undrained(missed, xcd_mask, 0);
+  return mode == 0 ? f.fetch(fold) : 0;
+}
+
+int xs_pinned_op(int dev, int mode, const void* src, void* dst, size_t bytes, uint32_t xcd_mask) {
+  if (mode == 0) return -1000;
+  return xs_pinned_op_g(dev, mode, src, dst, bytes, xcd_mask, 0, nullptr);
 }
 
 int xs_hbm_bandwidth(int dev, size_t bytes, int iters, int cu_limit, int mode, double* gbps, double* ms_per_iter) {
@@ -525,7 +709,7 @@ int xs_hbm_bandwidth_xcd_d(int dev, size_t bytes, int iters, uint32_t xcd_mask, 
                            double* ms_per_iter, double* detail) {
   XS_CHECK(hipSetDevice(dev));
   if (iters <= 0) iters = 10;
-  if (mode < 0 || mode > 2 || xcd_mask == 0) return -1000;
+  if (mode < 0 || mode > 2 || xcd_mask == 0 || (xcd_mask & ~0xffu)) return -1000;
   size_t n = bytes / sizeof(vec4);
   if (n == 0 || n / 16384 >= 0xffffff00ull) return -1000;
   bytes = n * sizeof(vec4);
@@ -551,6 +735,12 @@ int xs_hbm_bandwidth_xcd_d(int dev, size_t bytes, int iters, uint32_t xcd_mask, 
                                        sink.as<uint32_t>());
   }, t);
   if (rc) return rc;
+  // No rate for bytes that were not moved: every launch (the warm-up is
+  // launch `iters`) must have had a workgroup on each selected XCD.
+  std::vector<unsigned> hctr(per_launch * (iters + 1));
+  XS_CHECK(hipMemcpy(hctr.data(), counters.p, sizeof(unsigned) * hctr.size(), hipMemcpyDeviceToHost));
+  for (int i = 0; i <= iters; ++i)
+    if (uint32_t missed = undrained_xcds(&hctr[i * per_launch], n, xcd_mask)) return fail_undrained(missed, xcd_mask, i);
   const double moved = static_cast<double>(bytes) * (mode == 2 ? 2.0 : 1.0);
   if (gbps) *gbps = moved / (t[0] * 1e-3) / 1e9;
   if (ms_per_iter) *ms_per_iter = t[0];
@@ -608,6 +798,36 @@ int xs_segment_access(int dev, int mode, int nt, int seg_bytes, size_t stride_by
   return 0;
 }
 
+// One k_segments launch (arguments as xs_segment_access) over a caller-owned
+// device buffer of stride_bytes x touches bytes, run to completion, so a test
+// sees what the kernel touched. mode 1 writes the fill (5, 6, 7, 8); mode 0
+// needs `fold`, two host words: XOR of the 32-bit words read, 16-B loads issued.
+int xs_segment_op(int dev, int mode, int nt, int seg_bytes, size_t stride_bytes, size_t touches, void* buf,
+                  unsigned long long* fold) {
+  XS_CHECK(hipSetDevice(dev));
+  if (mode < 0 || mode > 1 || (mode == 0) != (fold != nullptr) || seg_bytes < 16 || seg_bytes > 1024 ||
+      seg_bytes % 16 || stride_bytes % 128 || stride_bytes < static_cast<size_t>(seg_bytes) || touches == 0)
+    return -1000;
+  if (!buf || (reinterpret_cast<uintptr_t>(buf) & (sizeof(vec4) - 1))) return -1001;
+  const int grid = cu_count(dev) * 8;
+  const size_t sv = stride_bytes / sizeof(vec4);
+  const int lanes = seg_bytes / 16;
+  vec4* p = static_cast<vec4*>(buf);
+  Fold f;
+  if (mode == 0) {
+    if (int rc = f.init()) return rc;
+    if (nt) k_segments_fold<true><<<grid, kBlock>>>(p, touches, sv, lanes, f.d.as<unsigned long long>());
+    else k_segments_fold<false><<<grid, kBlock>>>(p, touches, sv, lanes, f.d.as<unsigned long long>());
+  } else if (nt) {
+    k_segments<1, true><<<grid, kBlock>>>(p, touches, sv, lanes, nullptr);
+  } else {
+    k_segments<1, false><<<grid, kBlock>>>(p, touches, sv, lanes, nullptr);
+  }
+  XS_CHECK(hipGetLastError());
+  XS_CHECK(hipDeviceSynchronize());
+  return mode == 0 ? f.fetch(fold) : 0;
+}
+
 // Launches `blocks` single-wave workgroups; returns the number of distinct
 // XCDs observed and writes a 8-entry histogram of blocks per XCD.
 int xs_xcd_census(int dev, int blocks, int* xcd_hist8, int* distinct_cus) {
@@ -663,6 +883,23 @@ int xs_health_check(int dev, size_t bytes, unsigned long long* device_sum, unsig
   if (device_sum) *device_sum = d;
   if (host_sum) *host_sum = h;
   return d == h ? 0 : 1;
+}
+
+// k_checksum, launched as xs_health_check launches it, over a caller-owned
+// device buffer of `bytes` (a multiple of 4, 4-byte aligned): out_sum <- the
+// sum of its 32-bit words.
+int xs_checksum_op(int dev, const void* buf, size_t bytes, unsigned long long* out_sum) {
+  XS_CHECK(hipSetDevice(dev));
+  if (bytes == 0 || bytes % sizeof(uint32_t) != 0 || !out_sum) return -1000;
+  if (!buf || (reinterpret_cast<uintptr_t>(buf) & (sizeof(uint32_t) - 1))) return -1001;
+  DevMem out;
+  XS_CHECK(hipMalloc(&out.p, sizeof(unsigned long long)));
+  XS_CHECK(hipMemset(out.p, 0, sizeof(unsigned long long)));
+  k_checksum<<<cu_count(dev) * 8, kBlock>>>(static_cast<const uint32_t*>(buf), bytes / sizeof(uint32_t),
+                                           out.as<unsigned long long>());
+  XS_CHECK(hipGetLastError());
+  XS_CHECK(hipMemcpy(out_sum, out.p, sizeof *out_sum, hipMemcpyDeviceToHost));
+  return 0;
 }
 
 }  // extern "C"

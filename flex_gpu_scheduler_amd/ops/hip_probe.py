@@ -24,6 +24,12 @@ class ProbeError(RuntimeError):
     rc: int | None = None  # the C ABI's return code, where one caused the error
 
 
+BAD_ARGS = -1000
+# k_pinned: a selected XCD received no workgroup, so its slice of the buffer
+# was never processed (xs_pinned_op_g, xs_hbm_bandwidth_xcd_d).
+PINNED_UNDRAINED = -1002
+
+
 @dataclass
 class Bandwidth:
     """`gbps` / `ms_per_iter`: the median launch, each timed by its own event
@@ -86,6 +92,12 @@ class HipProbe:
                                    ctypes.c_size_t, ctypes.c_uint32, ctypes.c_float, ctypes.c_int]
         L.xs_pinned_op.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
                                    ctypes.c_uint32]
+        L.xs_stream_op_g.argtypes = [*L.xs_stream_op.argtypes, ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong)]
+        L.xs_pinned_op_g.argtypes = [*L.xs_pinned_op.argtypes, ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong)]
+        L.xs_checksum_op.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
+                                     ctypes.POINTER(ctypes.c_ulonglong)]
+        L.xs_segment_op.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_size_t,
+                                    ctypes.c_size_t, ctypes.c_void_p, ctypes.POINTER(ctypes.c_ulonglong)]
         L.xs_segment_access.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_size_t,
                                         ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
         L.xs_mfma_last_error.restype = ctypes.c_char_p
@@ -102,7 +114,10 @@ class HipProbe:
                                   ctypes.POINTER(ctypes.c_double)]
 
     def _err(self, rc: int, what: str) -> ProbeError:
-        return ProbeError(f"{what} failed ({rc}): {self.lib.xs_last_error().decode(errors='replace')}")
+        detail = "bad arguments" if rc == BAD_ARGS else self.lib.xs_last_error().decode(errors="replace")
+        e = ProbeError(f"{what} failed ({rc}): {detail}")
+        e.rc = rc
+        return e
 
     def device_count(self) -> int:
         return int(self.lib.xs_device_count())
@@ -163,26 +178,37 @@ class HipProbe:
             raise ValueError(f"{what}: {nbytes} bytes at {t.data_ptr():#x} is not 16-byte granular")
         return t.data_ptr(), nbytes
 
+    # `grid` > 0 launches that many workgroups of 256 lanes instead of the
+    # variant's own grid: small buffers then reach the unrolled loop bodies
+    # and the grid-stride path that production sizes reach.
     def _stream(self, dev: int, mode: int, a, b, c, nbytes: int, seed: int = 7, scale: float = 3.0,
-                variant: int = 0) -> None:
-        rc = self.lib.xs_stream_op(dev, mode, a, b, c, nbytes, seed, scale, variant)
+                variant: int = 0, grid: int = 0, fold=None) -> None:
+        rc = self.lib.xs_stream_op_g(dev, mode, a, b, c, nbytes, seed, scale, variant, grid, fold)
         if rc != 0:
             raise self._err(rc, "stream_op")
 
-    def write_pattern(self, dst, seed: int = 7, variant: int = 0) -> None:
+    def read_fold(self, src, variant: int = 0, grid: int = 0) -> tuple[int, int]:
+        """k_read, checked instantiation: (XOR of every 32-bit word of `src`,
+        number of 16-B loads the launch issued)."""
+        p, n = self._dev_buf(src, "src")
+        fold = (ctypes.c_ulonglong * 2)()
+        self._stream(src.device.index or 0, MODES["read"], p, None, None, n, variant=variant, grid=grid, fold=fold)
+        return int(fold[0]), int(fold[1])
+
+    def write_pattern(self, dst, seed: int = 7, variant: int = 0, grid: int = 0) -> None:
         """k_write: every 16-B lane of `dst` <- (seed, seed^0x55555555, seed+1, ~seed) as uint32."""
         p, n = self._dev_buf(dst, "dst")
-        self._stream(dst.device.index or 0, MODES["write"], p, None, None, n, seed=seed, variant=variant)
+        self._stream(dst.device.index or 0, MODES["write"], p, None, None, n, seed=seed, variant=variant, grid=grid)
 
-    def copy(self, dst, src, variant: int = 0) -> None:
+    def copy(self, dst, src, variant: int = 0, grid: int = 0) -> None:
         """k_copy: dst <- src (byte copy; equal sizes)."""
         pd, n = self._dev_buf(dst, "dst")
         ps, ns = self._dev_buf(src, "src")
         if n != ns:
             raise ValueError("copy: size mismatch")
-        self._stream(dst.device.index or 0, MODES["copy"], ps, pd, None, n, variant=variant)
+        self._stream(dst.device.index or 0, MODES["copy"], ps, pd, None, n, variant=variant, grid=grid)
 
-    def triad(self, a, b, c, scale: float = 3.0, variant: int = 0) -> None:
+    def triad(self, a, b, c, scale: float = 3.0, variant: int = 0, grid: int = 0) -> None:
         """k_triad (STREAM): a <- b + scale*c on fp32 tensors."""
         import torch
 
@@ -193,20 +219,64 @@ class HipProbe:
         pc, nc = self._dev_buf(c, "c")
         if not n == nb == nc:
             raise ValueError("triad: size mismatch")
-        self._stream(a.device.index or 0, MODES["triad"], pa, pb_, pc, n, scale=scale, variant=variant)
+        self._stream(a.device.index or 0, MODES["triad"], pa, pb_, pc, n, scale=scale, variant=variant, grid=grid)
 
-    def pinned(self, dst, src=None, xcd_mask: int = 0x1) -> None:
+    def pinned(self, dst, src=None, xcd_mask: int = 0x1, grid: int = 0) -> None:
         """k_pinned on the XCDs of `xcd_mask`: copy src -> dst, or write the
-        fill pattern (1, 2, 3, 4) into dst when src is None."""
+        fill pattern (1, 2, 3, 4) into dst when src is None. Raises ProbeError
+        with rc PINNED_UNDRAINED when a selected XCD received no workgroup
+        (its slice is then untouched). `grid` > 0: that many workgroups
+        instead of 8 per CU."""
         pd, n = self._dev_buf(dst, "dst")
         ps = 0
         if src is not None:
             ps, ns = self._dev_buf(src, "src")
             if ns != n:
                 raise ValueError("pinned: size mismatch")
-        rc = self.lib.xs_pinned_op(dst.device.index or 0, 2 if src is not None else 1, ps or None, pd, n, xcd_mask)
+        rc = self.lib.xs_pinned_op_g(dst.device.index or 0, 2 if src is not None else 1, ps or None, pd, n, xcd_mask,
+                                     grid, None)
         if rc != 0:
             raise self._err(rc, "pinned_op")
+
+    def pinned_read_fold(self, src, xcd_mask: int = 0x1, grid: int = 0) -> tuple[int, int]:
+        """k_pinned's read mode, checked instantiation: (XOR of every 32-bit
+        word of `src`, number of 16-B loads issued)."""
+        ps, n = self._dev_buf(src, "src")
+        fold = (ctypes.c_ulonglong * 2)()
+        rc = self.lib.xs_pinned_op_g(src.device.index or 0, 0, ps, None, n, xcd_mask, grid, fold)
+        if rc != 0:
+            raise self._err(rc, "pinned_op")
+        return int(fold[0]), int(fold[1])
+
+    def checksum(self, buf) -> int:
+        """k_checksum (the health check's kernel) over a device tensor: the
+        sum of its 32-bit words."""
+        if not buf.is_cuda or not buf.is_contiguous():
+            raise ValueError("buf must be a contiguous device tensor")
+        nbytes = buf.numel() * buf.element_size()
+        if nbytes % 4 or buf.data_ptr() % 4:
+            raise ValueError(f"buf: {nbytes} bytes at {buf.data_ptr():#x} is not 4-byte granular")
+        out = ctypes.c_ulonglong()
+        rc = self.lib.xs_checksum_op(buf.device.index or 0, buf.data_ptr(), nbytes, ctypes.byref(out))
+        if rc != 0:
+            raise self._err(rc, "checksum_op")
+        return int(out.value)
+
+    def segment_op(self, buf, mode: str = "read", seg_bytes: int = 128, stride_bytes: int = 4096, touches: int = 1,
+                   nontemporal: bool = False) -> tuple[int, int] | None:
+        """One k_segments launch over `buf` (stride_bytes x touches bytes).
+        "write" stores the fill (5, 6, 7, 8) into the first `seg_bytes` of
+        every slot; "read" returns (XOR of the 32-bit words read, number of
+        16-B loads issued)."""
+        p, n = self._dev_buf(buf, "buf")
+        if n != stride_bytes * touches:
+            raise ValueError(f"segment_op: buf holds {n} bytes, not {stride_bytes} x {touches}")
+        fold = (ctypes.c_ulonglong * 2)() if mode == "read" else None
+        rc = self.lib.xs_segment_op(buf.device.index or 0, MODES[mode], int(nontemporal), seg_bytes, stride_bytes,
+                                    touches, p, fold)
+        if rc != 0:
+            raise self._err(rc, "segment_op")
+        return (int(fold[0]), int(fold[1])) if fold is not None else None
 
     def hbm_bandwidth_xcd(self, dev: int = 0, xcd_mask: int = 0x1, nbytes: int = DEFAULT_BYTES, iters: int = 10,
                           mode: str = "read") -> Bandwidth:
@@ -225,6 +295,8 @@ class HipProbe:
         The node agent publishes it with the GPU's health (gpu/telemetry)."""
         rows = {}
         for mode_name, xcds in (("CPX", 1), ("QPX", 2), ("DPX", 4), ("SPX", 8)):
+            row = {"xcds": xcds, "cus": xcds * 32}
+            rows[mode_name] = row
             if xcds == 8:
                 # An SPX partition is the whole GPU, dispatched as any kernel
                 # is: measured with the full-device streaming kernels, not the
@@ -234,11 +306,20 @@ class HipProbe:
                 kernel = "k_read / k_copy (full device)"
             else:
                 mask = (1 << xcds) - 1
-                r = self.hbm_bandwidth_xcd(dev, mask, nbytes, iters, "read")
-                c = self.hbm_bandwidth_xcd(dev, mask, nbytes, iters, "copy")
                 kernel = "k_pinned (workgroups on the partition's XCDs)"
-            rows[mode_name] = {"xcds": xcds, "cus": xcds * 32, "read_GBps": round(r.gbps, 1),
-                               "copy_GBps": round(c.gbps, 1), "read_ms": round(r.ms_per_iter, 4), "kernel": kernel}
+                try:
+                    r = self.hbm_bandwidth_xcd(dev, mask, nbytes, iters, "read")
+                    c = self.hbm_bandwidth_xcd(dev, mask, nbytes, iters, "copy")
+                except ProbeError as e:
+                    if e.rc != PINNED_UNDRAINED:
+                        raise
+                    # Not every XCD of this set took work (a partitioned
+                    # device, or other tenants held it): no rate for bytes
+                    # that were not moved; the other rows stand.
+                    row.update(read_GBps=None, copy_GBps=None, read_ms=None, kernel=kernel, unmeasured=str(e))
+                    continue
+            row.update(read_GBps=round(r.gbps, 1), copy_GBps=round(c.gbps, 1), read_ms=round(r.ms_per_iter, 4),
+                       kernel=kernel)
         return {"bytes": nbytes, "timing": "median of per-launch event pairs", "partitions": rows}
 
     def segment_access(self, dev: int = 0, mode: str = "read", seg_bytes: int = 128, stride_bytes: int = 4096,

@@ -224,3 +224,51 @@ def test_failed_bandwidth_probe_is_not_retried_every_heartbeat(store):
     agent._bandwidth_retry_at.clear()
     agent.sync()
     assert calls.count(1) == 2
+
+
+def test_bandwidth_row_with_unreached_xcds_is_published_unmeasured(store):
+    """A k_pinned launch that left a selected XCD's slice untouched raises
+    (rc -1002) instead of returning a rate; partition_table reports that row
+    as unmeasured, with the reason, and the node agent still publishes the
+    other rows."""
+    import json as _json
+
+    from flex_gpu_scheduler_amd.control import LocalClient
+    from flex_gpu_scheduler_amd.control.node_agent import BANDWIDTH_ANNOTATION, NodeAgent
+    from flex_gpu_scheduler_amd.gpu.discovery import fake_host
+    from flex_gpu_scheduler_amd.ops.hip_probe import PINNED_UNDRAINED, Bandwidth, HipProbe, ProbeError
+
+    class Stub(HipProbe):
+        def __init__(self):  # no library: only the table's own logic runs
+            pass
+
+        def hbm_bandwidth(self, dev=0, nbytes=0, iters=0, cu_limit=0, mode="copy", variant=0):
+            return Bandwidth(mode, nbytes, 5000.0, 0.2, cu_limit)
+
+        def hbm_bandwidth_xcd(self, dev=0, xcd_mask=1, nbytes=0, iters=0, mode="read"):
+            if xcd_mask == 0x0F:
+                e = ProbeError("hbm_bandwidth_xcd failed (-1002): k_pinned: no workgroup ran on XCD(s) 3")
+                e.rc = PINNED_UNDRAINED
+                raise e
+            return Bandwidth(mode, nbytes, 700.0 * bin(xcd_mask).count("1"), 1.5, 0)
+
+    stub = Stub()
+    agent = NodeAgent(LocalClient(store), "n0", host_fn=lambda: fake_host(1), publish_metrics=False,
+                      bandwidth_fn=lambda dev: stub.partition_table(dev, 1 << 20, 2))
+    agent.sync()
+    rows = _json.loads(store.get("nodes", "", "n0")["metadata"]["annotations"][BANDWIDTH_ANNOTATION])["0"]["partitions"]
+    assert sorted(rows) == ["CPX", "DPX", "QPX", "SPX"]
+    assert rows["DPX"]["read_GBps"] is None and rows["DPX"]["copy_GBps"] is None and rows["DPX"]["read_ms"] is None
+    assert "XCD(s) 3" in rows["DPX"]["unmeasured"] and rows["DPX"]["xcds"] == 4
+    assert rows["CPX"]["read_GBps"] == 700.0 and rows["QPX"]["copy_GBps"] == 1400.0 and rows["SPX"]["read_GBps"] == 5000.0
+    assert all("unmeasured" not in rows[m] for m in ("CPX", "QPX", "SPX"))
+
+    # Any other probe failure is still an error of the whole table.
+    def broken(*a, **k):
+        e = ProbeError("hipMalloc: out of memory")
+        e.rc = -3
+        raise e
+
+    stub.hbm_bandwidth_xcd = broken
+    with pytest.raises(ProbeError):
+        stub.partition_table(0, 1 << 20, 2)
