@@ -329,6 +329,15 @@ def cmd_manager(args) -> int:
     return 0
 
 
+def health_fn_args(args) -> dict:
+    """hip_health_fn's keywords from the node-agent flags.
+    --health-matrix-sweep: absent -> None, bare -> "all", else a comma list."""
+    m = args.health_matrix_sweep
+    formats = None if m in (None, "all") else [f.strip() for f in m.split(",") if f.strip()]
+    return {"sweep": args.health_sweep, "sweep_period_s": args.health_sweep_period, "matrix": m is not None,
+            "matrix_formats": formats}
+
+
 def cmd_node_agent(args) -> int:
     from .control.node_agent import NodeAgent, hip_bandwidth_fn, hip_health_fn
     from .gpu.discovery import discover_host, fake_host
@@ -342,8 +351,9 @@ def cmd_node_agent(args) -> int:
                       heartbeat=args.heartbeat, telemetry_period=args.telemetry_period,
                       publish_metrics=not args.no_telemetry, reserved_cpu=args.reserved_cpu,
                       reserved_memory_gib=args.reserved_memory_gib,
-                      health_fn=(hip_health_fn(sweep=args.health_sweep, sweep_period_s=args.health_sweep_period)
-                                 if args.health_probe or args.health_sweep else None),
+                      health_fn=(hip_health_fn(**health_fn_args(args))
+                                 if args.health_probe or args.health_sweep or args.health_matrix_sweep is not None
+                                 else None),
                       bandwidth_fn=hip_bandwidth_fn() if args.bandwidth_probe else None,
                       kubelet_managed=args.kubelet_managed).start()
     if args.device_plugin:
@@ -502,6 +512,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--health-sweep", action="store_true",
                    help="health probe plus the CU sweep: MFMA, VALU and LDS checked on every CU; a bad XCD "
                         "fences its compute partition (xcdFaults) instead of the whole GPU. Implies --health-probe")
+    p.add_argument("--health-matrix-sweep", nargs="?", const="all", default=None, metavar="FORMATS",
+                   help="health probe plus the matrix-format sweep: f16, f32, f64, fp8, bf8, i8 and the block-scaled "
+                        "mxfp8, mxbf8, mxfp6, mxbf6, mxfp4 run on every CU (a comma list selects some; default all); "
+                        "a bad XCD is fenced like --health-sweep's and its formats are published as matrixFaults. "
+                        "Implies --health-probe; independent of --health-sweep")
     p.add_argument("--health-sweep-period", type=float, default=600.0, metavar="SECONDS",
                    help="reuse a sweep's verdict this long before sweeping the GPU again")
     p.add_argument("--bandwidth-probe", action="store_true",

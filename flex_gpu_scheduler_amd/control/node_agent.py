@@ -14,7 +14,8 @@ exporter + metrics-server:
     checksum per GPU) and withholds unhealthy GPUs from allocatable, tainting
     the node when none are healthy; a verdict that names bad XCDs (GpuHealth,
     e.g. from the CU sweep) fences only the compute partitions holding them
-    on a DPX/QPX/CPX GPU (`xcdFaults` in the topology annotation);
+    on a DPX/QPX/CPX GPU (`xcdFaults` in the topology annotation), and the
+    matrix formats such an XCD gets wrong are published as `matrixFaults`;
   * samples load (gpu/telemetry.py) and publishes its WatcherMetrics document
     for the Trimaran plugins.
 """
@@ -93,6 +94,9 @@ class NodeAgent:
         self.unhealthy: set[int] = set()
         # GPU index -> physical XCD ids a GpuHealth verdict named as bad.
         self.unhealthy_xcds: dict[int, set[int]] = {}
+        # GPU index -> {XCD id: matrix formats it mis-computes}, from
+        # GpuHealth.detail["matrixFaults"] (the matrix-format sweep).
+        self.matrix_faults: dict[int, dict[int, list[str]]] = {}
         self._stop = threading.Event()
         self._threads: list[threading.Thread] = []
         self.host: HostInfo | None = None
@@ -109,10 +113,15 @@ class NodeAgent:
         """(GPUs to withhold, bad XCDs per GPU). A `bool` from health_fn means
         the whole GPU; a GpuHealth with bad XCDs withholds an SPX GPU and only
         marks the XCDs of a partitioned one."""
+        return self._probe_health(host)[:2]
+
+    def _probe_health(self, host: HostInfo) -> tuple[set[int], dict[int, set[int]], dict[int, dict[int, list[str]]]]:
+        """probe_health plus the matrix formats each bad XCD got wrong."""
         if self.health_fn is None:
-            return set(), {}
+            return set(), {}, {}
         bad: set[int] = set()
         xcds: dict[int, set[int]] = {}
+        formats: dict[int, dict[int, list[str]]] = {}
         # HIP ordinals follow the KFD node order of the GPUs this process can
         # open; GPUs whose KFD node is hidden (other containers' devices) are
         # not probed. With no KFD info at all (fake hosts) use the index.
@@ -121,6 +130,10 @@ class NodeAgent:
         for ordinal, g in targets:
             try:
                 r = self.health_fn(ordinal)
+                if isinstance(r, GpuHealth):
+                    mf = {int(x): list(f) for x, f in (r.detail.get("matrixFaults") or {}).items() if f}
+                    if mf:
+                        formats[g.index] = mf
                 if isinstance(r, GpuHealth) and r.bad_xcds:
                     xcds[g.index] = set(r.bad_xcds)
                     if g.partitions == 1:
@@ -130,7 +143,7 @@ class NodeAgent:
             except Exception as e:  # noqa: BLE001
                 log.warning("health probe GPU %d failed: %s", g.index, e)
                 bad.add(g.index)
-        return bad, xcds
+        return bad, xcds, formats
 
     @staticmethod
     def _fenced(gpus, xcd_faults) -> dict[int, tuple[int, int]]:
@@ -165,7 +178,8 @@ class NodeAgent:
                 self._bandwidth_retry_at[g.index] = now + self.bandwidth_retry_s
 
     def build_node(self, host: HostInfo, unhealthy: set[int] = frozenset(),
-                   xcd_faults: dict[int, set[int]] | None = None) -> dict:
+                   xcd_faults: dict[int, set[int]] | None = None,
+                   matrix_faults: dict[int, dict[int, list[str]]] | None = None) -> dict:
         healthy = [g for g in host.gpus if g.index not in unhealthy]
         infos = [g.to_gpu_info() for g in healthy]
         mem_kib = max(0, host.memory_bytes // 1024 - self.reserved_memory_gib * (1 << 20))
@@ -192,6 +206,13 @@ class NodeAgent:
         faults = {str(i): sorted(x) for i, x in sorted((xcd_faults or {}).items()) if x}
         if faults:
             topo["xcdFaults"] = faults
+        # Which matrix formats each faulty XCD mis-computes: informational (the
+        # XCD is fenced through xcdFaults), for operators and RMA tooling.
+        formats = {str(i): {str(x): list(f) for x, f in sorted(per.items()) if f}
+                   for i, per in sorted((matrix_faults or {}).items())}
+        formats = {i: per for i, per in formats.items() if per}
+        if formats:
+            topo["matrixFaults"] = formats
         node["metadata"]["annotations"][TOPOLOGY_ANNOTATION] = json.dumps(topo, sort_keys=True)
         if self.bandwidth:
             node["metadata"]["annotations"][BANDWIDTH_ANNOTATION] = json.dumps(
@@ -283,13 +304,14 @@ class NodeAgent:
 
     def sync(self) -> HostInfo:
         host = self.host_fn()
-        self.unhealthy, self.unhealthy_xcds = self.probe_health(host)
+        self.unhealthy, self.unhealthy_xcds, self.matrix_faults = self._probe_health(host)
         self.measure_bandwidth(host)
         for dp in self.device_plugins:
             dp.host = host
             dp.set_unhealthy(self.unhealthy)
             dp.set_unhealthy_xcds(self.unhealthy_xcds)
-        self._upsert("nodes", self.build_node(host, self.unhealthy, self.unhealthy_xcds), keep_spec=True)
+        self._upsert("nodes", self.build_node(host, self.unhealthy, self.unhealthy_xcds, self.matrix_faults),
+                     keep_spec=True)
         self._upsert("noderesourcetopologies", self.build_nrt(host, self.unhealthy, self.unhealthy_xcds),
                      keep_spec=False)
         self.host = host
@@ -330,9 +352,9 @@ class NodeAgent:
 
     def _heartbeat_and_resync(self) -> None:
         host = self.host_fn()
-        unhealthy, xcds = self.probe_health(host)
+        unhealthy, xcds, formats = self._probe_health(host)
         changed = (self.host is None or [g.to_gpu_info() for g in host.gpus] != [g.to_gpu_info() for g in self.host.gpus]
-                   or unhealthy != self.unhealthy or xcds != self.unhealthy_xcds)
+                   or unhealthy != self.unhealthy or xcds != self.unhealthy_xcds or formats != self.matrix_faults)
         if changed:
             self.sync()
         else:
@@ -344,18 +366,24 @@ class NodeAgent:
             t.join(timeout=5)
 
 
-def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0,
-                  sweep_args: dict | None = None) -> Callable[[int], "bool | GpuHealth"]:
+def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args: dict | None = None,
+                  matrix: bool = False, matrix_formats: list | None = None,
+                  matrix_args: dict | None = None) -> Callable[[int], "bool | GpuHealth"]:
     """Health callback backed by the HIP probes (HBM pattern + checksum and an
     MFMA tile check per GPU).
 
     `sweep`: also run the CU sweep (HipProbe.cu_sweep, `sweep_args` are its
-    keywords), which checks MFMA, VALU and LDS on every CU. The callback runs
-    on every heartbeat, so a sweep's verdict is reused for `sweep_period_s`.
-    On a device that shows all 8 XCDs the verdict is a GpuHealth naming the
-    bad physical XCDs; a partition device numbers its XCDs logically, so
-    there a failed sweep fails the device as a whole (a plain bool). CUs the
-    sweep could not reach are logged, never counted as failed."""
+    keywords), which checks MFMA, VALU and LDS on every CU. `matrix`: also run
+    the matrix-format sweep (HipProbe.matrix_sweep over `matrix_formats`, None
+    for all; `matrix_args` are its other keywords), which runs f16, f32, f64,
+    fp8, bf8, i8 and the block-scaled MX formats on every CU. The callback
+    runs on every heartbeat, so the sweeps' verdict is reused for
+    `sweep_period_s`. On a device that shows all 8 XCDs the verdict is a
+    GpuHealth naming the bad physical XCDs of either sweep, with
+    detail["matrixFaults"] = {xcd: [format, ...]}; a partition device numbers
+    its XCDs logically, so there a failed sweep fails the device as a whole (a
+    plain bool). CUs a sweep could not reach are logged, never counted as
+    failed."""
     from ..ops.hip_probe import probe
 
     p = probe()
@@ -365,15 +393,30 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0,
         now = time.monotonic()
         if dev in last and now - last[dev][0] < sweep_period_s:
             return last[dev][1]
-        s = p.cu_sweep(dev, **(sweep_args or {}))["summary"]
-        log.log(logging.WARNING if s["bad_xcds"] else logging.INFO,
-                "cu sweep GPU %d: %d CUs on %d XCDs in %.2f ms (%d launch(es)), covered=%s uncovered=%s bad_xcds=%s",
-                dev, s["cus_seen"], len(s["xcds"]), s["ms"], s["rounds"], s["covered"],
-                {x: n for x, n in s["uncovered"].items() if n}, s["bad_xcds"])
+        bad: set[int] = set()
+        detail: dict = {}
+        if sweep:
+            s = p.cu_sweep(dev, **(sweep_args or {}))["summary"]
+            log.log(logging.WARNING if s["bad_xcds"] else logging.INFO,
+                    "cu sweep GPU %d: %d CUs on %d XCDs in %.2f ms (%d launch(es)), covered=%s uncovered=%s "
+                    "bad_xcds=%s", dev, s["cus_seen"], len(s["xcds"]), s["ms"], s["rounds"], s["covered"],
+                    {x: n for x, n in s["uncovered"].items() if n}, s["bad_xcds"])
+            bad |= set(s["bad_xcds"])
+            detail["sweep"] = s
+        if matrix:
+            m = p.matrix_sweep(dev, formats=matrix_formats, **(matrix_args or {}))["summary"]
+            faults = {int(x): list(v["failed_formats"]) for x, v in m["xcds"].items() if v["failed_formats"]}
+            log.log(logging.WARNING if m["bad_xcds"] else logging.INFO,
+                    "matrix sweep GPU %d: %d CUs on %d XCDs in %.2f ms (%d launch(es)), covered=%s uncovered=%s "
+                    "faults=%s", dev, m["cus_seen"], len(m["xcds"]), m["ms"], m["rounds"], m["covered"],
+                    {x: n for x, n in m["uncovered"].items() if n}, faults)
+            bad |= set(m["bad_xcds"])
+            detail["matrixSweep"] = m
+            detail["matrixFaults"] = faults
         if int(p.props(dev)["computeUnits"]) // 32 >= XCDS_PER_GPU:
-            v = GpuHealth(not s["bad_xcds"], frozenset(s["bad_xcds"]), {"sweep": s})
+            v = GpuHealth(not bad, frozenset(bad), detail)
         else:
-            v = not s["bad_xcds"]
+            v = not bad
         last[dev] = (now, v)
         return v
 
@@ -381,7 +424,7 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0,
         # HBM pattern/checksum and an exact-integer MFMA tile: a GPU whose matrix
         # cores mis-compute is withheld even if its memory checks out.
         ok = bool(p.health(dev)["healthy"]) and bool(p.mfma_check(dev)["healthy"])
-        if not sweep or not ok:
+        if not (sweep or matrix) or not ok:
             return ok
         return sweep_verdict(dev)
 

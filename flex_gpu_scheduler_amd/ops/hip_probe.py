@@ -1,5 +1,5 @@
 """ctypes front-end for the HIP/CDNA4 device probes (csrc/hip/hbm_probe.hip,
-csrc/hip/mfma_probe.hip, csrc/hip/cu_sweep.hip).
+csrc/hip/mfma_probe.hip, csrc/hip/cu_sweep.hip, csrc/hip/matrix_sweep.hip).
 
 The probes are what the node agent runs before advertising an MI355X as
 schedulable: device properties, HBM streaming bandwidth (optionally with a
@@ -7,7 +7,9 @@ partition-sized CU budget), an XCD census that verifies the compute-partition
 mode, a checksum health test, an exact-integer MFMA tile check of the matrix
 cores, the dense bf16 MFMA throughput of the whole GPU or of one
 partition's XCDs, and a sweep that checks MFMA, VALU and LDS on every CU and
-names the XCD of a CU that mis-computes.
+names the XCD of a CU that mis-computes, and a sweep that runs every matrix
+format (f16, f32, f64, fp8, bf8, i8 and the block-scaled MX fp8/fp6/fp4) on
+every CU and names the formats a CU gets wrong.
 """
 from __future__ import annotations
 
@@ -53,6 +55,10 @@ DEFAULT_BYTES = 1 << 30
 SWEEP_ENGINES = {1: "mfma", 2: "valu", 4: "lds"}  # fail bit -> digest of that engine
 SWEEP_LDS_MAX = 160 << 10
 SWEEP_BAD_ARGS = -1000
+
+# k_matrix_sweep (csrc/hip/matrix_sweep.hip): one 64-byte record per workgroup,
+# {xcd, cu, simd_mask, fail, one digest per format, 0}.
+MATRIX_RECORD_WORDS = 16
 
 
 class HipProbe:
@@ -112,6 +118,16 @@ class HipProbe:
         L.xs_cu_sweep.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, ctypes.c_int,
                                   ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int),
                                   ctypes.POINTER(ctypes.c_double)]
+        L.xs_matrix_sweep_last_error.restype = ctypes.c_char_p
+        L.xs_matrix_formats.restype = ctypes.c_char_p
+        L.xs_matrix_shape.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        L.xs_matrix_inputs.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_void_p]
+        L.xs_matrix_tile.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+        L.xs_matrix_sweep_expected.argtypes = [ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
+        L.xs_matrix_sweep.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int),
+                                      ctypes.POINTER(ctypes.c_double)]
 
     def _err(self, rc: int, what: str) -> ProbeError:
         detail = "bad arguments" if rc == BAD_ARGS else self.lib.xs_last_error().decode(errors="replace")
@@ -433,6 +449,125 @@ class HipProbe:
         summary.update(rounds=rounds, ms=total_ms, blocks=n_blocks, k=k, lds_bytes=lds_bytes)
         return {"records": records, "summary": summary}
 
+    # --------------------------------------------------------- matrix sweep
+    def matrix_formats(self) -> list[str]:
+        """Format names of the matrix sweep; the index is the format's bit."""
+        return self.lib.xs_matrix_formats().decode().split(",")
+
+    def _matrix_mask(self, formats) -> int:
+        names = self.matrix_formats()
+        if formats is None:
+            return (1 << len(names)) - 1
+        mask = 0
+        for f in [formats] if isinstance(formats, str) else formats:
+            if f not in names:
+                raise ValueError(f"unknown matrix format {f!r}; known: {', '.join(names)}")
+            mask |= 1 << names.index(f)
+        return mask
+
+    def matrix_shape(self, fmt: str) -> dict:
+        """`tile` (the result is tile x tile), `k` (both K-steps), `blocks`
+        (32-element scale blocks along K; 0 when not block-scaled),
+        `accumulator` and `frac` (every result is a multiple of 2^-frac)."""
+        out = (ctypes.c_int * 5)()
+        self._matrix_mask([fmt])
+        rc = self.lib.xs_matrix_shape(self.matrix_formats().index(fmt), out)
+        if rc != 0:
+            raise _matrix_error(self, rc, "matrix_shape")
+        return {"tile": out[0], "k": out[1], "blocks": out[2], "accumulator": ("f32", "f64", "i32")[out[3]],
+                "frac": out[4]}
+
+    def matrix_inputs(self, fmt: str) -> dict:
+        """The operand encodings of one format, as the kernels build them:
+        `a` [tile, k] and `b` [k, tile] (uint64 bit patterns: IEEE bits for
+        f16/f32/f64, one byte for fp8/bf8/i8, the 6- or 4-bit code for the MX
+        fp6/fp4 rows) and, for the block-scaled rows, the E8M0 scale bytes
+        `a_scale` [tile, k/32] and `b_scale` [k/32, tile] (else None)."""
+        import numpy as np
+
+        sh = self.matrix_shape(fmt)
+        t, k, nb = sh["tile"], sh["k"], sh["blocks"]
+        a, b = np.zeros((t, k), np.uint64), np.zeros((k, t), np.uint64)
+        sa = np.zeros((t, nb), np.uint8) if nb else None
+        sb = np.zeros((nb, t), np.uint8) if nb else None
+        rc = self.lib.xs_matrix_inputs(self.matrix_formats().index(fmt), a.ctypes.data, b.ctypes.data,
+                                       sa.ctypes.data if nb else None, sb.ctypes.data if nb else None)
+        if rc != 0:
+            raise _matrix_error(self, rc, "matrix_inputs")
+        return {"a": a, "b": b, "a_scale": sa, "b_scale": sb, **sh}
+
+    def matrix_tile(self, dev: int, fmt: str):
+        """k_matrix_tile: one wave computes the format's product; the whole
+        result tile as float64 (int64 for i8)."""
+        import numpy as np
+
+        sh = self.matrix_shape(fmt)
+        out = np.zeros((sh["tile"], sh["tile"]), np.float64)
+        rc = self.lib.xs_matrix_tile(dev, self.matrix_formats().index(fmt), out.ctypes.data)
+        if rc != 0:
+            raise _matrix_error(self, rc, "matrix_tile")
+        return out.astype(np.int64) if sh["accumulator"] == "i32" else out
+
+    def matrix_sweep_expected(self, formats=None) -> dict:
+        """The workgroup digest a healthy CU leaves per selected format,
+        computed on the host from the decoded operand encodings."""
+        names = self.matrix_formats()
+        mask = self._matrix_mask(formats)
+        out = (ctypes.c_uint32 * len(names))()
+        rc = self.lib.xs_matrix_sweep_expected(mask, out)
+        if rc != 0:
+            raise _matrix_error(self, rc, "matrix_sweep_expected")
+        return {n: out[i] for i, n in enumerate(names) if mask >> i & 1}
+
+    def matrix_sweep(self, dev: int = 0, formats=None, blocks: int = 0, inject: tuple | None = None,
+                     max_rounds: int = 4) -> dict:
+        """k_matrix_sweep: every selected matrix format (None: all) run on
+        every CU a workgroup lands on. `inject` = (xcd, cu key or None for
+        every CU of that XCD, [format names]): those workgroups flip one bit
+        of one result element of those formats (tests the comparator on a
+        healthy GPU). `blocks` 0: 4 per CU.
+
+        Relaunched while some CU has not been seen, as cu_sweep does. Returns
+        {"records": [...], "summary": summarize_matrix_sweep(...) plus rounds,
+        ms, blocks, formats}."""
+        names = self.matrix_formats()
+        mask = self._matrix_mask(formats)
+        cus = int(self.props(dev)["computeUnits"])
+        n_blocks = blocks if blocks != 0 else 4 * cus
+        ix, ic, im = -1, -1, 0
+        if inject is not None:
+            ix, ic, im = int(inject[0]), -1 if inject[1] is None else int(inject[1]), self._matrix_mask(inject[2])
+        expected = None
+        records: list[dict] = []
+        total_ms, rounds = 0.0, 0
+        summary: dict = {}
+        for _ in range(max(1, max_rounds if n_blocks >= cus else 1)):
+            buf = (ctypes.c_uint32 * (MATRIX_RECORD_WORDS * max(1, n_blocks)))()
+            n, ms = ctypes.c_int(), ctypes.c_double()
+            rc = self.lib.xs_matrix_sweep(dev, n_blocks, mask, ix, ic, im, buf, ctypes.byref(n), ctypes.byref(ms))
+            if rc != 0:
+                raise _matrix_error(self, rc, "matrix_sweep")
+            if expected is None:
+                expected = self.matrix_sweep_expected([f for i, f in enumerate(names) if mask >> i & 1])
+            rounds += 1
+            total_ms += ms.value
+            for i in range(n.value):
+                w = buf[MATRIX_RECORD_WORDS * i:MATRIX_RECORD_WORDS * (i + 1)]
+                rec = {"xcd": w[0], "cu": w[1], "simd_mask": w[2], "fail": w[3],
+                       "digests": {f: w[4 + b] for b, f in enumerate(names)}}
+                # A digest that differs from the host's is a failure even if
+                # the device-side comparator (on the same CU) passed it.
+                for b, f in enumerate(names):
+                    if rec["digests"][f] != expected.get(f, 0):
+                        rec["fail"] |= 1 << b
+                records.append(rec)
+            summary = summarize_matrix_sweep(records, cus, names)
+            if summary["covered"]:
+                break
+        summary.update(rounds=rounds, ms=total_ms, blocks=n_blocks,
+                       formats=[f for i, f in enumerate(names) if mask >> i & 1])
+        return {"records": records, "summary": summary}
+
 
 def _sweep_error(p: HipProbe, rc: int, what: str) -> ProbeError:
     detail = "bad arguments" if rc == SWEEP_BAD_ARGS else p.lib.xs_cu_sweep_last_error().decode(errors="replace")
@@ -466,6 +601,30 @@ def summarize_sweep(records: list[dict], compute_units: int) -> dict:
         uncovered[x] = max(0, expected - len(seen[x]))
     return {"xcds": xcds, "bad_xcds": sorted(failed), "covered": bool(seen) and not any(uncovered.values()),
             "uncovered": uncovered, "cus_seen": sum(len(v) for v in seen.values())}
+
+
+def _matrix_error(p: HipProbe, rc: int, what: str) -> ProbeError:
+    detail = "bad arguments" if rc == BAD_ARGS else p.lib.xs_matrix_sweep_last_error().decode(errors="replace")
+    e = ProbeError(f"{what} failed ({rc}): {detail}")
+    e.rc = rc
+    return e
+
+
+def summarize_matrix_sweep(records: list[dict], compute_units: int, formats: list[str]) -> dict:
+    """summarize_sweep over k_matrix_sweep records, whose fail bits are format
+    bits (`formats` names them in bit order): adds `failed_formats` per XCD
+    and overall."""
+    s = summarize_sweep(records, compute_units)
+
+    def names(bits: int) -> list[str]:
+        return [f for b, f in enumerate(formats) if bits >> b & 1]
+
+    every = 0
+    for v in s["xcds"].values():
+        v["failed_formats"] = names(v["fail_bits"])
+        every |= v["fail_bits"]
+    s["failed_formats"] = names(every)
+    return s
 
 
 _probe: HipProbe | None = None
