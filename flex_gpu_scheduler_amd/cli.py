@@ -329,13 +329,29 @@ def cmd_manager(args) -> int:
     return 0
 
 
+def _gib_or_all(s: str):
+    """--health-hbm-sweep's value: a positive number of GiB, or "all"."""
+    if s == "all":
+        return s
+    gib = float(s)
+    if not gib > 0:
+        raise argparse.ArgumentTypeError(f"{s!r} is not a positive number of GiB")
+    return gib
+
+
 def health_fn_args(args) -> dict:
     """hip_health_fn's keywords from the node-agent flags.
-    --health-matrix-sweep: absent -> None, bare -> "all", else a comma list."""
+    --health-matrix-sweep: absent -> None, bare -> "all", else a comma list.
+    --health-hbm-sweep: absent -> no hbm keys, bare -> all free HBM less the
+    reserve (hbm_gib None), else that many GiB."""
     m = args.health_matrix_sweep
     formats = None if m in (None, "all") else [f.strip() for f in m.split(",") if f.strip()]
-    return {"sweep": args.health_sweep, "sweep_period_s": args.health_sweep_period, "matrix": m is not None,
-            "matrix_formats": formats}
+    kw = {"sweep": args.health_sweep, "sweep_period_s": args.health_sweep_period, "matrix": m is not None,
+          "matrix_formats": formats}
+    h = getattr(args, "health_hbm_sweep", None)
+    if h is not None:
+        kw.update(hbm=True, hbm_gib=None if h == "all" else float(h))
+    return kw
 
 
 def cmd_node_agent(args) -> int:
@@ -353,7 +369,7 @@ def cmd_node_agent(args) -> int:
                       reserved_memory_gib=args.reserved_memory_gib,
                       health_fn=(hip_health_fn(**health_fn_args(args))
                                  if args.health_probe or args.health_sweep or args.health_matrix_sweep is not None
-                                 else None),
+                                 or args.health_hbm_sweep is not None else None),
                       bandwidth_fn=hip_bandwidth_fn() if args.bandwidth_probe else None,
                       kubelet_managed=args.kubelet_managed).start()
     if args.device_plugin:
@@ -517,6 +533,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "mxfp8, mxbf8, mxfp6, mxbf6, mxfp4 run on every CU (a comma list selects some; default all); "
                         "a bad XCD is fenced like --health-sweep's and its formats are published as matrixFaults. "
                         "Implies --health-probe; independent of --health-sweep")
+    p.add_argument("--health-hbm-sweep", nargs="?", const="all", default=None, metavar="GIB", type=_gib_or_all,
+                   help="health probe plus the HBM sweep: an address-keyed pattern written over all free HBM less a "
+                        "2 GiB reserve (or GIB of it), read back from DRAM in both polarities; a fault withholds the "
+                        "whole GPU and is published as hbmFaults. The sweep holds the memory it tests, so a tenant's "
+                        "allocation can fail while it runs: cap it with GIB and space it with --health-sweep-period. "
+                        "Implies --health-probe; independent of the other sweeps")
     p.add_argument("--health-sweep-period", type=float, default=600.0, metavar="SECONDS",
                    help="reuse a sweep's verdict this long before sweeping the GPU again")
     p.add_argument("--bandwidth-probe", action="store_true",

@@ -16,6 +16,8 @@ exporter + metrics-server:
     e.g. from the CU sweep) fences only the compute partitions holding them
     on a DPX/QPX/CPX GPU (`xcdFaults` in the topology annotation), and the
     matrix formats such an XCD gets wrong are published as `matrixFaults`;
+    a verdict that carries an HBM fault (the HBM sweep) withholds the whole
+    GPU, partitioned or not, and is published as `hbmFaults`;
   * samples load (gpu/telemetry.py) and publishes its WatcherMetrics document
     for the Trimaran plugins.
 """
@@ -54,7 +56,8 @@ class GpuHealth:
     physical XCD ids (0-7) that hold a faulty CU. An SPX GPU with a bad XCD is
     withheld like an unhealthy one; on a DPX/QPX/CPX GPU only the compute
     partitions that contain a bad XCD are fenced. `ok` False with no bad XCD
-    is a whole-GPU failure."""
+    is a whole-GPU failure, and so is a verdict whose detail["hbmFaults"] is
+    not empty, whatever XCDs it names."""
     ok: bool
     bad_xcds: frozenset = frozenset()
     detail: dict = field(default_factory=dict, compare=False)
@@ -97,6 +100,9 @@ class NodeAgent:
         # GPU index -> {XCD id: matrix formats it mis-computes}, from
         # GpuHealth.detail["matrixFaults"] (the matrix-format sweep).
         self.matrix_faults: dict[int, dict[int, list[str]]] = {}
+        # GPU index -> what the HBM sweep found wrong, from
+        # GpuHealth.detail["hbmFaults"]; such a GPU is withheld as a whole.
+        self.hbm_faults: dict[int, dict] = {}
         self._stop = threading.Event()
         self._threads: list[threading.Thread] = []
         self.host: HostInfo | None = None
@@ -115,13 +121,21 @@ class NodeAgent:
         marks the XCDs of a partitioned one."""
         return self._probe_health(host)[:2]
 
-    def _probe_health(self, host: HostInfo) -> tuple[set[int], dict[int, set[int]], dict[int, dict[int, list[str]]]]:
-        """probe_health plus the matrix formats each bad XCD got wrong."""
+    def _probe_health(self, host: HostInfo) -> tuple[set[int], dict[int, set[int]], dict[int, dict[int, list[str]]],
+                                                     dict[int, dict]]:
+        """probe_health plus the matrix formats each bad XCD got wrong and the
+        HBM faults per GPU.
+
+        An HBM fault (detail["hbmFaults"]) withholds the whole GPU, partitioned
+        or not, and even when the same verdict names bad XCDs: the sweep knows
+        a fault by its virtual address, which cannot be tied to the HBM slice
+        of one compute partition, so there is no partial fence for memory."""
         if self.health_fn is None:
-            return set(), {}, {}
+            return set(), {}, {}, {}
         bad: set[int] = set()
         xcds: dict[int, set[int]] = {}
         formats: dict[int, dict[int, list[str]]] = {}
+        hbm: dict[int, dict] = {}
         # HIP ordinals follow the KFD node order of the GPUs this process can
         # open; GPUs whose KFD node is hidden (other containers' devices) are
         # not probed. With no KFD info at all (fake hosts) use the index.
@@ -134,16 +148,20 @@ class NodeAgent:
                     mf = {int(x): list(f) for x, f in (r.detail.get("matrixFaults") or {}).items() if f}
                     if mf:
                         formats[g.index] = mf
+                    if r.detail.get("hbmFaults"):
+                        hbm[g.index] = dict(r.detail["hbmFaults"])
                 if isinstance(r, GpuHealth) and r.bad_xcds:
                     xcds[g.index] = set(r.bad_xcds)
-                    if g.partitions == 1:
+                    if g.partitions == 1 or g.index in hbm:
                         bad.add(g.index)
+                elif g.index in hbm:
+                    bad.add(g.index)
                 elif not (r.ok if isinstance(r, GpuHealth) else r):
                     bad.add(g.index)
             except Exception as e:  # noqa: BLE001
                 log.warning("health probe GPU %d failed: %s", g.index, e)
                 bad.add(g.index)
-        return bad, xcds, formats
+        return bad, xcds, formats, hbm
 
     @staticmethod
     def _fenced(gpus, xcd_faults) -> dict[int, tuple[int, int]]:
@@ -179,7 +197,8 @@ class NodeAgent:
 
     def build_node(self, host: HostInfo, unhealthy: set[int] = frozenset(),
                    xcd_faults: dict[int, set[int]] | None = None,
-                   matrix_faults: dict[int, dict[int, list[str]]] | None = None) -> dict:
+                   matrix_faults: dict[int, dict[int, list[str]]] | None = None,
+                   hbm_faults: dict[int, dict] | None = None) -> dict:
         healthy = [g for g in host.gpus if g.index not in unhealthy]
         infos = [g.to_gpu_info() for g in healthy]
         mem_kib = max(0, host.memory_bytes // 1024 - self.reserved_memory_gib * (1 << 20))
@@ -213,6 +232,10 @@ class NodeAgent:
         formats = {i: per for i, per in formats.items() if per}
         if formats:
             topo["matrixFaults"] = formats
+        # What the HBM sweep found on a GPU (which is withheld as a whole).
+        hbm = {str(i): dict(f) for i, f in sorted((hbm_faults or {}).items()) if f}
+        if hbm:
+            topo["hbmFaults"] = hbm
         node["metadata"]["annotations"][TOPOLOGY_ANNOTATION] = json.dumps(topo, sort_keys=True)
         if self.bandwidth:
             node["metadata"]["annotations"][BANDWIDTH_ANNOTATION] = json.dumps(
@@ -304,14 +327,14 @@ class NodeAgent:
 
     def sync(self) -> HostInfo:
         host = self.host_fn()
-        self.unhealthy, self.unhealthy_xcds, self.matrix_faults = self._probe_health(host)
+        self.unhealthy, self.unhealthy_xcds, self.matrix_faults, self.hbm_faults = self._probe_health(host)
         self.measure_bandwidth(host)
         for dp in self.device_plugins:
             dp.host = host
             dp.set_unhealthy(self.unhealthy)
             dp.set_unhealthy_xcds(self.unhealthy_xcds)
-        self._upsert("nodes", self.build_node(host, self.unhealthy, self.unhealthy_xcds, self.matrix_faults),
-                     keep_spec=True)
+        self._upsert("nodes", self.build_node(host, self.unhealthy, self.unhealthy_xcds, self.matrix_faults,
+                                              self.hbm_faults), keep_spec=True)
         self._upsert("noderesourcetopologies", self.build_nrt(host, self.unhealthy, self.unhealthy_xcds),
                      keep_spec=False)
         self.host = host
@@ -352,9 +375,10 @@ class NodeAgent:
 
     def _heartbeat_and_resync(self) -> None:
         host = self.host_fn()
-        unhealthy, xcds, formats = self._probe_health(host)
+        unhealthy, xcds, formats, hbm = self._probe_health(host)
         changed = (self.host is None or [g.to_gpu_info() for g in host.gpus] != [g.to_gpu_info() for g in self.host.gpus]
-                   or unhealthy != self.unhealthy or xcds != self.unhealthy_xcds or formats != self.matrix_faults)
+                   or unhealthy != self.unhealthy or xcds != self.unhealthy_xcds or formats != self.matrix_faults
+                   or hbm != self.hbm_faults)
         if changed:
             self.sync()
         else:
@@ -368,7 +392,8 @@ class NodeAgent:
 
 def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args: dict | None = None,
                   matrix: bool = False, matrix_formats: list | None = None,
-                  matrix_args: dict | None = None) -> Callable[[int], "bool | GpuHealth"]:
+                  matrix_args: dict | None = None, hbm: bool = False, hbm_gib: float | None = None,
+                  hbm_args: dict | None = None) -> Callable[[int], "bool | GpuHealth"]:
     """Health callback backed by the HIP probes (HBM pattern + checksum and an
     MFMA tile check per GPU).
 
@@ -383,8 +408,19 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
     detail["matrixFaults"] = {xcd: [format, ...]}; a partition device numbers
     its XCDs logically, so there a failed sweep fails the device as a whole (a
     plain bool). CUs a sweep could not reach are logged, never counted as
-    failed."""
-    from ..ops.hip_probe import probe
+    failed.
+
+    `hbm`: also run the HBM sweep (HipProbe.hbm_sweep over `hbm_gib` GiB, None
+    for all free HBM less its reserve; `hbm_args` are its other keywords) under
+    the same period, with or without the other two. It holds the memory it
+    tests for its duration, so a tenant's allocation can fail in that window:
+    hence the GiB cap and the period. A fault makes the verdict, on every kind
+    of device, a GpuHealth with ok False, the bad XCDs of the other sweeps,
+    detail["hbmSweep"] (the summary) and detail["hbmFaults"] (what the agent
+    publishes); the agent withholds such a GPU as a whole. A device on which no
+    memory could be had is logged as unswept and a sweep that got less than it
+    asked for as short; neither fails the device."""
+    from ..ops.hip_probe import HBM_UNSWEPT, ProbeError, probe
 
     p = probe()
     last: dict[int, tuple[float, object]] = {}  # dev -> (monotonic time, sweep verdict)
@@ -413,7 +449,32 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
             bad |= set(m["bad_xcds"])
             detail["matrixSweep"] = m
             detail["matrixFaults"] = faults
-        if int(p.props(dev)["computeUnits"]) // 32 >= XCDS_PER_GPU:
+        hbm_faults: dict = {}
+        if hbm:
+            h = None
+            try:
+                h = p.hbm_sweep(dev, nbytes=int(hbm_gib * (1 << 30)) if hbm_gib else 0, **(hbm_args or {}))["summary"]
+            except ProbeError as e:
+                if e.rc != HBM_UNSWEPT:
+                    raise
+                log.warning("hbm sweep GPU %d: unswept, no memory could be had (%s)", dev, e)
+            if h is not None:
+                gib = h["bytes_tested"] / (1 << 30)
+                log.log(logging.WARNING if h["bad_vectors"] or h["short"] else logging.INFO,
+                        "hbm sweep GPU %d: %.2f GiB%s in %s ms (%s GB/s), from_dram=%s bad_vectors=%d bad_bits=%d "
+                        "flip_mask=%s bad_chunks=%s", dev, gib, " (short: less than asked for)" if h["short"] else "",
+                        h["ms"], h["GBps"], h["from_dram"], h["bad_vectors"], h["bad_bits"], h["flip_mask"],
+                        h["bad_chunks"])
+                if h["bad_vectors"]:
+                    hbm_faults = {"badVectors": h["bad_vectors"], "badBits": h["bad_bits"],
+                                  "flipMask": h["flip_mask"], "oneToZero": h["one_to_zero"],
+                                  "zeroToOne": h["zero_to_one"], "testedGiB": round(gib, 3),
+                                  "fromDram": h["from_dram"], "readerXcds": list(h["reader_xcds"])}
+                detail["hbmSweep"] = h
+                detail["hbmFaults"] = hbm_faults
+        if hbm_faults:
+            v = GpuHealth(False, frozenset(bad), detail)
+        elif int(p.props(dev)["computeUnits"]) // 32 >= XCDS_PER_GPU:
             v = GpuHealth(not bad, frozenset(bad), detail)
         else:
             v = not bad
@@ -424,7 +485,7 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
         # HBM pattern/checksum and an exact-integer MFMA tile: a GPU whose matrix
         # cores mis-compute is withheld even if its memory checks out.
         ok = bool(p.health(dev)["healthy"]) and bool(p.mfma_check(dev)["healthy"])
-        if not (sweep or matrix) or not ok:
+        if not (sweep or matrix or hbm) or not ok:
             return ok
         return sweep_verdict(dev)
 

@@ -1,5 +1,6 @@
 """ctypes front-end for the HIP/CDNA4 device probes (csrc/hip/hbm_probe.hip,
-csrc/hip/mfma_probe.hip, csrc/hip/cu_sweep.hip, csrc/hip/matrix_sweep.hip).
+csrc/hip/mfma_probe.hip, csrc/hip/cu_sweep.hip, csrc/hip/matrix_sweep.hip,
+csrc/hip/hbm_sweep.hip).
 
 The probes are what the node agent runs before advertising an MI355X as
 schedulable: device properties, HBM streaming bandwidth (optionally with a
@@ -9,7 +10,9 @@ cores, the dense bf16 MFMA throughput of the whole GPU or of one
 partition's XCDs, and a sweep that checks MFMA, VALU and LDS on every CU and
 names the XCD of a CU that mis-computes, and a sweep that runs every matrix
 format (f16, f32, f64, fp8, bf8, i8 and the block-scaled MX fp8/fp6/fp4) on
-every CU and names the formats a CU gets wrong.
+every CU and names the formats a CU gets wrong, and a sweep of all free HBM
+with an address-keyed pattern in both polarities that names the vectors and
+bits that read back wrong.
 """
 from __future__ import annotations
 
@@ -59,6 +62,61 @@ SWEEP_BAD_ARGS = -1000
 # k_matrix_sweep (csrc/hip/matrix_sweep.hip): one 64-byte record per workgroup,
 # {xcd, cu, simd_mask, fail, one digest per format, 0}.
 MATRIX_RECORD_WORDS = 16
+
+# k_hbm_fill / k_hbm_verify (csrc/hip/hbm_sweep.hip)
+HBM_SWEEP_SEED = 0x5EED1E55
+HBM_SWEEP_LOG_CAP = 32
+HBM_SWEEP_STRIPES = 16
+HBM_SWEEP_BAD_CHUNKS = 64
+HBM_BAD_BUFFER = -1001
+# xs_hbm_sweep could not allocate even its first chunk: nothing was tested.
+# The GPU is unswept, never failed.
+HBM_UNSWEPT = -1003
+# From this size a sweep's reads come from HBM: 4x the 256 MiB Infinity Cache.
+HBM_FROM_DRAM_BYTES = 1 << 30
+HBM_NO_INJECT = (1 << 64) - 1
+
+
+class _HbmLogEntry(ctypes.Structure):
+    _fields_ = [("v", ctypes.c_uint64), ("expected", ctypes.c_uint32 * 4), ("actual", ctypes.c_uint32 * 4),
+                ("xcd", ctypes.c_uint32), ("pass_", ctypes.c_uint32)]
+
+
+class _HbmStripe(ctypes.Structure):
+    _fields_ = [("vectors_read", ctypes.c_uint64), ("fold", ctypes.c_uint64), ("reserved", ctypes.c_uint64 * 14)]
+
+
+class _HbmSweepResult(ctypes.Structure):
+    # The waves of a launch spread their (vectors_read, fold) atomics over 16
+    # stripes of one 128-byte line each: the count is their sum, the fold their XOR.
+    _fields_ = [("stripe", _HbmStripe * HBM_SWEEP_STRIPES), ("bad_vectors", ctypes.c_uint64),
+                ("bad_bits", ctypes.c_uint64), ("one_to_zero", ctypes.c_uint64), ("zero_to_one", ctypes.c_uint64),
+                ("flip_or", ctypes.c_uint32 * 4), ("reader_xcd_mask", ctypes.c_uint32),
+                ("log_claims", ctypes.c_uint32), ("log", _HbmLogEntry * HBM_SWEEP_LOG_CAP),
+                ("pad", ctypes.c_uint8 * 72)]
+
+
+class _HbmBadChunk(ctypes.Structure):
+    _fields_ = [("chunk", ctypes.c_uint64), ("bad_vectors", ctypes.c_uint64)]
+
+
+class _HbmSweepSummary(ctypes.Structure):
+    _fields_ = [("bytes_requested", ctypes.c_uint64), ("bytes_tested", ctypes.c_uint64),
+                ("chunk_bytes", ctypes.c_uint64), ("chunks", ctypes.c_uint32), ("short", ctypes.c_uint32),
+                ("vectors_read", ctypes.c_uint64), ("fold", ctypes.c_uint64 * 2), ("bad_vectors", ctypes.c_uint64),
+                ("bad_bits", ctypes.c_uint64), ("one_to_zero", ctypes.c_uint64), ("zero_to_one", ctypes.c_uint64),
+                ("flip_or", ctypes.c_uint32 * 4), ("reader_xcd_mask", ctypes.c_uint32),
+                ("log_entries", ctypes.c_uint32), ("ms", ctypes.c_double * 3), ("bad_chunks", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("bad_chunk", _HbmBadChunk * HBM_SWEEP_BAD_CHUNKS)]
+
+
+assert ctypes.sizeof(_HbmLogEntry) == 48 and ctypes.sizeof(_HbmSweepResult) == 3712 and _HbmSweepResult.log.offset == 2104
+assert ctypes.sizeof(_HbmSweepSummary) == 144 + 16 * HBM_SWEEP_BAD_CHUNKS
+
+
+def _hbm_log(entries) -> list[dict]:
+    return [{"v": int(e.v), "expected": [int(w) for w in e.expected], "actual": [int(w) for w in e.actual],
+             "xcd": int(e.xcd), "pass": int(e.pass_)} for e in entries]
 
 
 class HipProbe:
@@ -128,6 +186,13 @@ class HipProbe:
         L.xs_matrix_sweep.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int),
                                       ctypes.POINTER(ctypes.c_double)]
+        L.xs_hbm_sweep_last_error.restype = ctypes.c_char_p
+        L.xs_hbm_sweep_pattern.argtypes = [ctypes.c_uint64, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int,
+                                           ctypes.c_void_p]
+        L.xs_hbm_sweep_op.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64,
+                                      ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p]
+        L.xs_hbm_sweep.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint64,
+                                   ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
 
     def _err(self, rc: int, what: str) -> ProbeError:
         detail = "bad arguments" if rc == BAD_ARGS else self.lib.xs_last_error().decode(errors="replace")
@@ -186,11 +251,12 @@ class HipProbe:
     # must be imported before this library is loaded (one HIP runtime: both
     # resolve the soname libamdhip64.so.7 to the same copy).
     @staticmethod
-    def _dev_buf(t, what: str) -> tuple[int, int]:
+    def _dev_buf(t, what: str, granular: bool = True) -> tuple[int, int]:
+        """`granular` False leaves the 16-byte size and alignment check to the C ABI."""
         if not t.is_cuda or not t.is_contiguous():
             raise ValueError(f"{what} must be a contiguous device tensor")
         nbytes = t.numel() * t.element_size()
-        if nbytes % 16 or t.data_ptr() % 16:
+        if granular and (nbytes % 16 or t.data_ptr() % 16):
             raise ValueError(f"{what}: {nbytes} bytes at {t.data_ptr():#x} is not 16-byte granular")
         return t.data_ptr(), nbytes
 
@@ -567,6 +633,128 @@ class HipProbe:
         summary.update(rounds=rounds, ms=total_ms, blocks=n_blocks,
                        formats=[f for i, f in enumerate(names) if mask >> i & 1])
         return {"records": records, "summary": summary}
+
+    # ------------------------------------------------------------ HBM sweep
+    def hbm_sweep_pattern(self, first_vec: int, nvec: int, seed: int = HBM_SWEEP_SEED, inverted: bool = False):
+        """The sweep's pattern for 16-byte vectors [first_vec, first_vec +
+        nvec), computed on the host: uint32 [nvec, 4]. No device call."""
+        import numpy as np
+
+        out = np.zeros((nvec, 4), np.uint32)
+        rc = self.lib.xs_hbm_sweep_pattern(first_vec, nvec, seed, int(inverted), out.ctypes.data)
+        if rc != 0:
+            raise _hbm_error(self, rc, "hbm_sweep_pattern")
+        return out
+
+    def hbm_sweep_op(self, buf, pass_: int, first_vec: int = 0, seed: int = HBM_SWEEP_SEED,
+                     grid: int = 0) -> dict | None:
+        """One pass of the HBM sweep over the device tensor `buf`, whose first
+        16-byte vector has global index `first_vec`: 0 fills the pattern, 1
+        checks it and writes the complement of the expected value, 2 checks
+        the complement. `grid` > 0: that many workgroups instead of 8 per CU.
+        Passes 1 and 2 return the launch's result: vectors_read, fold,
+        bad_vectors, bad_bits, one_to_zero, zero_to_one, flip_or [4],
+        reader_xcd_mask, log_claims and log (at most 32 entries). Size and
+        alignment are the C ABI's to refuse (ProbeError, rc -1000 / -1001)."""
+        p, n = self._dev_buf(buf, "buf", granular=False)
+        res = _HbmSweepResult()
+        rc = self.lib.xs_hbm_sweep_op(buf.device.index or 0, pass_, p, n, first_vec, seed, grid,
+                                      ctypes.addressof(res) if pass_ != 0 else None)
+        if rc != 0:
+            raise _hbm_error(self, rc, "hbm_sweep_op")
+        if pass_ == 0:
+            return None
+        fold = 0
+        for st in res.stripe:
+            fold ^= int(st.fold)
+        return {"vectors_read": sum(int(st.vectors_read) for st in res.stripe), "fold": fold,
+                "bad_vectors": int(res.bad_vectors),
+                "bad_bits": int(res.bad_bits), "one_to_zero": int(res.one_to_zero),
+                "zero_to_one": int(res.zero_to_one), "flip_or": [int(w) for w in res.flip_or],
+                "reader_xcd_mask": int(res.reader_xcd_mask), "log_claims": int(res.log_claims),
+                "log": _hbm_log(res.log[:min(int(res.log_claims), HBM_SWEEP_LOG_CAP)])}
+
+    def hbm_sweep(self, dev: int = 0, nbytes: int = 0, chunk_bytes: int = 1 << 30, seed: int = HBM_SWEEP_SEED,
+                  inject: tuple | None = None) -> dict:
+        """The whole HBM sweep: fill, verify + invert, verify over `nbytes` of
+        HBM (0: all free HBM less a 2 GiB reserve) held in `chunk_bytes`
+        allocations until the last pass is done. `inject` = (global vector,
+        word 0..3, bit mask, after pass 0 or 1): the host flips those bits in
+        the sweep's own buffer between passes (tests the comparator on healthy
+        memory). Raises ProbeError with rc HBM_UNSWEPT when no memory could be
+        had: nothing was tested. Returns {"raw": the C summary as a dict,
+        "summary": summarize_hbm_sweep(raw)}."""
+        iv, iw, im, ip = HBM_NO_INJECT, 0, 0, 0
+        if inject is not None:
+            iv, iw, im, ip = (int(x) for x in inject)
+        s = _HbmSweepSummary()
+        log = (_HbmLogEntry * HBM_SWEEP_LOG_CAP)()
+        rc = self.lib.xs_hbm_sweep(dev, nbytes, chunk_bytes, seed, iv, iw, im, ip, ctypes.addressof(s),
+                                   ctypes.addressof(log))
+        if rc != 0:
+            raise _hbm_error(self, rc, "hbm_sweep")
+        raw = {"bytes_requested": int(s.bytes_requested), "bytes_tested": int(s.bytes_tested),
+               "chunk_bytes": int(s.chunk_bytes), "chunks": int(s.chunks), "short": bool(s.short),
+               "vectors_read": int(s.vectors_read), "fold": [int(f) for f in s.fold],
+               "bad_vectors": int(s.bad_vectors),
+               "bad_bits": int(s.bad_bits), "one_to_zero": int(s.one_to_zero), "zero_to_one": int(s.zero_to_one),
+               "flip_or": [int(w) for w in s.flip_or], "reader_xcd_mask": int(s.reader_xcd_mask),
+               "ms": [float(t) for t in s.ms], "bad_chunk_count": int(s.bad_chunks),
+               "bad_chunks": {int(b.chunk): int(b.bad_vectors)
+                              for b in s.bad_chunk[:min(int(s.bad_chunks), HBM_SWEEP_BAD_CHUNKS)]},
+               "log": _hbm_log(log[:int(s.log_entries)])}
+        return {"raw": raw, "summary": summarize_hbm_sweep(raw)}
+
+
+def _hbm_error(p: HipProbe, rc: int, what: str) -> ProbeError:
+    detail = {BAD_ARGS: "bad arguments", HBM_BAD_BUFFER: "null or mis-aligned buffer"}.get(rc)
+    if detail is None:
+        detail = p.lib.xs_hbm_sweep_last_error().decode(errors="replace")
+    e = ProbeError(f"{what} failed ({rc}): {detail}")
+    e.rc = rc
+    return e
+
+
+def summarize_hbm_sweep(raw: dict) -> dict:
+    """The verdict of one HBM sweep from xs_hbm_sweep's counters (`raw`:
+    bytes_tested, short, vectors_read, bad_vectors, bad_bits, one_to_zero,
+    zero_to_one, flip_or [4 words, word 0 = bytes 0..3 of a vector],
+    reader_xcd_mask, bad_chunks {chunk: bad vectors}, log, ms [3]).
+
+    `from_dram`: the sweep was large enough (1 GiB, 4x the Infinity Cache)
+    that its reads came from HBM. `flip_mask`: the 128 bits of a vector that
+    flipped anywhere, as hex (bit 0 = lowest bit of byte 0). `faults`: the
+    logged vectors by index, each with its byte offset into the sweep and the
+    flipped bits (0..127) by direction; at most 32 are logged, `bad_vectors`
+    counts them all. `GBps`: bytes moved over time per pass (pass 1 reads and
+    writes). `reader_xcds` are the XCDs whose waves read a bad vector, not
+    where the memory sits."""
+    tested = int(raw["bytes_tested"])
+    flip = 0
+    for j, w in enumerate(raw.get("flip_or", (0, 0, 0, 0))):
+        flip |= int(w) << (32 * j)
+    faults = []
+    for e in sorted(raw.get("log", ()), key=lambda e: (int(e["v"]), int(e["pass"]))):
+        exp = sum(int(w) << (32 * j) for j, w in enumerate(e["expected"]))
+        act = sum(int(w) << (32 * j) for j, w in enumerate(e["actual"]))
+        d = exp ^ act
+        faults.append({"v": int(e["v"]), "offset": int(e["v"]) * 16, "pass": int(e["pass"]), "xcd": int(e["xcd"]),
+                       "expected": [int(w) for w in e["expected"]], "actual": [int(w) for w in e["actual"]],
+                       "bits": [b for b in range(128) if d >> b & 1],
+                       "one_to_zero": [b for b in range(128) if (d & exp) >> b & 1],
+                       "zero_to_one": [b for b in range(128) if (d & ~exp) >> b & 1]})
+    ms = [float(t) for t in raw.get("ms", (0.0, 0.0, 0.0))]
+    moved = (tested, 2 * tested, tested)
+    mask = int(raw.get("reader_xcd_mask", 0))
+    bad = int(raw["bad_vectors"])
+    return {"bytes_tested": tested, "short": bool(raw.get("short", False)), "from_dram": tested >= HBM_FROM_DRAM_BYTES,
+            "vectors_read": int(raw["vectors_read"]), "bad_vectors": bad, "bad_bits": int(raw["bad_bits"]),
+            "one_to_zero": int(raw["one_to_zero"]), "zero_to_one": int(raw["zero_to_one"]),
+            "flip_mask": f"{flip:032x}", "reader_xcds": [x for x in range(32) if mask >> x & 1],
+            "bad_chunks": {int(c): int(n) for c, n in sorted(raw.get("bad_chunks", {}).items())},
+            "faults": faults, "unlogged": max(0, bad - len(faults)), "ms": [round(t, 4) for t in ms],
+            "GBps": [round(b / (t * 1e-3) / 1e9, 1) if t > 0 else 0.0 for b, t in zip(moved, ms)],
+            "healthy": bad == 0}
 
 
 def _sweep_error(p: HipProbe, rc: int, what: str) -> ProbeError:
