@@ -259,6 +259,7 @@ struct RelaxedI64 {
 
 struct GpuNames;
 const GpuNames& default_gpu_names();
+class Gang;
 
 // What a Pod asks for, derived once at parse time. Immutable and shared by
 // the copies of a Pod (the scheduler copies a Pod per assume and per bind
@@ -325,6 +326,10 @@ struct Pod {
   QoS qos = QoS::BestEffort;
   std::string pod_group;  // value of kPodGroupLabel ("" if none)
   uint64_t pg_key = 0;    // pg_key_of("ns/pod_group"), 0 if no group
+  // The lister's entry for (ns, pod_group) (scheduler/gang.h): set by the
+  // informer before it publishes the pod, carried along by copies. Null for
+  // a pod without a group or one parsed outside the lister.
+  std::shared_ptr<Gang> gang;
   std::vector<ContainerPort> host_ports;
   GpuAssignment gpu;      // decoded from annotations (mutable via cache only)
   GpuDemand gpu_demand;   // FlexGPU demand from container limits
@@ -401,9 +406,6 @@ struct PodGroup {
   std::string phase, occupied_by;
   int32_t scheduled = 0, running = 0, succeeded = 0, failed = 0;
   MicroTime schedule_start_time = 0;
-  // Set by the informer when a newer version replaces this object (or the
-  // PodGroup is deleted): per-thread lookup caches drop it then.
-  mutable RelaxedI64 superseded = 0;
   static std::shared_ptr<PodGroup> from_json(const Json& obj);
 };
 using PodGroupPtr = std::shared_ptr<PodGroup>;

@@ -131,7 +131,7 @@ class Coscheduling : public Plugin {
   MicroTime creation(const QueuedPodInfo& q) const {
     if (q.sort_key_cache != INT64_MIN) return q.sort_key_cache;
     if (!q.pod->pod_group.empty())
-      if (auto pg = h_.informers->pod_group_of(*q.pod)) {
+      if (auto pg = h_.informers->gang_pod_group(*q.pod)) {
         q.sort_key_cache = pg->meta.creation;
         return q.sort_key_cache;
       }
@@ -163,7 +163,7 @@ class Coscheduling : public Plugin {
   // ---- PreFilter (core.go:149-196) ----
   Status pre_filter(CycleState&, const Pod& p) override {
     if (p.pod_group.empty()) return {};
-    auto pg = h_.informers->pod_group_of(p);
+    auto pg = h_.informers->gang_pod_group(p);
     if (!pg) return {};
     if (denied_.has(p.pg_key)) {
       // A parked group that is now denied leaves the parking line (its
@@ -172,7 +172,7 @@ class Coscheduling : public Plugin {
       return Status::unresolvable("pod with pgName: " + p.pg_full_name() + " last failed in " +
                                   std::to_string(denied_ttl_us_ / 1000000) + "s, deny");
     }
-    size_t n = h_.informers->count_pods_in_group_of(p);
+    size_t n = h_.informers->gang_count(p);
     if (static_cast<int64_t>(n) < pg->min_member) {
       // A parked group that lost members (one deleted, the PodGroup kept)
       // cannot pass the gate until new ones arrive: it must not stay at the
@@ -240,7 +240,7 @@ class Coscheduling : public Plugin {
 
   // ---- PostFilter (coscheduling.go:140-176) ----
   std::pair<PostFilterResult, Status> post_filter(CycleState&, const Pod& p, const NodeStatusMap& m) override {
-    auto pg = p.pod_group.empty() ? nullptr : h_.informers->pod_group_of(p);
+    auto pg = p.pod_group.empty() ? nullptr : h_.informers->gang_pod_group(p);
     if (!pg) return {PostFilterResult{}, Status::unschedulable("can not find pod group")};
     // Deliberate deviation: when the cycle failed on this plugin's own
     // PreFilter (siblings not created yet, or group already denied) there is
@@ -300,6 +300,7 @@ class Coscheduling : public Plugin {
     member->meta.ns = p.ns();
     member->pod_group = p.pod_group;
     member->pg_key = p.pg_key;
+    member->gang = p.gang;
     arm_requeue(member, denied_ttl_us_ + 1000);
   }
 
@@ -318,7 +319,7 @@ class Coscheduling : public Plugin {
       }
       if (denied_.has(member->pg_key)) return;
       std::vector<PodPtr> pods;
-      for (auto& q : h_.informers->pods_in_group_of(*member))
+      for (auto& q : h_.informers->gang_members(*member))
         if (q->node_name.empty()) pods.push_back(std::move(q));
       if (!pods.empty()) h_.activate(pods);
     });
@@ -344,7 +345,7 @@ class Coscheduling : public Plugin {
   // ---- Permit (coscheduling.go:184-216, core.go:199-216) ----
   std::pair<Status, int64_t> permit(CycleState& s, const PodPtr& p, const std::string&) override {
     if (p->pod_group.empty()) return {Status(), 0};
-    auto pg = h_.informers->pod_group_of(*p);
+    auto pg = h_.informers->gang_pod_group(*p);
     if (!pg) return {Status::unschedulable("PodGroup not found"), 0};
     // The cache already holds this (assumed) pod, so `assigned` includes it:
     // equivalent to the reference's snapshot count + 1.
@@ -371,7 +372,7 @@ class Coscheduling : public Plugin {
   void activate_siblings(const Pod& p, CycleState& s) {
     auto* pta = s.read_as<PodsToActivate>(kPodsToActivateKey);
     if (!pta) return;
-    auto pods = h_.informers->pods_in_group_of(p);
+    auto pods = h_.informers->gang_members(p);
     std::lock_guard<std::mutex> g(pta->mu);
     for (const auto& q : pods)
       if (q->uid() != p.uid()) pta->pods.push_back(q);
@@ -381,7 +382,7 @@ class Coscheduling : public Plugin {
   Status reserve(CycleState&, const PodPtr&, const std::string&) override { return {}; }
   void unreserve(CycleState&, const PodPtr& p, const std::string&) override {
     if (p->pod_group.empty()) return;
-    auto pg = h_.informers->pod_group_of(*p);
+    auto pg = h_.informers->gang_pod_group(*p);
     if (!pg) {
       // The group was deleted while this member waited at Permit: nothing to
       // reject or deny, but the GPUs noted as owed to it must not stay owed
@@ -400,7 +401,7 @@ class Coscheduling : public Plugin {
   // ---- PostBind (core.go:220-252) ----
   void post_bind(CycleState&, const PodPtr& p, const std::string&) override {
     if (p->pod_group.empty()) return;
-    auto pg = h_.informers->pod_group_of(*p);
+    auto pg = h_.informers->gang_pod_group(*p);
     if (!pg) return;
     // Deliberate fix: the reference increments the lister's status.scheduled,
     // which is only written back on a phase change (core.go:220-252), so the
@@ -521,11 +522,12 @@ class Coscheduling : public Plugin {
       member.meta.ns = parked_[pos->second].ns;
       member.pod_group = parked_[pos->second].group;
       member.pg_key = key;
+      member.gang = parked_[pos->second].gang;
       was = true;
       unpark_locked(key, probe);
     }
     if (was && wake)
-      for (auto& q : h_.informers->pods_in_group_of(member))
+      for (auto& q : h_.informers->gang_members(member))
         if (q->node_name.empty()) probe.push_back(std::move(q));
     if (!probe.empty()) h_.activate(probe);
   }
@@ -667,6 +669,7 @@ class Coscheduling : public Plugin {
   }
   struct Parked {
     std::string ns, group;
+    std::shared_ptr<Gang> gang;  // the group's lister entry, as the parking member's pod held it
     GpuDemand::Kind kind = GpuDemand::None;
     int64_t need = 0;  // units for the group's remaining members
   };
@@ -820,6 +823,7 @@ class Coscheduling : public Plugin {
     Parked& pk = parked_[k];
     pk.ns = p.ns();
     pk.group = p.pod_group;
+    pk.gang = p.gang;
     pk.kind = kind;
     pk.need = need;
     parked_pos_[p.pg_key] = k;
@@ -857,7 +861,7 @@ class Coscheduling : public Plugin {
   void park_members(const Pod& p) {
     if (!h_.deactivate) return;
     std::vector<PodPtr> members;
-    for (auto& q : h_.informers->pods_in_group_of(p))
+    for (auto& q : h_.informers->gang_members(p))
       if (q->node_name.empty()) members.push_back(std::move(q));
     if (!members.empty()) h_.deactivate(members);
   }
@@ -904,14 +908,15 @@ class Coscheduling : public Plugin {
       member.meta.ns = it->second.ns;
       member.pod_group = it->second.group;
       member.pg_key = key;
-      auto pg = h_.informers->pod_group_of(member);
+      member.gang = it->second.gang;
+      auto pg = h_.informers->gang_pod_group(member);
       bool viable = pg && !denied_.has(key) &&
-                    static_cast<int64_t>(h_.informers->count_pods_in_group_of(member)) >= pg->min_member;
+                    static_cast<int64_t>(h_.informers->gang_count(member)) >= pg->min_member;
       // A member the cache does not hold (an assumed pod may not show its
       // node in the lister yet): activating one that is binding would lose
       // the probe until kProbeStaleUs.
       if (viable)
-        for (auto& q : h_.informers->pods_in_group_of(member))
+        for (auto& q : h_.informers->gang_members(member))
           if (q->node_name.empty() && !q->terminating() && !h_.cache->get_pod(q->uid())) {
             out.push_back(std::move(q));
             break;
@@ -929,7 +934,7 @@ class Coscheduling : public Plugin {
       parked_.erase(it);
       parked_n_.store(parked_.size(), std::memory_order_release);
       if (!viable) {
-        for (auto& q : h_.informers->pods_in_group_of(member))
+        for (auto& q : h_.informers->gang_members(member))
           if (q->node_name.empty()) wake_.push_back(std::move(q));
       }
     }

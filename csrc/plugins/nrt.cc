@@ -93,7 +93,7 @@ class TopologyMatch : public Plugin {
     if (colocation_ == GangPlacement::Mode::Off || !h_.gangs || !h_.snapshot || p.pod_group.empty() ||
         !GangPlacement::gang_demand(p.gpu_demand))
       return {};
-    auto pg = h_.informers->pod_group_of(p);
+    auto pg = h_.informers->gang_pod_group(p);
     if (!pg || pg->min_member <= 1) return {};
     GangPlacement::Plan plan = h_.gangs->plan(*h_.snapshot, p, pg->min_member, &s);
     if (!plan.gang) return {};
@@ -356,7 +356,7 @@ class TopologyMatch : public Plugin {
     ctx->hosts.clear();
     ctx->hosts_known = false;
     if (!p.pod_group.empty()) {
-      auto pg = h_.informers->pod_group_of(p);
+      auto pg = h_.informers->gang_pod_group(p);
       const GpuDemand& d = p.gpu_demand;
       if (pg && pg->min_member > 1 && d.amount > 0 && (d.kind == GpuDemand::Gpu || d.kind == GpuDemand::Xcd)) {
         ctx->gang = true;
@@ -526,7 +526,7 @@ class TopologyMatch : public Plugin {
     if (what != "gangPlan") return Plugin::debug_call(what, s, p, args);
     Json out = Json::object();
     out.set("mode", Json(GangPlacement::mode_name(colocation_)));
-    auto pg = p->pod_group.empty() ? nullptr : h_.informers->pod_group_of(*p);
+    auto pg = p->pod_group.empty() ? nullptr : h_.informers->gang_pod_group(*p);
     if (!pg || !h_.gangs || !h_.snapshot) {
       out.set("gang", Json(false));
       return out;

@@ -6,8 +6,7 @@
 namespace xsched {
 
 namespace {
-// "ns/group" in a per-thread buffer: gang bookkeeping runs per pod and a
-// lookup must not allocate a key string.
+// "ns/group" in a per-thread buffer (the name a denial is recorded under).
 const std::string& gang_key(const Pod& p) {
   thread_local std::string k;
   k.assign(p.ns());
@@ -17,38 +16,50 @@ const std::string& gang_key(const Pod& p) {
 }
 }  // namespace
 
-void Scheduler::note_gang_enqueue(const Pod& p, int64_t t) {
+// A gang's open record lives in its lister entry (scheduler/gang.h), reached
+// through the pod: these run once per pod on the informer, the scheduling
+// thread and every binder, under that gang's lock only. A pod whose entry is
+// retired, or that has none, finds the group's current entry by name.
+template <typename F>
+void Scheduler::with_gang_record(const Pod& p, bool open, GangRecord* done, F&& fn) {
   if (p.pod_group.empty()) return;
-  const std::string& key = gang_key(p);
-  std::lock_guard<std::mutex> g(stats_mu_);
-  auto it = gangs_.find(key);
-  if (it != gangs_.end()) return;
-  GangRecord& r = gangs_[key];
-  r.pg = key;
-  r.first_enqueue_us = t;
+  if (p.gang && p.gang->with_record(open, done, fn)) return;
+  if (GangPtr e = informers_->gang_by_name(p)) e->with_record(open, done, fn);
+}
+
+void Scheduler::note_gang_enqueue(const Pod& p, int64_t t) {
+  with_gang_record(p, true, nullptr, [&](const PodGroupPtr&, GangRecord* r, bool fresh) {
+    if (fresh) r->first_enqueue_us = t;
+    return false;
+  });
 }
 
 void Scheduler::note_gang_event(const Pod& p, bool bound) {
   if (p.pod_group.empty()) return;
-  auto pg = informers_->pod_group_of(p);
-  if (!pg) return;
-  int need = std::max(1, pg->min_member);
-  const std::string& key = gang_key(p);
-  std::lock_guard<std::mutex> g(stats_mu_);
-  auto it = gangs_.find(key);
-  if (it == gangs_.end()) return;
-  GangRecord& r = it->second;
-  r.size = need;
-  int64_t now = clock_->now_us();
-  if (!bound) {
+  GangRecord done;
+  bool finished = false;
+  int need = 0;
+  with_gang_record(p, false, &done, [&](const PodGroupPtr& pg, GangRecord* rp, bool) {
+    if (!pg || !rp) return false;
+    GangRecord& r = *rp;
+    need = std::max(1, pg->min_member);
+    r.size = need;
+    int64_t now = clock_->now_us();
+    if (!bound) {
+      if (r.admit_us == 0) r.admit_us = now;
+      return false;
+    }
+    const uint64_t nh = std::hash<std::string_view>{}(std::string_view(p.node_name));
+    if (std::find(r.nodes.begin(), r.nodes.end(), nh) == r.nodes.end()) r.nodes.push_back(nh);
+    if (++r.bound < need) return false;
+    r.bound_us = now;
     if (r.admit_us == 0) r.admit_us = now;
-    return;
-  }
-  const uint64_t nh = std::hash<std::string_view>{}(std::string_view(p.node_name));
-  if (std::find(r.nodes.begin(), r.nodes.end(), nh) == r.nodes.end()) r.nodes.push_back(nh);
-  if (++r.bound < need) return;
-  r.bound_us = now;
-  if (r.admit_us == 0) r.admit_us = now;
+    finished = true;
+    return true;
+  });
+  if (!finished) return;
+  // Once per gang: the finished record moves to the collected ones.
+  std::lock_guard<std::mutex> g(stats_mu_);
   // The per-size histogram, looked up once per size and metrics epoch.
   const uint64_t epoch = metrics_->epoch();
   if (gang_hist_epoch_ != epoch) {
@@ -57,17 +68,15 @@ void Scheduler::note_gang_event(const Pod& p, bool bound) {
   }
   Histogram*& hist = gang_hist_[need];
   if (!hist) hist = &metrics_->histogram("xsched_gang_admit_seconds", "size=\"" + std::to_string(need) + "\"");
-  hist->observe(static_cast<double>(r.bound_us - r.first_enqueue_us) / 1e6);
-  gang_done_.push_back(r);
-  gangs_.erase(it);
+  hist->observe(static_cast<double>(done.bound_us - done.first_enqueue_us) / 1e6);
+  gang_done_.push_back(std::move(done));
 }
 
 void Scheduler::note_gang_planned(const Pod& p, bool hostable) {
-  if (p.pod_group.empty()) return;
-  const std::string& key = gang_key(p);
-  std::lock_guard<std::mutex> g(stats_mu_);
-  auto it = gangs_.find(key);
-  if (it != gangs_.end()) it->second.hostable = hostable ? 1 : 0;
+  with_gang_record(p, false, nullptr, [&](const PodGroupPtr&, GangRecord* r, bool) {
+    if (r) r->hostable = hostable ? 1 : 0;
+    return false;
+  });
 }
 
 // Why was a gang denied? The cache's view (free SPX GPUs, those held by
@@ -84,7 +93,7 @@ void Scheduler::note_gang_denied(const Pod& p, const char* why) {
   d.pg = gang_key(p);
   d.why = why;
   d.t_us = clock_->now_us();
-  auto pg = informers_->pod_group_of(p);
+  auto pg = informers_->gang_pod_group(p);
   d.min_member = pg ? pg->min_member : 0;
   d.assigned = cache_->assigned_in_group(p.pg_key);
   d.waiting_at_permit = static_cast<int>(permit_waiting());

@@ -20,12 +20,17 @@
 
 #include "api/storage.h"
 #include "api/types.h"
+#include "scheduler/gang.h"
 
 namespace xsched {
 
 class Informers {
  public:
+  Informers() = default;
+  ~Informers();
   // ---- mutation (informer thread) ----
+  // Key strings and new gang entries are built before the lister lock is
+  // taken exclusive; objects that leave the lister are released after it.
   void upsert_pod(const PodPtr& p);
   void delete_pod(const Pod& p);
   void delete_pods(const std::vector<PodPtr>& ps);  // one lock for a run of deletions
@@ -37,6 +42,9 @@ class Informers {
   // nullptr (the caller parses the event's final state).
   std::vector<PodPtr> take_pods(const std::vector<std::string>& keys, const std::vector<std::string_view>& uids,
                                 const std::vector<std::string_view>& nodes);
+  // A group that already has an entry (any Modified event, e.g. the status
+  // events our own PostBind PATCH produces) swaps the object in under the
+  // entry's lock; the lister lock is held shared, for the map lookup only.
   void upsert_pod_group(const PodGroupPtr& pg);
   void delete_pod_group(const std::string& key);
   void upsert_elastic_quota(const ElasticQuotaPtr& eq);
@@ -66,10 +74,20 @@ class Informers {
   size_t count_pods_in_group_of(const Pod& p) const;
   std::vector<PodPtr> all_pods() const;
   PodGroupPtr pod_group(const std::string& ns, const std::string& name) const;
-  // The PodGroup named by p's group label, looked up by p.pg_key (no string
-  // building on the scheduling path).
+  // The PodGroup named by p's namespace and group label, by name under the
+  // lister lock (the scheduling path uses gang_pod_group).
   PodGroupPtr pod_group_of(const Pod& p) const;
   std::vector<PodGroupPtr> pod_groups() const;
+  // ---- p's gang through its entry (Pod::gang), without the lister lock ----
+  // The answers of pod_group_of / count_pods_in_group_of / pods_in_group_of.
+  // A pod with no entry, or whose entry is retired, gets exactly those (the
+  // locked lookup by name).
+  PodGroupPtr gang_pod_group(const Pod& p) const;
+  size_t gang_count(const Pod& p) const;
+  std::vector<PodPtr> gang_members(const Pod& p) const;
+  // The entry of p's (namespace, group) by name, under the lister lock
+  // (nullptr: the group has neither a PodGroup nor a lister pod).
+  GangPtr gang_by_name(const Pod& p) const;
   ElasticQuotaPtr elastic_quota_for_namespace(const std::string& ns) const;
   std::vector<ElasticQuotaPtr> elastic_quotas() const;
   NRTPtr nrt(const std::string& node) const;
@@ -97,9 +115,26 @@ class Informers {
   // PodGroup members by Pod::pg_key (64-bit hash of "ns/pg"). Readers still
   // compare namespace and group name, so a hash collision cannot mix groups.
   std::unordered_map<uint64_t, std::vector<PodPtr>> pods_by_group_;
-  std::unordered_map<std::string, PodGroupPtr> pgs_;
-  std::unordered_map<uint64_t, PodGroupPtr> pgs_by_key_;  // same objects, keyed by pg_key_of("ns/name")
+  // One entry per (namespace, group name) that has a PodGroup or a lister
+  // pod, keyed by the entry's own "ns/name" string. The map is written under
+  // mu_ exclusive; an entry's content under the entry's lock (mu_ first).
+  std::unordered_map<std::string_view, GangPtr> gangs_;
+  // What left the lister under the lock, to be released after it.
+  struct Released {
+    std::vector<PodPtr> pods;
+    std::vector<GangPtr> gangs;
+    std::vector<PodGroupPtr> pgs;
+  };
+  static Released& released();
+  struct Drain;
   void group_remove(const PodPtr& p);
+  GangPtr find_gang_locked(std::string_view ns, std::string_view name) const;
+  // The live entry for (ns, name), `hint` when it is that; created if missing.
+  GangPtr live_gang_locked(GangPtr hint, std::string_view ns, std::string_view name);
+  void gang_drop_member_locked(const PodPtr& p);
+  void gang_remove_locked(const PodPtr& p, Released& rel);
+  void retire_if_empty_locked(const GangPtr& g, Released& rel);
+  void unlist_locked(PodPtr& p, Released& rel);
   std::map<std::string, ElasticQuotaPtr> eqs_;  // ordered: "first listed wins"
   std::unordered_map<std::string, NRTPtr> nrts_;
   std::unordered_map<std::string, PDBPtr> pdbs_;

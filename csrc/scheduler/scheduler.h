@@ -99,20 +99,6 @@ struct SchedulerOptions {
   static SchedulerOptions from_json(const Json& j);
 };
 
-struct GangRecord {
-  std::string pg;  // ns/name
-  int size = 0;
-  int bound = 0;
-  int64_t first_enqueue_us = 0;
-  int64_t admit_us = 0;   // last member allowed at Permit
-  int64_t bound_us = 0;   // last member bound
-  // Placement: distinct nodes the bound members landed on (hashes of their
-  // names), and whether one node could take the whole gang when its first
-  // rank was planned (-1: not planned, e.g. no GPU ranks or co-location off).
-  std::vector<uint64_t> nodes;
-  int hostable = -1;
-};
-
 // One Coscheduling group denial with the GPU census at that moment
 // (Scheduler::note_gang_denied). store_* are -1 without an in-process store.
 struct GangDenial {
@@ -298,8 +284,11 @@ class Scheduler {
   void note_gang_event(const Pod& p, bool bound);
   void note_gang_planned(const Pod& p, bool hostable);
   void note_gang_denied(const Pod& p, const char* why);
-  mutable std::mutex stats_mu_;  // gang records and denials, condition memo
-  std::unordered_map<std::string, GangRecord> gangs_;  // open groups
+  // Runs fn on the open record of p's gang, which lives in the gang's lister
+  // entry (GangRecord, scheduler/gang.h) under that entry's lock.
+  template <typename F>
+  void with_gang_record(const Pod& p, bool open, GangRecord* done, F&& fn);
+  mutable std::mutex stats_mu_;  // finished gang records, denials, condition memo
   // Completed gangs until a caller collects them: a deque, so the push on a
   // binding thread (under stats_mu_) never moves the records already there
   // (a benchmark collects ~10^5 of them at once).

@@ -158,11 +158,10 @@ void Scheduler::handle_event(const WatchEvent& ev) {
           // hundreds of groups at once).
           const Json& md = o["metadata"];
           const std::string key = md["namespace"].as_string() + "/" + md["name"].as_string();
+          // A gang deleted before it was admitted leaves no open record (it
+          // goes with the entry's PodGroup): a later PodGroup of the same
+          // name starts its own timeline.
           informers_->delete_pod_group(key);
-          // A gang deleted before it was admitted leaves no open record: a
-          // later PodGroup of the same name starts its own timeline.
-          std::lock_guard<std::mutex> g(stats_mu_);
-          gangs_.erase(key);
         } else {
           informers_->upsert_pod_group(PodGroup::from_json(o));
         }
@@ -397,7 +396,7 @@ void Scheduler::apply_pod_update(const WatchEvent& ev, const PodPtr& np, PodPtr 
       // in unschedulableQ/backoffQ (targeted form of the Pod/Add cluster
       // event Coscheduling registers; O(group size), not O(queue)).
       if (!np->pod_group.empty()) {
-        std::vector<PodPtr> sib = informers_->pods_in_group_of(*np);
+        std::vector<PodPtr> sib = informers_->gang_members(*np);
         sib.erase(std::remove_if(sib.begin(), sib.end(),
                                  [&](const PodPtr& q) { return q->uid() == np->uid() || !q->node_name.empty(); }),
                   sib.end());

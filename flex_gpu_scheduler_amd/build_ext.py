@@ -11,6 +11,7 @@ Usage:
     python -m flex_gpu_scheduler_amd.build_ext --core     # C++ core only
     python -m flex_gpu_scheduler_amd.build_ext --tsan     # ThreadSanitizer stress driver
     python -m flex_gpu_scheduler_amd.build_ext --stress-count  # allocation-counting stress driver
+    python -m flex_gpu_scheduler_amd.build_ext --gang-tests    # native gang-entry tests (--gang-tests-tsan)
 """
 from __future__ import annotations
 
@@ -262,6 +263,28 @@ def build_tests(verbose: bool = True) -> Path:
     return out
 
 
+def build_gang_tests(verbose: bool = True, tsan: bool = False) -> Path:
+    """Native tests of the lister's gang entries (csrc/tests/gang_tests.cc).
+    The plain build shares build/core with the extension; `tsan` builds with
+    -fsanitize=thread and shares build/tsan with the stress driver (host only)."""
+    includes = [str(CSRC)]
+    extra = ["-fsanitize=thread", "-g", "-O1", "-include", str(CSRC / "tools" / "tsan_compat.h")] if tsan else []
+    objs = build_objects(core_sources() + [CSRC / "tests" / "gang_tests.cc"], BUILD / ("tsan" if tsan else "core"),
+                         extra, includes)
+    out = BUILD / ("xsched_gang_tests_tsan" if tsan else "xsched_gang_tests")
+    newest = max(o.stat().st_mtime for o in objs)
+    if out.exists() and out.stat().st_mtime >= newest:
+        return out
+    cmd = ["g++", *(["-fsanitize=thread"] if tsan else []), "-pthread", *[str(o) for o in objs], *LINK_LIBS,
+           "-o", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"gang tests link failed:\n{r.stderr[-8000:]}")
+    if verbose:
+        print(f"[build_ext] built {out.relative_to(ROOT)}")
+    return out
+
+
 def main(argv: list[str] | None = None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--core", action="store_true")
@@ -276,7 +299,12 @@ def main(argv: list[str] | None = None) -> int:
     ap.add_argument("--stress-count-g", action="store_true", help="the same with line tables (call stacks)")
     ap.add_argument("--tests", action="store_true")
     ap.add_argument("--core-g", action="store_true", help="the extension with -g into dbg/ (sampling runs)")
+    ap.add_argument("--gang-tests", action="store_true", help="native tests of the lister's gang entries")
+    ap.add_argument("--gang-tests-tsan", action="store_true", help="the same under ThreadSanitizer (host only)")
     a = ap.parse_args(argv)
+    if a.gang_tests or a.gang_tests_tsan:
+        build_gang_tests(tsan=a.gang_tests_tsan)
+        return 0
     if a.core_g:
         build_core_debuginfo()
         return 0

@@ -22,6 +22,12 @@ run() {  # name dir waves
     echo "$s  $1  rc=$rc  reports=$n  $(tail -1 "$log")" | tee -a "$out"
   done
 }
+# The lister's gang entries: random lister sequences and readers on several
+# threads against a changing lister (csrc/tests/gang_tests.cc), as a
+# stand-alone ThreadSanitizer program.
+python -m flex_gpu_scheduler_amd.build_ext --gang-tests-tsan > /dev/null || exit 1
+timeout -k 10 600 build/xsched_gang_tests_tsan > /tmp/san_tsan_gang_tests.log 2>&1
+echo "tsan  gang_tests  rc=$?  reports=$(grep -c "WARNING: ThreadSanitizer" /tmp/san_tsan_gang_tests.log)  $(tail -1 /tmp/san_tsan_gang_tests.log)" | tee -a "$out"
 run bench64 /tmp/san_bench 3
 # The 1,024-node headline waves: gang window, Filter scan memo, column
 # equivalence table, snapshot arrays (one wave of 12k pods).
