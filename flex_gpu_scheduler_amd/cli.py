@@ -343,7 +343,8 @@ def health_fn_args(args) -> dict:
     """hip_health_fn's keywords from the node-agent flags.
     --health-matrix-sweep: absent -> None, bare -> "all", else a comma list.
     --health-hbm-sweep: absent -> no hbm keys, bare -> all free HBM less the
-    reserve (hbm_gib None), else that many GiB."""
+    reserve (hbm_gib None), else that many GiB.
+    --health-register-sweep: absent -> no regfile key."""
     m = args.health_matrix_sweep
     formats = None if m in (None, "all") else [f.strip() for f in m.split(",") if f.strip()]
     kw = {"sweep": args.health_sweep, "sweep_period_s": args.health_sweep_period, "matrix": m is not None,
@@ -351,6 +352,8 @@ def health_fn_args(args) -> dict:
     h = getattr(args, "health_hbm_sweep", None)
     if h is not None:
         kw.update(hbm=True, hbm_gib=None if h == "all" else float(h))
+    if getattr(args, "health_register_sweep", False):
+        kw.update(regfile=True)
     return kw
 
 
@@ -369,7 +372,7 @@ def cmd_node_agent(args) -> int:
                       reserved_memory_gib=args.reserved_memory_gib,
                       health_fn=(hip_health_fn(**health_fn_args(args))
                                  if args.health_probe or args.health_sweep or args.health_matrix_sweep is not None
-                                 or args.health_hbm_sweep is not None else None),
+                                 or args.health_hbm_sweep is not None or args.health_register_sweep else None),
                       bandwidth_fn=hip_bandwidth_fn() if args.bandwidth_probe else None,
                       kubelet_managed=args.kubelet_managed).start()
     if args.device_plugin:
@@ -539,6 +542,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "whole GPU and is published as hbmFaults. The sweep holds the memory it tests, so a tenant's "
                         "allocation can fail while it runs: cap it with GIB and space it with --health-sweep-period. "
                         "Implies --health-probe; independent of the other sweeps")
+    p.add_argument("--health-register-sweep", action="store_true",
+                   help="health probe plus the register-file sweep: all 512 VGPR/AGPR entries of every lane of every "
+                        "SIMD written and read back in both polarities on every CU; a bad XCD is fenced like "
+                        "--health-sweep's and its register files are published as registerFaults. Implies "
+                        "--health-probe; independent of the other sweeps")
     p.add_argument("--health-sweep-period", type=float, default=600.0, metavar="SECONDS",
                    help="reuse a sweep's verdict this long before sweeping the GPU again")
     p.add_argument("--bandwidth-probe", action="store_true",

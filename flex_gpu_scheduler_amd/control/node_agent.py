@@ -15,7 +15,8 @@ exporter + metrics-server:
     the node when none are healthy; a verdict that names bad XCDs (GpuHealth,
     e.g. from the CU sweep) fences only the compute partitions holding them
     on a DPX/QPX/CPX GPU (`xcdFaults` in the topology annotation), and the
-    matrix formats such an XCD gets wrong are published as `matrixFaults`;
+    matrix formats such an XCD gets wrong are published as `matrixFaults`
+    and the register files it reads back wrong as `registerFaults`;
     a verdict that carries an HBM fault (the HBM sweep) withholds the whole
     GPU, partitioned or not, and is published as `hbmFaults`;
   * samples load (gpu/telemetry.py) and publishes its WatcherMetrics document
@@ -100,6 +101,9 @@ class NodeAgent:
         # GPU index -> {XCD id: matrix formats it mis-computes}, from
         # GpuHealth.detail["matrixFaults"] (the matrix-format sweep).
         self.matrix_faults: dict[int, dict[int, list[str]]] = {}
+        # GPU index -> {XCD id: {"files", "cells", "flipMask", "simds"}}, from
+        # GpuHealth.detail["registerFaults"] (the register-file sweep).
+        self.register_faults: dict[int, dict[int, dict]] = {}
         # GPU index -> what the HBM sweep found wrong, from
         # GpuHealth.detail["hbmFaults"]; such a GPU is withheld as a whole.
         self.hbm_faults: dict[int, dict] = {}
@@ -122,20 +126,21 @@ class NodeAgent:
         return self._probe_health(host)[:2]
 
     def _probe_health(self, host: HostInfo) -> tuple[set[int], dict[int, set[int]], dict[int, dict[int, list[str]]],
-                                                     dict[int, dict]]:
-        """probe_health plus the matrix formats each bad XCD got wrong and the
-        HBM faults per GPU.
+                                                     dict[int, dict], dict[int, dict[int, dict]]]:
+        """probe_health plus the matrix formats each bad XCD got wrong, the
+        HBM faults per GPU and what the register-file sweep found per bad XCD.
 
         An HBM fault (detail["hbmFaults"]) withholds the whole GPU, partitioned
         or not, and even when the same verdict names bad XCDs: the sweep knows
         a fault by its virtual address, which cannot be tied to the HBM slice
         of one compute partition, so there is no partial fence for memory."""
         if self.health_fn is None:
-            return set(), {}, {}, {}
+            return set(), {}, {}, {}, {}
         bad: set[int] = set()
         xcds: dict[int, set[int]] = {}
         formats: dict[int, dict[int, list[str]]] = {}
         hbm: dict[int, dict] = {}
+        registers: dict[int, dict[int, dict]] = {}
         # HIP ordinals follow the KFD node order of the GPUs this process can
         # open; GPUs whose KFD node is hidden (other containers' devices) are
         # not probed. With no KFD info at all (fake hosts) use the index.
@@ -150,6 +155,9 @@ class NodeAgent:
                         formats[g.index] = mf
                     if r.detail.get("hbmFaults"):
                         hbm[g.index] = dict(r.detail["hbmFaults"])
+                    rf = {int(x): dict(f) for x, f in (r.detail.get("registerFaults") or {}).items() if f}
+                    if rf:
+                        registers[g.index] = rf
                 if isinstance(r, GpuHealth) and r.bad_xcds:
                     xcds[g.index] = set(r.bad_xcds)
                     if g.partitions == 1 or g.index in hbm:
@@ -161,7 +169,7 @@ class NodeAgent:
             except Exception as e:  # noqa: BLE001
                 log.warning("health probe GPU %d failed: %s", g.index, e)
                 bad.add(g.index)
-        return bad, xcds, formats, hbm
+        return bad, xcds, formats, hbm, registers
 
     @staticmethod
     def _fenced(gpus, xcd_faults) -> dict[int, tuple[int, int]]:
@@ -198,7 +206,8 @@ class NodeAgent:
     def build_node(self, host: HostInfo, unhealthy: set[int] = frozenset(),
                    xcd_faults: dict[int, set[int]] | None = None,
                    matrix_faults: dict[int, dict[int, list[str]]] | None = None,
-                   hbm_faults: dict[int, dict] | None = None) -> dict:
+                   hbm_faults: dict[int, dict] | None = None,
+                   register_faults: dict[int, dict[int, dict]] | None = None) -> dict:
         healthy = [g for g in host.gpus if g.index not in unhealthy]
         infos = [g.to_gpu_info() for g in healthy]
         mem_kib = max(0, host.memory_bytes // 1024 - self.reserved_memory_gib * (1 << 20))
@@ -232,6 +241,13 @@ class NodeAgent:
         formats = {i: per for i, per in formats.items() if per}
         if formats:
             topo["matrixFaults"] = formats
+        # Which register files each faulty XCD reads back wrong: informational,
+        # as matrixFaults is.
+        regs = {str(i): {str(x): dict(f) for x, f in sorted(per.items()) if f}
+                for i, per in sorted((register_faults or {}).items())}
+        regs = {i: per for i, per in regs.items() if per}
+        if regs:
+            topo["registerFaults"] = regs
         # What the HBM sweep found on a GPU (which is withheld as a whole).
         hbm = {str(i): dict(f) for i, f in sorted((hbm_faults or {}).items()) if f}
         if hbm:
@@ -327,14 +343,15 @@ class NodeAgent:
 
     def sync(self) -> HostInfo:
         host = self.host_fn()
-        self.unhealthy, self.unhealthy_xcds, self.matrix_faults, self.hbm_faults = self._probe_health(host)
+        (self.unhealthy, self.unhealthy_xcds, self.matrix_faults, self.hbm_faults,
+         self.register_faults) = self._probe_health(host)
         self.measure_bandwidth(host)
         for dp in self.device_plugins:
             dp.host = host
             dp.set_unhealthy(self.unhealthy)
             dp.set_unhealthy_xcds(self.unhealthy_xcds)
         self._upsert("nodes", self.build_node(host, self.unhealthy, self.unhealthy_xcds, self.matrix_faults,
-                                              self.hbm_faults), keep_spec=True)
+                                              self.hbm_faults, self.register_faults), keep_spec=True)
         self._upsert("noderesourcetopologies", self.build_nrt(host, self.unhealthy, self.unhealthy_xcds),
                      keep_spec=False)
         self.host = host
@@ -375,10 +392,10 @@ class NodeAgent:
 
     def _heartbeat_and_resync(self) -> None:
         host = self.host_fn()
-        unhealthy, xcds, formats, hbm = self._probe_health(host)
+        unhealthy, xcds, formats, hbm, registers = self._probe_health(host)
         changed = (self.host is None or [g.to_gpu_info() for g in host.gpus] != [g.to_gpu_info() for g in self.host.gpus]
                    or unhealthy != self.unhealthy or xcds != self.unhealthy_xcds or formats != self.matrix_faults
-                   or hbm != self.hbm_faults)
+                   or hbm != self.hbm_faults or registers != self.register_faults)
         if changed:
             self.sync()
         else:
@@ -393,7 +410,8 @@ class NodeAgent:
 def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args: dict | None = None,
                   matrix: bool = False, matrix_formats: list | None = None,
                   matrix_args: dict | None = None, hbm: bool = False, hbm_gib: float | None = None,
-                  hbm_args: dict | None = None) -> Callable[[int], "bool | GpuHealth"]:
+                  hbm_args: dict | None = None, regfile: bool = False,
+                  regfile_args: dict | None = None) -> Callable[[int], "bool | GpuHealth"]:
     """Health callback backed by the HIP probes (HBM pattern + checksum and an
     MFMA tile check per GPU).
 
@@ -401,14 +419,17 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
     keywords), which checks MFMA, VALU and LDS on every CU. `matrix`: also run
     the matrix-format sweep (HipProbe.matrix_sweep over `matrix_formats`, None
     for all; `matrix_args` are its other keywords), which runs f16, f32, f64,
-    fp8, bf8, i8 and the block-scaled MX formats on every CU. The callback
-    runs on every heartbeat, so the sweeps' verdict is reused for
+    fp8, bf8, i8 and the block-scaled MX formats on every CU. `regfile`: also
+    run the register-file sweep (HipProbe.regfile_sweep, `regfile_args` are its
+    keywords), which writes and reads back every VGPR and AGPR of every SIMD.
+    The callback runs on every heartbeat, so the sweeps' verdict is reused for
     `sweep_period_s`. On a device that shows all 8 XCDs the verdict is a
-    GpuHealth naming the bad physical XCDs of either sweep, with
-    detail["matrixFaults"] = {xcd: [format, ...]}; a partition device numbers
-    its XCDs logically, so there a failed sweep fails the device as a whole (a
-    plain bool). CUs a sweep could not reach are logged, never counted as
-    failed.
+    GpuHealth naming the bad physical XCDs of any of the three sweeps, with
+    detail["matrixFaults"] = {xcd: [format, ...]} and detail["registerFaults"]
+    = {xcd: {"files": [...], "cells": n, "flipMask": "0x...", "simds": n}}; a
+    partition device numbers its XCDs logically, so there a failed sweep fails
+    the device as a whole (a plain bool). CUs a sweep could not reach are
+    logged, never counted as failed.
 
     `hbm`: also run the HBM sweep (HipProbe.hbm_sweep over `hbm_gib` GiB, None
     for all free HBM less its reserve; `hbm_args` are its other keywords) under
@@ -449,6 +470,19 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
             bad |= set(m["bad_xcds"])
             detail["matrixSweep"] = m
             detail["matrixFaults"] = faults
+        if regfile:
+            g = p.regfile_sweep(dev, **(regfile_args or {}))["summary"]
+            reg_faults = {int(x): {"files": list(v["failed_files"]), "cells": int(v["bad_cells"]),
+                                   "flipMask": v["flip_mask"],
+                                   "simds": sum(len(sm) for sm in v["bad_simds"].values())}
+                          for x, v in g["xcds"].items() if v["failed_files"]}
+            log.log(logging.WARNING if g["bad_xcds"] else logging.INFO,
+                    "register sweep GPU %d: %d CUs on %d XCDs in %.2f ms (%d launch(es)), covered=%s uncovered=%s "
+                    "faults=%s", dev, g["cus_seen"], len(g["xcds"]), g["ms"], g["rounds"], g["covered"],
+                    {x: n for x, n in g["uncovered"].items() if n}, reg_faults)
+            bad |= set(g["bad_xcds"])
+            detail["registerSweep"] = g
+            detail["registerFaults"] = reg_faults
         hbm_faults: dict = {}
         if hbm:
             h = None
@@ -485,7 +519,7 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
         # HBM pattern/checksum and an exact-integer MFMA tile: a GPU whose matrix
         # cores mis-compute is withheld even if its memory checks out.
         ok = bool(p.health(dev)["healthy"]) and bool(p.mfma_check(dev)["healthy"])
-        if not (sweep or matrix or hbm) or not ok:
+        if not (sweep or matrix or hbm or regfile) or not ok:
             return ok
         return sweep_verdict(dev)
 

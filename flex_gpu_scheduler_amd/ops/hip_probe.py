@@ -1,6 +1,6 @@
 """ctypes front-end for the HIP/CDNA4 device probes (csrc/hip/hbm_probe.hip,
 csrc/hip/mfma_probe.hip, csrc/hip/cu_sweep.hip, csrc/hip/matrix_sweep.hip,
-csrc/hip/hbm_sweep.hip).
+csrc/hip/hbm_sweep.hip, csrc/hip/regfile_sweep.hip).
 
 The probes are what the node agent runs before advertising an MI355X as
 schedulable: device properties, HBM streaming bandwidth (optionally with a
@@ -12,7 +12,8 @@ names the XCD of a CU that mis-computes, and a sweep that runs every matrix
 format (f16, f32, f64, fp8, bf8, i8 and the block-scaled MX fp8/fp6/fp4) on
 every CU and names the formats a CU gets wrong, and a sweep of all free HBM
 with an address-keyed pattern in both polarities that names the vectors and
-bits that read back wrong.
+bits that read back wrong, and a sweep of every SIMD's whole VGPR/AGPR file
+that names the register file, the cells and the SIMDs that read back wrong.
 """
 from __future__ import annotations
 
@@ -62,6 +63,15 @@ SWEEP_BAD_ARGS = -1000
 # k_matrix_sweep (csrc/hip/matrix_sweep.hip): one 64-byte record per workgroup,
 # {xcd, cu, simd_mask, fail, one digest per format, 0}.
 MATRIX_RECORD_WORDS = 16
+
+# k_regfile_sweep (csrc/hip/regfile_sweep.hip): one 64-byte record per
+# workgroup, {xcd, cu, simd_mask, fail, bad_vgpr, bad_agpr, first, flip, digest,
+# bad_simds, 0 x 6}.
+REGFILE_RECORD_WORDS = 16
+REGFILE_SEED = 0x5BD1E995
+REGFILE_FILES = ["vgpr", "agpr"]  # fail bit order
+REGFILE_CELLS = 512  # per lane: v0..v255 then a0..a255
+REGFILE_NO_CELL = 0xFFFF  # `first` of a record without a mis-compare
 
 # k_hbm_fill / k_hbm_verify (csrc/hip/hbm_sweep.hip)
 HBM_SWEEP_SEED = 0x5EED1E55
@@ -186,6 +196,12 @@ class HipProbe:
         L.xs_matrix_sweep.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_int,
                                       ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int),
                                       ctypes.POINTER(ctypes.c_double)]
+        L.xs_regfile_sweep_last_error.restype = ctypes.c_char_p
+        L.xs_regfile_sweep_expected.argtypes = [ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
+        L.xs_regfile_sweep_info.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        L.xs_regfile_sweep.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                       ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]
         L.xs_hbm_sweep_last_error.restype = ctypes.c_char_p
         L.xs_hbm_sweep_pattern.argtypes = [ctypes.c_uint64, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int,
                                            ctypes.c_void_p]
@@ -634,6 +650,82 @@ class HipProbe:
                        formats=[f for i, f in enumerate(names) if mask >> i & 1])
         return {"records": records, "summary": summary}
 
+    # -------------------------------------------------- register-file sweep
+    def regfile_sweep_expected(self, seed: int = REGFILE_SEED) -> int:
+        """The workgroup digest a healthy CU leaves, computed on the host."""
+        out = ctypes.c_uint32()
+        rc = self.lib.xs_regfile_sweep_expected(seed, ctypes.byref(out))
+        if rc != 0:
+            raise _regfile_error(self, rc, "regfile_sweep_expected")
+        return int(out.value)
+
+    def regfile_sweep_info(self, dev: int = 0) -> dict:
+        """What the runtime reports for k_regfile_sweep: `num_regs`,
+        `scratch_bytes` per lane and `blocks_per_cu` (256-thread workgroups
+        that fit on a CU at once)."""
+        out = (ctypes.c_int * 3)()
+        rc = self.lib.xs_regfile_sweep_info(dev, out)
+        if rc != 0:
+            raise _regfile_error(self, rc, "regfile_sweep_info")
+        return {"num_regs": out[0], "scratch_bytes": out[1], "blocks_per_cu": out[2]}
+
+    def regfile_sweep(self, dev: int = 0, blocks: int = 0, seed: int = REGFILE_SEED, inject: tuple | None = None,
+                      poison: tuple | None = None, max_rounds: int = 4) -> dict:
+        """k_regfile_sweep: all 512 VGPR/AGPR entries of every lane of every
+        SIMD written and read back in both polarities on every CU a workgroup
+        lands on. `inject` = (xcd, cu key or None for every CU of that XCD,
+        cell 0..511, bit 0..31): those workgroups flip that bit of what they
+        read back from that cell in pass 0 (tests the comparator on a healthy
+        GPU). `poison` = (xcd, cu key or None, VGPR 0..255): those workgroups
+        complement that physical register through the index mode between pass
+        0's writes and reads (tests that the read-back names the register it
+        reads). Given together they select the same workgroups. `blocks` 0:
+        4 per CU.
+
+        Relaunched while some CU has not been seen, as cu_sweep does. Returns
+        {"records": [...], "summary": summarize_regfile_sweep(...) plus rounds,
+        ms, blocks, seed}."""
+        cus = int(self.props(dev)["computeUnits"])
+        n_blocks = blocks if blocks != 0 else 4 * cus
+        ix, ic, ir, ib, pr = -1, -1, -1, 0, -1
+        if inject is not None:
+            ix, ic, ir, ib = int(inject[0]), -1 if inject[1] is None else int(inject[1]), int(inject[2]), int(inject[3])
+        if poison is not None:
+            px, pc, pr = int(poison[0]), -1 if poison[1] is None else int(poison[1]), int(poison[2])
+            if inject is not None and (px, pc) != (ix, ic):
+                raise ValueError("regfile_sweep: inject and poison select different workgroups")
+            ix, ic = px, pc
+        expected = None
+        records: list[dict] = []
+        total_ms, rounds = 0.0, 0
+        summary: dict = {}
+        for _ in range(max(1, max_rounds if n_blocks >= cus else 1)):
+            buf = (ctypes.c_uint32 * (REGFILE_RECORD_WORDS * max(1, n_blocks)))()
+            n, ms = ctypes.c_int(), ctypes.c_double()
+            rc = self.lib.xs_regfile_sweep(dev, n_blocks, seed, ix, ic, ir, ib, pr, buf, ctypes.byref(n),
+                                           ctypes.byref(ms))
+            if rc != 0:
+                raise _regfile_error(self, rc, "regfile_sweep")
+            if expected is None:
+                expected = self.regfile_sweep_expected(seed)
+            rounds += 1
+            total_ms += ms.value
+            for i in range(n.value):
+                w = buf[REGFILE_RECORD_WORDS * i:REGFILE_RECORD_WORDS * (i + 1)]
+                rec = {"xcd": w[0], "cu": w[1], "simd_mask": w[2], "fail": w[3], "bad_vgpr": w[4], "bad_agpr": w[5],
+                       "first": w[6], "flip": w[7], "digest": w[8], "bad_simds": w[9]}
+                # A digest that differs from the host's with no cell named is a
+                # failure of both files even if the device-side comparator
+                # (on the same CU) passed it.
+                if not rec["fail"] and rec["digest"] != expected:
+                    rec["fail"] = 3
+                records.append(rec)
+            summary = summarize_regfile_sweep(records, cus)
+            if summary["covered"]:
+                break
+        summary.update(rounds=rounds, ms=total_ms, blocks=n_blocks, seed=seed)
+        return {"records": records, "summary": summary}
+
     # ------------------------------------------------------------ HBM sweep
     def hbm_sweep_pattern(self, first_vec: int, nvec: int, seed: int = HBM_SWEEP_SEED, inverted: bool = False):
         """The sweep's pattern for 16-byte vectors [first_vec, first_vec +
@@ -812,6 +904,51 @@ def summarize_matrix_sweep(records: list[dict], compute_units: int, formats: lis
         v["failed_formats"] = names(v["fail_bits"])
         every |= v["fail_bits"]
     s["failed_formats"] = names(every)
+    return s
+
+
+def _regfile_error(p: HipProbe, rc: int, what: str) -> ProbeError:
+    detail = "bad arguments" if rc == BAD_ARGS else p.lib.xs_regfile_sweep_last_error().decode(errors="replace")
+    e = ProbeError(f"{what} failed ({rc}): {detail}")
+    e.rc = rc
+    return e
+
+
+def summarize_regfile_sweep(records: list[dict], compute_units: int) -> dict:
+    """summarize_sweep over k_regfile_sweep records, whose fail bits are
+    register files (bit 0 VGPR, bit 1 AGPR). Adds per XCD and overall:
+    `failed_files`, `bad_cells` (mis-compared (cell, lane) pairs; of the worst
+    record of a CU that ran more than one workgroup) and `flip_mask` (hex, the
+    bits that flipped); per XCD also `bad_simds` = {cu: [SIMD id, ...]}."""
+    s = summarize_sweep(records, compute_units)
+
+    def files(bits: int) -> list[str]:
+        return [f for b, f in enumerate(REGFILE_FILES) if bits >> b & 1]
+
+    cells: dict[tuple[int, int], int] = {}
+    flips: dict[int, int] = {}
+    simds: dict[int, dict[int, int]] = {}
+    for r in records:
+        if not int(r.get("fail", 0)):
+            continue
+        x, c = int(r["xcd"]), int(r["cu"])
+        cells[x, c] = max(cells.get((x, c), 0), int(r.get("bad_vgpr", 0)) + int(r.get("bad_agpr", 0)))
+        flips[x] = flips.get(x, 0) | int(r.get("flip", 0))
+        per = simds.setdefault(x, {})
+        per[c] = per.get(c, 0) | int(r.get("bad_simds", 0))
+    every = 0
+    for x, v in s["xcds"].items():
+        v["failed_files"] = files(v["fail_bits"])
+        v["bad_cells"] = sum(n for (xx, _), n in cells.items() if xx == x)
+        v["flip_mask"] = f"0x{flips.get(x, 0):08x}"
+        v["bad_simds"] = {c: [i for i in range(4) if m >> i & 1] for c, m in sorted(simds.get(x, {}).items())}
+        every |= v["fail_bits"]
+    s["failed_files"] = files(every)
+    s["bad_cells"] = sum(cells.values())
+    flip = 0
+    for f in flips.values():
+        flip |= f
+    s["flip_mask"] = f"0x{flip:08x}"
     return s
 
 
