@@ -37,7 +37,10 @@
 //                       XCDs, CPX -> 1).
 //  * xs_health_check    deterministic integer checksum over a pattern buffer
 //                       (catches a dead/ECC-faulting device before the node is
-//                       advertised schedulable).
+//                       advertised schedulable): allocate, xs_pattern_op,
+//                       xs_health_verify; the two halves also run on a
+//                       caller-owned buffer, so the GPU tests hold the pattern
+//                       to numpy and see the verdict fail on a flipped bit.
 //
 // Exposed as a C ABI (loaded with ctypes from flex_gpu_scheduler_amd/ops).
 #include <hip/hip_runtime.h>
@@ -862,27 +865,48 @@ int xs_xcd_census(int dev, int blocks, int* xcd_hist8, int* distinct_cus) {
   return distinct;
 }
 
-// Writes a pattern over `bytes` and verifies its checksum on the host.
-// Returns 0 when healthy, 1 on mismatch, <0 on HIP errors.
-int xs_health_check(int dev, size_t bytes, unsigned long long* device_sum, unsigned long long* host_sum) {
+int xs_checksum_op(int dev, const void* buf, size_t bytes, unsigned long long* out_sum);
+
+// k_pattern, launched as xs_health_check launches it, over a caller-owned
+// device buffer of `bytes` (a multiple of 4, 4-byte aligned): word i <-
+// uint32(i * 2654435761) ^ 0xa5a5a5a5.
+int xs_pattern_op(int dev, void* buf, size_t bytes) {
   XS_CHECK(hipSetDevice(dev));
-  size_t n = bytes / sizeof(uint32_t);
-  if (n == 0) n = 1 << 20;
-  DevMem buf, out;
-  XS_CHECK(hipMalloc(&buf.p, n * sizeof(uint32_t)));
-  XS_CHECK(hipMalloc(&out.p, sizeof(unsigned long long)));
-  XS_CHECK(hipMemset(out.p, 0, sizeof(unsigned long long)));
-  int grid = cu_count(dev) * 8;
-  k_pattern<<<grid, kBlock>>>(buf.as<uint32_t>(), n);
-  k_checksum<<<grid, kBlock>>>(buf.as<uint32_t>(), n, out.as<unsigned long long>());
+  if (bytes == 0 || bytes % sizeof(uint32_t) != 0) return -1000;
+  if (!buf || (reinterpret_cast<uintptr_t>(buf) & (sizeof(uint32_t) - 1))) return -1001;
+  k_pattern<<<cu_count(dev) * 8, kBlock>>>(static_cast<uint32_t*>(buf), bytes / sizeof(uint32_t));
   XS_CHECK(hipGetLastError());
+  XS_CHECK(hipDeviceSynchronize());
+  return 0;
+}
+
+// The health check's verdict over a caller-owned device buffer (as
+// xs_pattern_op): k_checksum's sum of its words against the host's sum of the
+// pattern for that many words. Returns 0 when they agree, 1 when they differ,
+// <0 on bad arguments or HIP errors.
+int xs_health_verify(int dev, const void* buf, size_t bytes, unsigned long long* device_sum,
+                     unsigned long long* host_sum) {
   unsigned long long d = 0;
-  XS_CHECK(hipMemcpy(&d, out.p, sizeof d, hipMemcpyDeviceToHost));
+  if (int rc = xs_checksum_op(dev, buf, bytes, &d)) return rc;
+  const size_t n = bytes / sizeof(uint32_t);
   unsigned long long h = 0;
   for (size_t i = 0; i < n; ++i) h += static_cast<uint32_t>(static_cast<uint32_t>(i * 2654435761u) ^ 0xa5a5a5a5u);
   if (device_sum) *device_sum = d;
   if (host_sum) *host_sum = h;
   return d == h ? 0 : 1;
+}
+
+// Writes a pattern over `bytes` and verifies its checksum on the host:
+// allocate -> xs_pattern_op -> xs_health_verify. Returns 0 when healthy, 1 on
+// mismatch, <0 on HIP errors.
+int xs_health_check(int dev, size_t bytes, unsigned long long* device_sum, unsigned long long* host_sum) {
+  XS_CHECK(hipSetDevice(dev));
+  size_t n = bytes / sizeof(uint32_t);
+  if (n == 0) n = 1 << 20;
+  DevMem buf;
+  XS_CHECK(hipMalloc(&buf.p, n * sizeof(uint32_t)));
+  if (int rc = xs_pattern_op(dev, buf.p, n * sizeof(uint32_t))) return rc;
+  return xs_health_verify(dev, buf.p, n * sizeof(uint32_t), device_sum, host_sum);
 }
 
 // k_checksum, launched as xs_health_check launches it, over a caller-owned

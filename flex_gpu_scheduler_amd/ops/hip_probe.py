@@ -34,6 +34,12 @@ BAD_ARGS = -1000
 # k_pinned: a selected XCD received no workgroup, so its slice of the buffer
 # was never processed (xs_pinned_op_g, xs_hbm_bandwidth_xcd_d).
 PINNED_UNDRAINED = -1002
+# k_mfma_peak: a selected XCD ran no workgroup, so the rate would be that of
+# fewer XCDs than asked for (xs_mfma_peak).
+MFMA_IDLE_XCD = -1002
+MFMA_PEAK_BLOCK = 256  # threads per k_mfma_peak workgroup: 4 waves
+MFMA_PEAK_ACC = 4  # independent 32x32 accumulators per wave
+MFMA_DID_NOT_RUN = 1 << 31  # xs_mfma_peak_op: flag of a workgroup that exited
 
 
 @dataclass
@@ -178,7 +184,17 @@ class HipProbe:
         L.xs_mfma_check.argtypes = [ctypes.c_int, ctypes.c_int]
         L.xs_mfma_peak.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
                                    ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
-                                   ctypes.POINTER(ctypes.c_int)]
+                                   ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint),
+                                   ctypes.POINTER(ctypes.c_double)]
+        L.xs_mfma_max_k.restype = ctypes.c_int
+        L.xs_mfma_tile_op.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        L.xs_mfma_inputs.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+        L.xs_mfma_compare.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        L.xs_mfma_peak_op.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint)]
+        L.xs_pattern_op.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t]
+        L.xs_health_verify.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
+                                       ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong)]
         L.xs_cu_sweep_last_error.restype = ctypes.c_char_p
         L.xs_cu_sweep_max_lds.argtypes = [ctypes.c_int]
         L.xs_cu_sweep_max_lds.restype = ctypes.c_size_t
@@ -450,20 +466,116 @@ class HipProbe:
         return {"healthy": rc == 0, "device_sum": d.value, "host_sum": h.value}
 
 
+    def pattern(self, buf) -> None:
+        """k_pattern (the health check's fill) over a device tensor: 32-bit
+        word i <- uint32(i * 2654435761) ^ 0xa5a5a5a5."""
+        p, n = self._dev_buf(buf, "buf", granular=False)
+        rc = self.lib.xs_pattern_op(buf.device.index or 0, p, n)
+        if rc != 0:
+            raise self._err(rc, "pattern_op")
+
+    def health_verify(self, buf) -> dict:
+        """The health check's verdict over a device tensor: k_checksum's sum
+        of its words against the host's sum of the pattern for that size."""
+        p, n = self._dev_buf(buf, "buf", granular=False)
+        d, h = ctypes.c_ulonglong(), ctypes.c_ulonglong()
+        rc = self.lib.xs_health_verify(buf.device.index or 0, p, n, ctypes.byref(d), ctypes.byref(h))
+        if rc < 0:
+            raise self._err(rc, "health_verify")
+        return {"healthy": rc == 0, "device_sum": d.value, "host_sum": h.value}
+
+    def _mfma_err(self, rc: int, what: str) -> ProbeError:
+        detail = {BAD_ARGS: "bad arguments", -1001: "null buffer"}.get(rc)
+        if detail is None:
+            detail = self.lib.xs_mfma_last_error().decode(errors="replace")
+        e = ProbeError(f"{what} failed ({rc}): {detail}")
+        e.rc = rc
+        return e
+
     def mfma_check(self, dev: int = 0, k: int = 64) -> dict:
-        """C[32x32] = A·B through v_mfma_f32_32x32x16_bf16 on exact integers."""
+        """C[32x32] = A·B through v_mfma_f32_32x32x16_bf16 on exact integers.
+        `k`: a positive multiple of 16, at most mfma_max_k() (ProbeError with
+        rc BAD_ARGS otherwise)."""
         rc = self.lib.xs_mfma_check(dev, k)
         if rc < 0:
-            raise ProbeError(f"mfma_check failed: {self.lib.xs_mfma_last_error().decode(errors='replace')}")
+            raise self._mfma_err(rc, "mfma_check")
         return {"healthy": rc == 0, "mismatches": int(rc), "k": k}
 
-    def mfma_peak(self, dev: int = 0, xcd_mask: int = 0xFF, iters: int = 4096, blocks: int = 0) -> dict:
-        """Dense bf16 MFMA TFLOP/s on the XCDs of `xcd_mask`."""
-        tf, ms, act = ctypes.c_double(), ctypes.c_double(), ctypes.c_int()
-        rc = self.lib.xs_mfma_peak(dev, iters, xcd_mask, blocks, ctypes.byref(tf), ctypes.byref(ms), ctypes.byref(act))
+    def mfma_max_k(self) -> int:
+        return int(self.lib.xs_mfma_max_k())
+
+    def mfma_inputs(self, k: int = 64):
+        """The check's operands as integers: (A [32, k], B [k, 32]), int32. No device call."""
+        import numpy as np
+
+        a, b = np.zeros((32, max(k, 0)), np.int32), np.zeros((max(k, 0), 32), np.int32)
+        rc = self.lib.xs_mfma_inputs(k, a.ctypes.data, b.ctypes.data)
         if rc != 0:
-            raise ProbeError(f"mfma_peak failed: {self.lib.xs_mfma_last_error().decode(errors='replace')}")
-        return {"tflops": tf.value, "ms": ms.value, "active_blocks": act.value, "xcd_mask": xcd_mask}
+            raise self._mfma_err(rc, "mfma_inputs")
+        return a, b
+
+    def mfma_compare(self, k: int, c, cap: int = 32) -> tuple[int, list[int]]:
+        """The check's comparator over a caller's C [32, 32] (fp32): the number
+        of elements that differ from the integer product of mfma_inputs(k) and
+        the flat indices of the first `cap` of them. No device call."""
+        import numpy as np
+
+        c = np.ascontiguousarray(c, np.float32)
+        if c.shape != (32, 32):
+            raise ValueError(f"mfma_compare: C is {c.shape}, not (32, 32)")
+        idx = np.full(max(cap, 1), -1, np.int32)
+        rc = self.lib.xs_mfma_compare(k, c.ctypes.data, idx.ctypes.data, cap)
+        if rc < 0:
+            raise self._mfma_err(rc, "mfma_compare")
+        return int(rc), [int(i) for i in idx[:min(rc, cap)]]
+
+    def mfma_tile(self, a_bits, b_bits, dev: int = 0):
+        """k_mfma_tile as the check launches it, on the caller's operands:
+        `a_bits` [32, K] and `b_bits` [K, 32] are uint16 bf16 bit patterns;
+        returns C [32, 32] as fp32. K is taken from `a_bits` and refused by the
+        C ABI unless a positive multiple of 16 up to mfma_max_k()."""
+        import numpy as np
+
+        a = np.ascontiguousarray(a_bits, np.uint16)
+        b = np.ascontiguousarray(b_bits, np.uint16)
+        if a.ndim != 2 or a.shape[0] != 32 or b.shape != (a.shape[1], 32):
+            raise ValueError(f"mfma_tile: A {a.shape} and B {b.shape} are not [32, K] and [K, 32]")
+        c = np.zeros((32, 32), np.float32)
+        rc = self.lib.xs_mfma_tile_op(dev, a.ctypes.data, b.ctypes.data, a.shape[1], c.ctypes.data)
+        if rc != 0:
+            raise self._mfma_err(rc, "mfma_tile_op")
+        return c
+
+    def mfma_peak_op(self, dev: int = 0, xcd_mask: int = 0xFF, iters: int = 1, blocks: int = 0) -> dict:
+        """One launch of k_mfma_peak's checked instantiation. `acc`: fp32
+        [blocks, 256, 4, 16], every lane's accumulators (all-ones bit patterns
+        where the workgroup did not run); `xcd`: the XCD of every workgroup;
+        `ran`: whether it ran; `active_per_xcd`: the kernel's eight counters."""
+        import numpy as np
+
+        n = blocks if blocks > 0 else 8 * int(self.props(dev)["computeUnits"])
+        acc = np.zeros((n, MFMA_PEAK_BLOCK, MFMA_PEAK_ACC, 16), np.float32)
+        xcd = np.zeros(n, np.uint32)
+        per = (ctypes.c_uint * 8)()
+        rc = self.lib.xs_mfma_peak_op(dev, iters, xcd_mask, n, acc.ctypes.data, xcd.ctypes.data, per)
+        if rc != 0:
+            raise self._mfma_err(rc, "mfma_peak_op")
+        return {"acc": acc, "xcd": (xcd & 0xF).astype(np.int64), "ran": (xcd & MFMA_DID_NOT_RUN) == 0,
+                "raw_xcd": xcd, "active_per_xcd": [int(v) for v in per], "iters": iters, "xcd_mask": xcd_mask}
+
+    def mfma_peak(self, dev: int = 0, xcd_mask: int = 0xFF, iters: int = 4096, blocks: int = 0) -> dict:
+        """Dense bf16 MFMA TFLOP/s on the XCDs of `xcd_mask` (1..0xFF). `flops`
+        is what the timed dispatch is credited with: active_blocks x 4 waves x
+        4 accumulators x iters x 2*32*32*16. Raises ProbeError with rc
+        MFMA_IDLE_XCD when a selected XCD ran no workgroup."""
+        tf, ms, act, fl = ctypes.c_double(), ctypes.c_double(), ctypes.c_int(), ctypes.c_double()
+        per = (ctypes.c_uint * 8)()
+        rc = self.lib.xs_mfma_peak(dev, iters, xcd_mask, blocks, ctypes.byref(tf), ctypes.byref(ms), ctypes.byref(act),
+                                   per, ctypes.byref(fl))
+        if rc != 0:
+            raise self._mfma_err(rc, "mfma_peak")
+        return {"tflops": tf.value, "ms": ms.value, "active_blocks": act.value, "xcd_mask": xcd_mask,
+                "active_per_xcd": [int(v) for v in per], "flops": fl.value, "iters": iters if iters > 0 else 4096}
 
 
     # ------------------------------------------------------------- CU sweep

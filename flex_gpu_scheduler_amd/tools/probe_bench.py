@@ -9,7 +9,7 @@ from __future__ import annotations
 import json
 import sys
 
-from ..ops.hip_probe import probe
+from ..ops.hip_probe import MFMA_IDLE_XCD, ProbeError, probe
 
 
 def main() -> int:
@@ -26,7 +26,15 @@ def main() -> int:
     out["mfma_check"] = pr.mfma_check(dev, 256)
     out["mfma_bf16"] = []
     for label, mask in (("cpx-1xcd", 0x01), ("qpx-2xcd", 0x03), ("dpx-4xcd", 0x0F), ("spx-8xcd", 0xFF)):
-        r = pr.mfma_peak(dev, mask, iters=8192)
+        try:
+            r = pr.mfma_peak(dev, mask, iters=8192)
+        except ProbeError as e:
+            if e.rc != MFMA_IDLE_XCD:
+                raise
+            # A selected XCD ran no workgroup (a partitioned device, or other
+            # tenants held it): no rate for a partition that did not all work.
+            out["mfma_bf16"].append({"partition": label, "TFLOPs": None, "ms": None, "unmeasured": str(e)})
+            continue
         out["mfma_bf16"].append({"partition": label, "TFLOPs": round(r["tflops"], 1), "ms": round(r["ms"], 3),
                                  "active_blocks": r["active_blocks"]})
     print(json.dumps(out))

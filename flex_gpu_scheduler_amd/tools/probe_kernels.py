@@ -17,7 +17,16 @@ from __future__ import annotations
 import json
 import sys
 
-from ..ops.hip_probe import probe
+from ..ops.hip_probe import MFMA_IDLE_XCD, ProbeError, probe
+
+
+def mfma_row(r: dict) -> dict:
+    """The `mfma` line from a HipProbe.mfma_peak result: the flops the probe
+    credited to the timed dispatch (every dispatch runs the same tile loop)
+    and the MFMA instructions that is."""
+    flops = r["flops"]
+    return {"kernel": "k_mfma_peak", "TFLOPs": round(r["tflops"], 1), "ms": round(r["ms"], 3),
+            "flops_per_dispatch": round(flops), "mfma_insts_per_dispatch": round(flops / (2 * 32 * 32 * 16))}
 
 
 def main() -> int:
@@ -26,10 +35,12 @@ def main() -> int:
     iters = int(sys.argv[3]) if len(sys.argv) > 3 else 5
     pr = probe()
     if what == "mfma":
-        r = pr.mfma_peak(dev, 0xFF, iters=8192)
-        flops = r["tflops"] * 1e12 * r["ms"] * 1e-3  # per dispatch: every dispatch runs the same tile loop
-        out = {"kernel": "k_mfma_peak", "TFLOPs": round(r["tflops"], 1), "ms": round(r["ms"], 3),
-               "flops_per_dispatch": round(flops), "mfma_insts_per_dispatch": round(flops / (2 * 32 * 32 * 16))}
+        try:
+            out = mfma_row(pr.mfma_peak(dev, 0xFF, iters=8192))
+        except ProbeError as e:
+            if e.rc != MFMA_IDLE_XCD:
+                raise
+            out = {"kernel": "k_mfma_peak", "TFLOPs": None, "ms": None, "unmeasured": str(e)}
     elif what in ("hbm-read", "hbm-copy", "hbm-triad", "hbm-write"):
         mode = what.split("-")[1]
         bw = pr.hbm_bandwidth(dev, 2 << 30, iters=iters, mode=mode)
