@@ -344,7 +344,9 @@ def health_fn_args(args) -> dict:
     --health-matrix-sweep: absent -> None, bare -> "all", else a comma list.
     --health-hbm-sweep: absent -> no hbm keys, bare -> all free HBM less the
     reserve (hbm_gib None), else that many GiB.
-    --health-register-sweep: absent -> no regfile key."""
+    --health-register-sweep: absent -> no regfile key.
+    --health-lane-sweep: absent -> no lane keys, bare -> every path
+    (lane_paths None), else a comma list."""
     m = args.health_matrix_sweep
     formats = None if m in (None, "all") else [f.strip() for f in m.split(",") if f.strip()]
     kw = {"sweep": args.health_sweep, "sweep_period_s": args.health_sweep_period, "matrix": m is not None,
@@ -354,6 +356,9 @@ def health_fn_args(args) -> dict:
         kw.update(hbm=True, hbm_gib=None if h == "all" else float(h))
     if getattr(args, "health_register_sweep", False):
         kw.update(regfile=True)
+    ln = getattr(args, "health_lane_sweep", None)
+    if ln is not None:
+        kw.update(lane=True, lane_paths=None if ln == "all" else [f.strip() for f in ln.split(",") if f.strip()])
     return kw
 
 
@@ -372,7 +377,8 @@ def cmd_node_agent(args) -> int:
                       reserved_memory_gib=args.reserved_memory_gib,
                       health_fn=(hip_health_fn(**health_fn_args(args))
                                  if args.health_probe or args.health_sweep or args.health_matrix_sweep is not None
-                                 or args.health_hbm_sweep is not None or args.health_register_sweep else None),
+                                 or args.health_hbm_sweep is not None or args.health_register_sweep
+                                 or args.health_lane_sweep is not None else None),
                       bandwidth_fn=hip_bandwidth_fn() if args.bandwidth_probe else None,
                       kubelet_managed=args.kubelet_managed).start()
     if args.device_plugin:
@@ -547,6 +553,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "SIMD written and read back in both polarities on every CU; a bad XCD is fenced like "
                         "--health-sweep's and its register files are published as registerFaults. Implies "
                         "--health-probe; independent of the other sweeps")
+    p.add_argument("--health-lane-sweep", nargs="?", const="all", default=None, metavar="PATHS",
+                   help="health probe plus the lane sweep: dpp, permlane, readlane, bpermute, ldswide, ldstr, "
+                        "ldsatomic and ldsdma (the cross-lane network and the wide, sub-dword, transposed, atomic and "
+                        "DMA LDS paths) run on every CU (a comma list selects some; default all); a bad XCD is fenced "
+                        "like --health-sweep's and its paths are published as laneFaults. Implies --health-probe; "
+                        "independent of the other sweeps")
     p.add_argument("--health-sweep-period", type=float, default=600.0, metavar="SECONDS",
                    help="reuse a sweep's verdict this long before sweeping the GPU again")
     p.add_argument("--bandwidth-probe", action="store_true",

@@ -16,7 +16,8 @@ exporter + metrics-server:
     e.g. from the CU sweep) fences only the compute partitions holding them
     on a DPX/QPX/CPX GPU (`xcdFaults` in the topology annotation), and the
     matrix formats such an XCD gets wrong are published as `matrixFaults`
-    and the register files it reads back wrong as `registerFaults`;
+    and the register files it reads back wrong as `registerFaults` and the
+    cross-lane and LDS paths it moves data wrongly through as `laneFaults`;
     a verdict that carries an HBM fault (the HBM sweep) withholds the whole
     GPU, partitioned or not, and is published as `hbmFaults`;
   * samples load (gpu/telemetry.py) and publishes its WatcherMetrics document
@@ -104,6 +105,9 @@ class NodeAgent:
         # GPU index -> {XCD id: {"files", "cells", "flipMask", "simds"}}, from
         # GpuHealth.detail["registerFaults"] (the register-file sweep).
         self.register_faults: dict[int, dict[int, dict]] = {}
+        # GPU index -> {XCD id: lane-sweep paths it gets wrong}, from
+        # GpuHealth.detail["laneFaults"] (the lane sweep).
+        self.lane_faults: dict[int, dict[int, list[str]]] = {}
         # GPU index -> what the HBM sweep found wrong, from
         # GpuHealth.detail["hbmFaults"]; such a GPU is withheld as a whole.
         self.hbm_faults: dict[int, dict] = {}
@@ -126,21 +130,24 @@ class NodeAgent:
         return self._probe_health(host)[:2]
 
     def _probe_health(self, host: HostInfo) -> tuple[set[int], dict[int, set[int]], dict[int, dict[int, list[str]]],
-                                                     dict[int, dict], dict[int, dict[int, dict]]]:
+                                                     dict[int, dict], dict[int, dict[int, dict]],
+                                                     dict[int, dict[int, list[str]]]]:
         """probe_health plus the matrix formats each bad XCD got wrong, the
-        HBM faults per GPU and what the register-file sweep found per bad XCD.
+        HBM faults per GPU, what the register-file sweep found per bad XCD and
+        the lane-sweep paths each bad XCD got wrong.
 
         An HBM fault (detail["hbmFaults"]) withholds the whole GPU, partitioned
         or not, and even when the same verdict names bad XCDs: the sweep knows
         a fault by its virtual address, which cannot be tied to the HBM slice
         of one compute partition, so there is no partial fence for memory."""
         if self.health_fn is None:
-            return set(), {}, {}, {}, {}
+            return set(), {}, {}, {}, {}, {}
         bad: set[int] = set()
         xcds: dict[int, set[int]] = {}
         formats: dict[int, dict[int, list[str]]] = {}
         hbm: dict[int, dict] = {}
         registers: dict[int, dict[int, dict]] = {}
+        lanes: dict[int, dict[int, list[str]]] = {}
         # HIP ordinals follow the KFD node order of the GPUs this process can
         # open; GPUs whose KFD node is hidden (other containers' devices) are
         # not probed. With no KFD info at all (fake hosts) use the index.
@@ -158,6 +165,9 @@ class NodeAgent:
                     rf = {int(x): dict(f) for x, f in (r.detail.get("registerFaults") or {}).items() if f}
                     if rf:
                         registers[g.index] = rf
+                    lf = {int(x): list(f) for x, f in (r.detail.get("laneFaults") or {}).items() if f}
+                    if lf:
+                        lanes[g.index] = lf
                 if isinstance(r, GpuHealth) and r.bad_xcds:
                     xcds[g.index] = set(r.bad_xcds)
                     if g.partitions == 1 or g.index in hbm:
@@ -169,7 +179,7 @@ class NodeAgent:
             except Exception as e:  # noqa: BLE001
                 log.warning("health probe GPU %d failed: %s", g.index, e)
                 bad.add(g.index)
-        return bad, xcds, formats, hbm, registers
+        return bad, xcds, formats, hbm, registers, lanes
 
     @staticmethod
     def _fenced(gpus, xcd_faults) -> dict[int, tuple[int, int]]:
@@ -207,7 +217,8 @@ class NodeAgent:
                    xcd_faults: dict[int, set[int]] | None = None,
                    matrix_faults: dict[int, dict[int, list[str]]] | None = None,
                    hbm_faults: dict[int, dict] | None = None,
-                   register_faults: dict[int, dict[int, dict]] | None = None) -> dict:
+                   register_faults: dict[int, dict[int, dict]] | None = None,
+                   lane_faults: dict[int, dict[int, list[str]]] | None = None) -> dict:
         healthy = [g for g in host.gpus if g.index not in unhealthy]
         infos = [g.to_gpu_info() for g in healthy]
         mem_kib = max(0, host.memory_bytes // 1024 - self.reserved_memory_gib * (1 << 20))
@@ -248,6 +259,13 @@ class NodeAgent:
         regs = {i: per for i, per in regs.items() if per}
         if regs:
             topo["registerFaults"] = regs
+        # Which cross-lane and LDS paths each faulty XCD gets wrong:
+        # informational, as matrixFaults is.
+        lanes = {str(i): {str(x): list(f) for x, f in sorted(per.items()) if f}
+                 for i, per in sorted((lane_faults or {}).items())}
+        lanes = {i: per for i, per in lanes.items() if per}
+        if lanes:
+            topo["laneFaults"] = lanes
         # What the HBM sweep found on a GPU (which is withheld as a whole).
         hbm = {str(i): dict(f) for i, f in sorted((hbm_faults or {}).items()) if f}
         if hbm:
@@ -344,14 +362,15 @@ class NodeAgent:
     def sync(self) -> HostInfo:
         host = self.host_fn()
         (self.unhealthy, self.unhealthy_xcds, self.matrix_faults, self.hbm_faults,
-         self.register_faults) = self._probe_health(host)
+         self.register_faults, self.lane_faults) = self._probe_health(host)
         self.measure_bandwidth(host)
         for dp in self.device_plugins:
             dp.host = host
             dp.set_unhealthy(self.unhealthy)
             dp.set_unhealthy_xcds(self.unhealthy_xcds)
         self._upsert("nodes", self.build_node(host, self.unhealthy, self.unhealthy_xcds, self.matrix_faults,
-                                              self.hbm_faults, self.register_faults), keep_spec=True)
+                                              self.hbm_faults, self.register_faults, self.lane_faults),
+                     keep_spec=True)
         self._upsert("noderesourcetopologies", self.build_nrt(host, self.unhealthy, self.unhealthy_xcds),
                      keep_spec=False)
         self.host = host
@@ -392,10 +411,11 @@ class NodeAgent:
 
     def _heartbeat_and_resync(self) -> None:
         host = self.host_fn()
-        unhealthy, xcds, formats, hbm, registers = self._probe_health(host)
+        unhealthy, xcds, formats, hbm, registers, lanes = self._probe_health(host)
         changed = (self.host is None or [g.to_gpu_info() for g in host.gpus] != [g.to_gpu_info() for g in self.host.gpus]
                    or unhealthy != self.unhealthy or xcds != self.unhealthy_xcds or formats != self.matrix_faults
-                   or hbm != self.hbm_faults or registers != self.register_faults)
+                   or hbm != self.hbm_faults or registers != self.register_faults
+                   or lanes != self.lane_faults)
         if changed:
             self.sync()
         else:
@@ -411,7 +431,8 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
                   matrix: bool = False, matrix_formats: list | None = None,
                   matrix_args: dict | None = None, hbm: bool = False, hbm_gib: float | None = None,
                   hbm_args: dict | None = None, regfile: bool = False,
-                  regfile_args: dict | None = None) -> Callable[[int], "bool | GpuHealth"]:
+                  regfile_args: dict | None = None, lane: bool = False, lane_paths: list | None = None,
+                  lane_args: dict | None = None) -> Callable[[int], "bool | GpuHealth"]:
     """Health callback backed by the HIP probes (HBM pattern + checksum and an
     MFMA tile check per GPU).
 
@@ -422,9 +443,14 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
     fp8, bf8, i8 and the block-scaled MX formats on every CU. `regfile`: also
     run the register-file sweep (HipProbe.regfile_sweep, `regfile_args` are its
     keywords), which writes and reads back every VGPR and AGPR of every SIMD.
+    `lane`: also run the lane sweep (HipProbe.lane_sweep over `lane_paths`,
+    None for all; `lane_args` are its other keywords), which moves hashed
+    values through the DPP shifters, the permlane swaps, readlane / writelane,
+    the LDS crossbar and the wide, sub-dword, transposed, atomic and DMA LDS
+    paths of every CU; detail["laneFaults"] = {xcd: [path, ...]}.
     The callback runs on every heartbeat, so the sweeps' verdict is reused for
     `sweep_period_s`. On a device that shows all 8 XCDs the verdict is a
-    GpuHealth naming the bad physical XCDs of any of the three sweeps, with
+    GpuHealth naming the bad physical XCDs of any of these sweeps, with
     detail["matrixFaults"] = {xcd: [format, ...]} and detail["registerFaults"]
     = {xcd: {"files": [...], "cells": n, "flipMask": "0x...", "simds": n}}; a
     partition device numbers its XCDs logically, so there a failed sweep fails
@@ -483,6 +509,16 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
             bad |= set(g["bad_xcds"])
             detail["registerSweep"] = g
             detail["registerFaults"] = reg_faults
+        if lane:
+            n = p.lane_sweep(dev, paths=lane_paths, **(lane_args or {}))["summary"]
+            lane_faults = {int(x): list(v["failed_paths"]) for x, v in n["xcds"].items() if v["failed_paths"]}
+            log.log(logging.WARNING if n["bad_xcds"] else logging.INFO,
+                    "lane sweep GPU %d: %d CUs on %d XCDs in %.2f ms (%d launch(es)), covered=%s uncovered=%s "
+                    "faults=%s", dev, n["cus_seen"], len(n["xcds"]), n["ms"], n["rounds"], n["covered"],
+                    {x: u for x, u in n["uncovered"].items() if u}, lane_faults)
+            bad |= set(n["bad_xcds"])
+            detail["laneSweep"] = n
+            detail["laneFaults"] = lane_faults
         hbm_faults: dict = {}
         if hbm:
             h = None
@@ -519,7 +555,7 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
         # HBM pattern/checksum and an exact-integer MFMA tile: a GPU whose matrix
         # cores mis-compute is withheld even if its memory checks out.
         ok = bool(p.health(dev)["healthy"]) and bool(p.mfma_check(dev)["healthy"])
-        if not (sweep or matrix or hbm or regfile) or not ok:
+        if not (sweep or matrix or hbm or regfile or lane) or not ok:
             return ok
         return sweep_verdict(dev)
 

@@ -1,6 +1,6 @@
 """ctypes front-end for the HIP/CDNA4 device probes (csrc/hip/hbm_probe.hip,
 csrc/hip/mfma_probe.hip, csrc/hip/cu_sweep.hip, csrc/hip/matrix_sweep.hip,
-csrc/hip/hbm_sweep.hip, csrc/hip/regfile_sweep.hip).
+csrc/hip/hbm_sweep.hip, csrc/hip/regfile_sweep.hip, csrc/hip/lane_sweep.hip).
 
 The probes are what the node agent runs before advertising an MI355X as
 schedulable: device properties, HBM streaming bandwidth (optionally with a
@@ -13,7 +13,10 @@ format (f16, f32, f64, fp8, bf8, i8 and the block-scaled MX fp8/fp6/fp4) on
 every CU and names the formats a CU gets wrong, and a sweep of all free HBM
 with an address-keyed pattern in both polarities that names the vectors and
 bits that read back wrong, and a sweep of every SIMD's whole VGPR/AGPR file
-that names the register file, the cells and the SIMDs that read back wrong.
+that names the register file, the cells and the SIMDs that read back wrong,
+and a sweep of every CU's cross-lane network (DPP, permlane swaps, readlane /
+writelane, the LDS crossbar) and wide, sub-dword, transposed, atomic and DMA
+LDS paths that names the paths a CU gets wrong.
 """
 from __future__ import annotations
 
@@ -78,6 +81,12 @@ REGFILE_SEED = 0x5BD1E995
 REGFILE_FILES = ["vgpr", "agpr"]  # fail bit order
 REGFILE_CELLS = 512  # per lane: v0..v255 then a0..a255
 REGFILE_NO_CELL = 0xFFFF  # `first` of a record without a mis-compare
+
+# k_lane_sweep (csrc/hip/lane_sweep.hip): one 128-byte record per workgroup,
+# {xcd, cu, simd_mask, fail, 8 bad counts, 8 digests, bad_simds, 0 x 11}.
+LANE_RECORD_WORDS = 32
+LANE_SEED = 0x1B873593
+LANE_BLOCK = 256  # threads per workgroup: the last axis of a probe's dump
 
 # k_hbm_fill / k_hbm_verify (csrc/hip/hbm_sweep.hip)
 HBM_SWEEP_SEED = 0x5EED1E55
@@ -218,6 +227,15 @@ class HipProbe:
         L.xs_regfile_sweep.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_int,
                                        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                        ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]
+        L.xs_lane_sweep_last_error.restype = ctypes.c_char_p
+        L.xs_lane_paths.restype = ctypes.c_char_p
+        L.xs_lane_shape.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        L.xs_lane_probe.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]
+        L.xs_lane_sweep_expected.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
+        L.xs_lane_sweep_info.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        L.xs_lane_sweep.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int,
+                                    ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int),
+                                    ctypes.POINTER(ctypes.c_double)]
         L.xs_hbm_sweep_last_error.restype = ctypes.c_char_p
         L.xs_hbm_sweep_pattern.argtypes = [ctypes.c_uint64, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int,
                                            ctypes.c_void_p]
@@ -838,6 +856,114 @@ class HipProbe:
         summary.update(rounds=rounds, ms=total_ms, blocks=n_blocks, seed=seed)
         return {"records": records, "summary": summary}
 
+    # ----------------------------------------------------------- lane sweep
+    def lane_paths(self) -> list[str]:
+        """Path names of the lane sweep; the index is the path's bit."""
+        return self.lib.xs_lane_paths().decode().split(",")
+
+    def _lane_mask(self, paths) -> int:
+        names = self.lane_paths()
+        if paths is None:
+            return (1 << len(names)) - 1
+        mask = 0
+        for f in [paths] if isinstance(paths, str) else paths:
+            if f not in names:
+                raise ValueError(f"unknown lane path {f!r}; known: {', '.join(names)}")
+            mask |= 1 << names.index(f)
+        return mask
+
+    def lane_shape(self, path: str) -> dict:
+        """`steps` of one path and the `words` every thread receives per step."""
+        self._lane_mask([path])
+        out = (ctypes.c_int * 2)()
+        rc = self.lib.xs_lane_shape(self.lane_paths().index(path), out)
+        if rc != 0:
+            raise _lane_error(self, rc, "lane_shape")
+        return {"steps": out[0], "words": out[1]}
+
+    def lane_probe(self, dev: int, path: str, seed: int = LANE_SEED):
+        """k_lane_probe: one workgroup runs `path` and stores every value it
+        received: uint32 [steps, words, 256] (thread = 64 x wave + lane)."""
+        import numpy as np
+
+        sh = self.lane_shape(path)
+        out = np.zeros((sh["steps"], sh["words"], LANE_BLOCK), np.uint32)
+        rc = self.lib.xs_lane_probe(dev, self.lane_paths().index(path), seed, out.ctypes.data, out.size)
+        if rc != 0:
+            raise _lane_error(self, rc, "lane_probe")
+        return out
+
+    def lane_sweep_expected(self, paths=None, seed: int = LANE_SEED) -> dict:
+        """The workgroup digest a healthy CU leaves per selected path,
+        computed on the host from the lane maps."""
+        names = self.lane_paths()
+        mask = self._lane_mask(paths)
+        out = (ctypes.c_uint32 * len(names))()
+        rc = self.lib.xs_lane_sweep_expected(mask, seed, out)
+        if rc != 0:
+            raise _lane_error(self, rc, "lane_sweep_expected")
+        return {n: out[i] for i, n in enumerate(names) if mask >> i & 1}
+
+    def lane_sweep_info(self, dev: int = 0) -> dict:
+        """What the runtime reports for k_lane_sweep: `num_regs`,
+        `scratch_bytes` per lane, `lds_bytes` per workgroup and `blocks_per_cu`
+        (workgroups that fit on a CU at once)."""
+        out = (ctypes.c_int * 4)()
+        rc = self.lib.xs_lane_sweep_info(dev, out)
+        if rc != 0:
+            raise _lane_error(self, rc, "lane_sweep_info")
+        return {"num_regs": out[0], "scratch_bytes": out[1], "lds_bytes": out[2], "blocks_per_cu": out[3]}
+
+    def lane_sweep(self, dev: int = 0, blocks: int = 0, paths=None, seed: int = LANE_SEED,
+                   inject: tuple | None = None, max_rounds: int = 4) -> dict:
+        """k_lane_sweep: every selected path (None: all) of the cross-lane
+        network and the LDS access paths run on every CU a workgroup lands on.
+        `inject` = (xcd, cu key or None for every CU of that XCD, [path
+        names]): those workgroups flip one bit of one received value of those
+        paths (tests the comparator on a healthy GPU). `blocks` 0: 4 per CU.
+
+        Relaunched while some CU has not been seen, as cu_sweep does. Returns
+        {"records": [...], "summary": summarize_lane_sweep(...) plus rounds,
+        ms, blocks, paths, seed}."""
+        names = self.lane_paths()
+        mask = self._lane_mask(paths)
+        cus = int(self.props(dev)["computeUnits"])
+        n_blocks = blocks if blocks != 0 else 4 * cus
+        ix, ic, im = -1, -1, 0
+        if inject is not None:
+            ix, ic, im = int(inject[0]), -1 if inject[1] is None else int(inject[1]), self._lane_mask(inject[2])
+        expected = None
+        records: list[dict] = []
+        total_ms, rounds = 0.0, 0
+        summary: dict = {}
+        for _ in range(max(1, max_rounds if n_blocks >= cus else 1)):
+            buf = (ctypes.c_uint32 * (LANE_RECORD_WORDS * max(1, n_blocks)))()
+            n, ms = ctypes.c_int(), ctypes.c_double()
+            rc = self.lib.xs_lane_sweep(dev, n_blocks, mask, seed, ix, ic, im, buf, ctypes.byref(n), ctypes.byref(ms))
+            if rc != 0:
+                raise _lane_error(self, rc, "lane_sweep")
+            if expected is None:
+                expected = self.lane_sweep_expected([f for i, f in enumerate(names) if mask >> i & 1], seed)
+            rounds += 1
+            total_ms += ms.value
+            for i in range(n.value):
+                w = buf[LANE_RECORD_WORDS * i:LANE_RECORD_WORDS * (i + 1)]
+                rec = {"xcd": w[0], "cu": w[1], "simd_mask": w[2], "fail": w[3],
+                       "bad": {f: w[4 + b] for b, f in enumerate(names)},
+                       "digests": {f: w[12 + b] for b, f in enumerate(names)}, "bad_simds": w[20]}
+                # A digest that differs from the host's is a failure even if
+                # the device-side comparator (on the same CU) passed it.
+                for b, f in enumerate(names):
+                    if rec["digests"][f] != expected.get(f, 0):
+                        rec["fail"] |= 1 << b
+                records.append(rec)
+            summary = summarize_lane_sweep(records, cus, names)
+            if summary["covered"]:
+                break
+        summary.update(rounds=rounds, ms=total_ms, blocks=n_blocks, seed=seed,
+                       paths=[f for i, f in enumerate(names) if mask >> i & 1])
+        return {"records": records, "summary": summary}
+
     # ------------------------------------------------------------ HBM sweep
     def hbm_sweep_pattern(self, first_vec: int, nvec: int, seed: int = HBM_SWEEP_SEED, inverted: bool = False):
         """The sweep's pattern for 16-byte vectors [first_vec, first_vec +
@@ -1061,6 +1187,30 @@ def summarize_regfile_sweep(records: list[dict], compute_units: int) -> dict:
     for f in flips.values():
         flip |= f
     s["flip_mask"] = f"0x{flip:08x}"
+    return s
+
+
+def _lane_error(p: HipProbe, rc: int, what: str) -> ProbeError:
+    detail = "bad arguments" if rc == BAD_ARGS else p.lib.xs_lane_sweep_last_error().decode(errors="replace")
+    e = ProbeError(f"{what} failed ({rc}): {detail}")
+    e.rc = rc
+    return e
+
+
+def summarize_lane_sweep(records: list[dict], compute_units: int, paths: list[str]) -> dict:
+    """summarize_sweep over k_lane_sweep records, whose fail bits are path
+    bits (`paths` names them in bit order): adds `failed_paths` per XCD and
+    overall."""
+    s = summarize_sweep(records, compute_units)
+
+    def names(bits: int) -> list[str]:
+        return [f for b, f in enumerate(paths) if bits >> b & 1]
+
+    every = 0
+    for v in s["xcds"].values():
+        v["failed_paths"] = names(v["fail_bits"])
+        every |= v["fail_bits"]
+    s["failed_paths"] = names(every)
     return s
 
 
