@@ -46,34 +46,21 @@
 #include <cstdint>
 #include <cstdio>
 
-#include "hip/device_raii.h"
+#include "hip/sweep_common.h"
 
-#define XS_CHECK(x)                                                                        \
-  do {                                                                                     \
-    hipError_t e_ = (x);                                                                   \
-    if (e_ != hipSuccess) {                                                                \
-      std::snprintf(g_sweep_err, sizeof g_sweep_err, "%s: %s", #x, hipGetErrorString(e_)); \
-      return -static_cast<int>(e_) - 1;                                                    \
-    }                                                                                      \
-  } while (0)
+#define XS_ERR_BUF g_sweep_err
 
 namespace {
 
-char g_sweep_err[512];
+xsprobe::ErrBuf g_sweep_err;
 
-using xsprobe::DevMem;
-using xsprobe::Event;
+using namespace xsprobe;
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kSweepBlock = 256;            // 4 waves: one per SIMD
-constexpr int kSweepChain = 32768;          // hash-chain steps per lane
-constexpr size_t kLdsPerCu = 160u << 10;    // LDS of one gfx950 CU
-constexpr size_t kLdsExclusive = 96u << 10; // > half a CU's LDS: one sweep workgroup per CU
-constexpr int kMaxBlocks = 1 << 20;
-constexpr int kBadArgs = -1000;
+constexpr int kSweepBlock = 256;    // 4 waves: one per SIMD
+constexpr int kSweepChain = 32768;  // hash-chain steps per lane
 
 enum : uint32_t { kFailMfma = 1, kFailValu = 2, kFailLds = 4 };
 
@@ -83,10 +70,6 @@ struct SweepRecord {
 };
 static_assert(sizeof(SweepRecord) == 32, "one 32-byte record per workgroup");
 
-__host__ __device__ __forceinline__ uint32_t rotl32(uint32_t x, int s) {
-  s &= 31;
-  return s ? (x << s) | (x >> (32 - s)) : x;
-}
 __host__ __device__ __forceinline__ uint32_t chain_step(uint32_t x) {
   x = x * 1664525u + 1013904223u;
   x ^= x >> 15;
@@ -98,39 +81,16 @@ __host__ __device__ __forceinline__ uint32_t lds_pattern(uint32_t i, int pass) {
   return (i * 2654435761u ^ 0xa5a5a5a5u) ^ (pass ? 0xffffffffu : 0u);
 }
 
-__device__ __forceinline__ uint32_t sweep_xcc_id() {
-  uint32_t v;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
-  return v & 0xf;
-}
-__device__ __forceinline__ uint32_t sweep_hw_id() {
-  uint32_t v;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(v));
-  return v;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_or(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(kSweepBlock) void k_cu_sweep(SweepRecord* __restrict__ records, int K, uint32_t lds_words,
                                                          int inject_xcd, int inject_cu, uint32_t inject_engines,
                                                          uint32_t expect_valu) {
   extern __shared__ uint32_t sweep_lds[];
   const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const uint32_t xcd = sweep_xcc_id();
-  const uint32_t hw = sweep_hw_id();
-  const uint32_t cu = (hw >> 8) & 0xffu;
-  const uint32_t simd = (hw >> 4) & 0x3u;
-  const bool inject = inject_xcd >= 0 && xcd == static_cast<uint32_t>(inject_xcd) &&
-                      (inject_cu < 0 || cu == static_cast<uint32_t>(inject_cu));
+  const uint32_t xcd = xcc_id();
+  const uint32_t hw = hw_id();
+  const uint32_t cu = cu_key(hw);
+  const uint32_t simd = simd_id(hw);
+  const bool inject = inject_selected(inject_xcd, inject_cu, xcd, cu);
   const uint32_t inj = inject ? inject_engines : 0u;
   uint32_t fail = 0;
 
@@ -248,15 +208,6 @@ uint32_t expected_lds(size_t lds_bytes) {
   return d[0] ^ rotl32(d[1], 16);
 }
 
-// Largest dynamic LDS one workgroup may ask for on `dev`, in whole KiB.
-int max_lds(int dev, size_t* out) {
-  hipDeviceProp_t p;
-  XS_CHECK(hipGetDeviceProperties(&p, dev));
-  size_t m = std::max<size_t>(p.sharedMemPerBlock, p.maxSharedMemoryPerMultiProcessor);
-  *out = std::min(m, kLdsPerCu) & ~static_cast<size_t>(1023);
-  return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -266,7 +217,7 @@ const char* xs_cu_sweep_last_error() { return g_sweep_err; }
 // Bytes of LDS the sweep can cover on `dev` (0 on error).
 size_t xs_cu_sweep_max_lds(int dev) {
   size_t m = 0;
-  return max_lds(dev, &m) == 0 ? m : 0;
+  return max_workgroup_lds(g_sweep_err, dev, &m) == 0 ? m : 0;
 }
 
 // Host-side digests from the same formulas: out3 = {mfma, valu, lds}.
@@ -280,46 +231,23 @@ int xs_cu_sweep_expected(int k, size_t lds_bytes, uint32_t* out3) {
 
 // One sweep launch of `blocks` workgroups (0: 4 per CU). Writes `blocks`
 // 32-byte records to records_out (the caller's buffer holds at least that
-// many; with blocks == 0, 4 x computeUnits). Returns 0, -1000 for bad
+// many; with blocks == 0, 4 x computeUnits). Any negative inject_xcd selects
+// no workgroup and any negative inject_cu every CU. Returns 0, -1000 for bad
 // arguments (nothing is launched), or a negative HIP error.
 int xs_cu_sweep(int dev, int blocks, int k, size_t lds_bytes, int inject_xcd, int inject_cu, int inject_engines,
                 void* records_out, int* n_records, double* ms) {
-  if ((k != 16 && k != 64) || lds_bytes < 1024 || lds_bytes % 1024 || !records_out) return kBadArgs;
-  if (inject_engines < 0 || inject_engines > 7 || inject_xcd > 15 || inject_cu > 0xff) return kBadArgs;
-  XS_CHECK(hipSetDevice(dev));
-  hipDeviceProp_t p;
-  XS_CHECK(hipGetDeviceProperties(&p, dev));
-  size_t lds_max = 0;
-  if (int rc = max_lds(dev, &lds_max)) return rc;
-  if (lds_bytes > lds_max) return kBadArgs;
-  if (blocks == 0) blocks = 4 * p.multiProcessorCount;
-  if (blocks <= 0 || blocks > kMaxBlocks) return kBadArgs;
-  // The allocation always exceeds half a CU's LDS, whatever part of it is
-  // tested, so sweep workgroups never share a CU.
-  const size_t smem = std::max(lds_bytes, std::min(kLdsExclusive, lds_max));
-  XS_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_cu_sweep), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               static_cast<int>(smem)));
-  DevMem rec;
-  const size_t bytes = static_cast<size_t>(blocks) * sizeof(SweepRecord);
-  XS_CHECK(hipMalloc(&rec.p, bytes));
-  XS_CHECK(hipMemset(rec.p, 0xff, bytes));
-  Event e0, e1;
-  XS_CHECK(hipEventCreate(&e0.e));
-  XS_CHECK(hipEventCreate(&e1.e));
+  if ((k != 16 && k != 64) || lds_bytes < 1024 || lds_bytes % 1024) return kBadArgs;
+  if (inject_engines < 0 || inject_engines > 7) return kBadArgs;
+  SweepCall call{dev, blocks, inject_xcd, inject_cu, records_out, n_records, ms};
+  call.negative_inject_ok = true;
   const uint32_t expect_valu = expected_valu();
-  XS_CHECK(hipEventRecord(e0.e, 0));
-  hipLaunchKernelGGL(k_cu_sweep, dim3(blocks), dim3(kSweepBlock), smem, 0, rec.as<SweepRecord>(), k,
-                     static_cast<uint32_t>(lds_bytes / 4), inject_xcd, inject_cu, static_cast<uint32_t>(inject_engines),
-                     expect_valu);
-  XS_CHECK(hipGetLastError());
-  XS_CHECK(hipEventRecord(e1.e, 0));
-  XS_CHECK(hipEventSynchronize(e1.e));
-  float t = 0.f;
-  XS_CHECK(hipEventElapsedTime(&t, e0.e, e1.e));
-  XS_CHECK(hipMemcpy(records_out, rec.p, bytes, hipMemcpyDeviceToHost));
-  if (n_records) *n_records = blocks;
-  if (ms) *ms = t;
-  return 0;
+  // The first lds_bytes of the allocation are tested, whatever its size.
+  return launch_sweep(g_sweep_err, call, reinterpret_cast<const void*>(k_cu_sweep), kSweepBlock, lds_bytes,
+                      sizeof(SweepRecord), [&](dim3 grid, dim3 block, size_t smem, void* rec) {
+                        hipLaunchKernelGGL(k_cu_sweep, grid, block, smem, 0, static_cast<SweepRecord*>(rec), k,
+                                           static_cast<uint32_t>(lds_bytes / 4), inject_xcd, inject_cu,
+                                           static_cast<uint32_t>(inject_engines), expect_valu);
+                      });
 }
 
 }  // extern "C"

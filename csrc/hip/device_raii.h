@@ -1,5 +1,5 @@
-// Scoped owners for the probes' HIP resources. Every XS_CHECK/XS_MCHECK early
-// return releases what was acquired so far: the node agent runs these probes
+// Scoped owners for the probes' HIP resources. Every XS_CHECK early return
+// releases what was acquired so far: the node agent runs these probes
 // repeatedly in one long-lived process, so an error path must not leak HBM.
 #pragma once
 

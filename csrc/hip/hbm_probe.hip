@@ -51,24 +51,19 @@
 #include <cstring>
 #include <vector>
 
-#include "hip/device_raii.h"
+#include "hip/sweep_common.h"
 
-#define XS_CHECK(x)                                                            \
-  do {                                                                         \
-    hipError_t e_ = (x);                                                       \
-    if (e_ != hipSuccess) {                                                    \
-      std::snprintf(g_err, sizeof g_err, "%s: %s", #x, hipGetErrorString(e_)); \
-      return -static_cast<int>(e_) - 1;                                        \
-    }                                                                          \
-  } while (0)
+#define XS_ERR_BUF g_err
 
 namespace {
 
-char g_err[512];
+xsprobe::ErrBuf g_err;
 
 using xsprobe::DevMem;
 using xsprobe::Event;
 using xsprobe::Stream;
+using xsprobe::hw_id;
+using xsprobe::xcc_id;
 
 constexpr int kBlock = 256;  // 4 waves of 64 lanes
 
@@ -185,18 +180,6 @@ __global__ __launch_bounds__(kBlock) void k_triad(f32x4* __restrict__ a, const f
   for (; i < n; i += stride) st<NT>(ld<NT>(&b[i]) + s * ld<NT>(&c[i]), &a[i]);
 }
 
-__device__ __forceinline__ uint32_t xcc_id() {
-  uint32_t v;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
-  return v & 0xf;
-}
-
-__device__ __forceinline__ uint32_t hw_cu_id() {
-  uint32_t v;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(v));
-  return v;
-}
-
 // XCD-pinned streaming: workgroups off the selected XCDs exit at once. The
 // selected XCDs split the buffer into equal contiguous slices (by their rank
 // in xcd_mask) and the workgroups of each XCD pull 256 KiB chunks of their
@@ -286,7 +269,7 @@ __global__ __launch_bounds__(kBlock) void k_pinned_fold(const vec4* __restrict__
 __global__ __launch_bounds__(64) void k_census(uint32_t* __restrict__ xcd_of_block, uint32_t* __restrict__ hwid_of_block) {
   if (threadIdx.x == 0) {
     xcd_of_block[blockIdx.x] = xcc_id();
-    hwid_of_block[blockIdx.x] = hw_cu_id();
+    hwid_of_block[blockIdx.x] = hw_id();
   }
 }
 

@@ -70,24 +70,19 @@
 #include <cstring>
 #include <vector>
 
-#include "hip/device_raii.h"
+#include "hip/sweep_common.h"
 
-#define XS_HCHECK(x)                                                                 \
-  do {                                                                               \
-    hipError_t e_ = (x);                                                             \
-    if (e_ != hipSuccess) {                                                          \
-      std::snprintf(g_hbm_err, sizeof g_hbm_err, "%s: %s", #x, hipGetErrorString(e_)); \
-      return -static_cast<int>(e_) - 1;                                              \
-    }                                                                                \
-  } while (0)
+#define XS_ERR_BUF g_hbm_err
 
 namespace {
 
-char g_hbm_err[512];
+xsprobe::ErrBuf g_hbm_err;
 
 using xsprobe::DevMem;
 using xsprobe::Event;
 using xsprobe::Stream;
+using xsprobe::kBadArgs;
+using xsprobe::xcc_id;
 
 typedef uint32_t vec4 __attribute__((ext_vector_type(4)));  // 16 B/lane
 
@@ -101,7 +96,6 @@ constexpr int kMaxBadChunks = 64;     // per-chunk counts reported (sparse); the
 constexpr size_t kMaxChunks = 1 << 16;
 constexpr size_t kDefaultChunk = size_t{1} << 30;
 constexpr size_t kReserve = size_t{2} << 30;  // left free when the budget is "all free HBM"
-constexpr int kBadArgs = -1000;
 constexpr int kBadBuffer = -1001;
 constexpr int kUnswept = -1003;       // no chunk could be allocated: nothing was tested
 constexpr uint64_t kNoInject = ~uint64_t{0};
@@ -190,12 +184,6 @@ struct LanePattern {
   }
 };
 
-__device__ __forceinline__ uint32_t hbm_xcc_id() {
-  uint32_t v;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
-  return v & 0xf;
-}
-
 __global__ __launch_bounds__(kBlock) void k_hbm_fill(vec4* __restrict__ buf, size_t n, uint64_t first_vec,
                                                      uint32_t seed) {
   const size_t stride = static_cast<size_t>(gridDim.x) * kBlock;
@@ -213,7 +201,7 @@ __device__ __forceinline__ void hbm_report(HbmSweepResult* __restrict__ r, uint6
   const vec4 d = e ^ a;
   const uint32_t down = __popc(d.x & e.x) + __popc(d.y & e.y) + __popc(d.z & e.z) + __popc(d.w & e.w);
   const uint32_t up = __popc(d.x & ~e.x) + __popc(d.y & ~e.y) + __popc(d.z & ~e.z) + __popc(d.w & ~e.w);
-  const uint32_t xcd = hbm_xcc_id();
+  const uint32_t xcd = xcc_id();
   atomicAdd(&r->bad_vectors, 1ull);
   atomicAdd(&r->bad_bits, static_cast<unsigned long long>(down + up));
   atomicAdd(&r->one_to_zero, static_cast<unsigned long long>(down));
@@ -333,17 +321,17 @@ int xs_hbm_sweep_op(int dev, int pass, void* buf, size_t bytes, uint64_t first_v
       (pass != 0 && !result))
     return kBadArgs;
   if (!buf || (reinterpret_cast<uintptr_t>(buf) & (sizeof(vec4) - 1))) return kBadBuffer;
-  XS_HCHECK(hipSetDevice(dev));
+  XS_CHECK(hipSetDevice(dev));
   if (grid == 0) grid = production_grid(dev);
   DevMem res;
   if (pass != 0) {
-    XS_HCHECK(hipMalloc(&res.p, sizeof(HbmSweepResult)));
-    XS_HCHECK(hipMemset(res.p, 0, sizeof(HbmSweepResult)));
+    XS_CHECK(hipMalloc(&res.p, sizeof(HbmSweepResult)));
+    XS_CHECK(hipMemset(res.p, 0, sizeof(HbmSweepResult)));
   }
   launch_pass(pass, grid, nullptr, buf, bytes / sizeof(vec4), first_vec, seed, res.as<HbmSweepResult>());
-  XS_HCHECK(hipGetLastError());
-  XS_HCHECK(hipDeviceSynchronize());
-  if (pass != 0) XS_HCHECK(hipMemcpy(result, res.p, sizeof(HbmSweepResult), hipMemcpyDeviceToHost));
+  XS_CHECK(hipGetLastError());
+  XS_CHECK(hipDeviceSynchronize());
+  if (pass != 0) XS_CHECK(hipMemcpy(result, res.p, sizeof(HbmSweepResult), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -366,10 +354,10 @@ int xs_hbm_sweep(int dev, size_t bytes, size_t chunk_bytes, uint32_t seed, uint6
   if (chunk_bytes % sizeof(vec4) != 0) return kBadArgs;
   const bool inject = inject_vec != kNoInject;
   if (inject && (inject_word < 0 || inject_word > 3 || inject_after_pass < 0 || inject_after_pass > 1)) return kBadArgs;
-  XS_HCHECK(hipSetDevice(dev));
+  XS_CHECK(hipSetDevice(dev));
   if (bytes == 0) {
     size_t free_b = 0, total_b = 0;
-    XS_HCHECK(hipMemGetInfo(&free_b, &total_b));
+    XS_CHECK(hipMemGetInfo(&free_b, &total_b));
     if (free_b <= kReserve + sizeof(vec4)) {
       std::snprintf(g_hbm_err, sizeof g_hbm_err, "unswept: %zu bytes free, the reserve is %zu", free_b, kReserve);
       return kUnswept;
@@ -410,35 +398,35 @@ int xs_hbm_sweep(int dev, size_t bytes, size_t chunk_bytes, uint32_t seed, uint6
   // One result per (chunk, verify pass): [2c] pass 1, [2c + 1] pass 2.
   DevMem res;
   const size_t res_bytes = 2 * got * sizeof(HbmSweepResult);
-  XS_HCHECK(hipMalloc(&res.p, res_bytes));
-  XS_HCHECK(hipMemset(res.p, 0, res_bytes));
+  XS_CHECK(hipMalloc(&res.p, res_bytes));
+  XS_CHECK(hipMemset(res.p, 0, res_bytes));
   const int grid = production_grid(dev);
   Stream s;
-  XS_HCHECK(hipStreamCreateWithFlags(&s.s, hipStreamNonBlocking));
+  XS_CHECK(hipStreamCreateWithFlags(&s.s, hipStreamNonBlocking));
   Event ev[6];
-  for (auto& e : ev) XS_HCHECK(hipEventCreate(&e.e));
-  XS_HCHECK(hipDeviceSynchronize());  // the memset above, before work on a non-blocking stream
+  for (auto& e : ev) XS_CHECK(hipEventCreate(&e.e));
+  XS_CHECK(hipDeviceSynchronize());  // the memset above, before work on a non-blocking stream
   for (int pass = 0; pass < 3; ++pass) {
-    XS_HCHECK(hipEventRecord(ev[2 * pass].e, s.s));
+    XS_CHECK(hipEventRecord(ev[2 * pass].e, s.s));
     for (size_t c = 0; c < got; ++c) {
       HbmSweepResult* r = pass == 0 ? nullptr : res.as<HbmSweepResult>() + 2 * c + (pass - 1);
       launch_pass(pass, grid, s.s, chunk[c].p, nvec[c], c * chunk_vecs, seed, r);
     }
-    XS_HCHECK(hipGetLastError());
-    XS_HCHECK(hipEventRecord(ev[2 * pass + 1].e, s.s));
-    XS_HCHECK(hipEventSynchronize(ev[2 * pass + 1].e));
+    XS_CHECK(hipGetLastError());
+    XS_CHECK(hipEventRecord(ev[2 * pass + 1].e, s.s));
+    XS_CHECK(hipEventSynchronize(ev[2 * pass + 1].e));
     if (inject && pass == inject_after_pass) {
       // The 8 aligned bytes that hold the word: read, flip, write back.
       char* at = chunk[inj_chunk].as<char>() + inj_off * sizeof(vec4) + (inject_word & ~1) * sizeof(uint32_t);
       uint32_t pair[2];
-      XS_HCHECK(hipMemcpy(pair, at, sizeof pair, hipMemcpyDeviceToHost));
+      XS_CHECK(hipMemcpy(pair, at, sizeof pair, hipMemcpyDeviceToHost));
       pair[inject_word & 1] ^= inject_mask;
-      XS_HCHECK(hipMemcpy(at, pair, sizeof pair, hipMemcpyHostToDevice));
+      XS_CHECK(hipMemcpy(at, pair, sizeof pair, hipMemcpyHostToDevice));
     }
   }
 
   std::vector<HbmSweepResult> h(2 * got);
-  XS_HCHECK(hipMemcpy(h.data(), res.p, res_bytes, hipMemcpyDeviceToHost));
+  XS_CHECK(hipMemcpy(h.data(), res.p, res_bytes, hipMemcpyDeviceToHost));
   HbmSweepSummary out;
   std::memset(&out, 0, sizeof out);
   out.bytes_requested = bytes;
@@ -472,7 +460,7 @@ int xs_hbm_sweep(int dev, size_t bytes, size_t chunk_bytes, uint32_t seed, uint6
   }
   for (int pass = 0; pass < 3; ++pass) {
     float ms = 0.f;
-    XS_HCHECK(hipEventElapsedTime(&ms, ev[2 * pass].e, ev[2 * pass + 1].e));
+    XS_CHECK(hipEventElapsedTime(&ms, ev[2 * pass].e, ev[2 * pass + 1].e));
     out.ms[pass] = ms;
   }
   std::memcpy(summary, &out, sizeof out);

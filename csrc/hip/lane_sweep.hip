@@ -169,30 +169,20 @@
 #include <utility>
 #include <vector>
 
-#include "hip/device_raii.h"
+#include "hip/sweep_common.h"
 
-#define XS_CHECK(x)                                                                      \
-  do {                                                                                   \
-    hipError_t e_ = (x);                                                                 \
-    if (e_ != hipSuccess) {                                                              \
-      std::snprintf(g_lane_err, sizeof g_lane_err, "%s: %s", #x, hipGetErrorString(e_)); \
-      return -static_cast<int>(e_) - 1;                                                  \
-    }                                                                                    \
-  } while (0)
-
+#define XS_ERR_BUF g_lane_err
 #define XS_HD __host__ __device__ __forceinline__
 #define XS_D __device__ __forceinline__
 
 namespace {
 
-char g_lane_err[512];
+xsprobe::ErrBuf g_lane_err;
 
-using xsprobe::DevMem;
-using xsprobe::Event;
+using namespace xsprobe;
 
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 enum Path : int { kDpp, kPermlane, kReadlane, kBpermute, kLdsWide, kLdsTr, kLdsAtomic, kLdsDma, kNumPaths };
 const char kPathNames[] = "dpp,permlane,readlane,bpermute,ldswide,ldstr,ldsatomic,ldsdma";
@@ -203,11 +193,7 @@ struct Shape {
 };
 constexpr Shape kShape[kNumPaths] = {{75, 1}, {4, 2}, {133, 1}, {137, 1}, {112, 4}, {32, 2}, {13, 4}, {6, 4}};
 
-constexpr int kBlock = 256;                  // 4 waves: one per SIMD
-constexpr size_t kLdsPerCu = 160u << 10;     // LDS of one gfx950 CU
-constexpr size_t kLdsExclusive = 96u << 10;  // > half a CU's LDS: one sweep workgroup per CU
-constexpr int kMaxBlocks = 1 << 20;
-constexpr int kBadArgs = -1000;
+constexpr int kBlock = 256;  // 4 waves: one per SIMD
 
 // LDS layout in bytes from the start of the allocation.
 constexpr uint32_t kRedWords = 2 * kNumPaths + 2;            // per thread: bad[8], digest[8], bad simd, simd
@@ -798,29 +784,17 @@ XS_D void run_paths(const Ctx& c, uint32_t mask, uint32_t* lds, const uint32_t* 
   if (mask & (1u << kLdsDma)) run_ldsdma(c, y[kLdsDma], lds, dma_src);
 }
 
-__device__ __forceinline__ uint32_t lane_xcc_id() {
-  uint32_t v;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
-  return v & 0xf;
-}
-__device__ __forceinline__ uint32_t lane_hw_id() {
-  uint32_t v;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(v));
-  return v;
-}
-
 __global__ __launch_bounds__(kBlock) void k_lane_sweep(LaneRecord* __restrict__ records,
                                                       const uint32_t* __restrict__ dma_src, uint32_t path_mask,
                                                       uint32_t seed, int inject_xcd, int inject_cu,
                                                       uint32_t inject_paths, Expect expect) {
   extern __shared__ uint32_t lane_lds[];
   const uint32_t t = threadIdx.x;
-  const uint32_t xcd = lane_xcc_id();
-  const uint32_t hw = lane_hw_id();
-  const uint32_t cu = (hw >> 8) & 0xffu;
-  const uint32_t simd = (hw >> 4) & 0x3u;
-  const bool inject = inject_xcd >= 0 && xcd == static_cast<uint32_t>(inject_xcd) &&
-                      (inject_cu < 0 || cu == static_cast<uint32_t>(inject_cu));
+  const uint32_t xcd = xcc_id();
+  const uint32_t hw = hw_id();
+  const uint32_t cu = cu_key(hw);
+  const uint32_t simd = simd_id(hw);
+  const bool inject = inject_selected(inject_xcd, inject_cu, xcd, cu);
   const Ctx c{seed, t, t & 63u, t >> 6, inject ? inject_paths : 0u, nullptr};
 
   Tally y[kNumPaths];
@@ -909,16 +883,6 @@ void expected(uint32_t path_mask, uint32_t seed, Expect* e) {
 
 bool bad_mask(uint32_t m) { return m == 0 || (m & ~kAllPaths); }
 
-int lds_bytes(int dev, size_t* out) {
-  hipDeviceProp_t p;
-  XS_CHECK(hipGetDeviceProperties(&p, dev));
-  const size_t lds_max =
-      std::min(std::max<size_t>(p.sharedMemPerBlock, p.maxSharedMemoryPerMultiProcessor), kLdsPerCu) & ~size_t{1023};
-  // More than half a CU's LDS, though less is used: sweep workgroups never share a CU.
-  *out = std::min(kLdsExclusive, lds_max);
-  return 0;
-}
-
 // The LDS-DMA source: [step][wave][64][4] of src(ldsdma, step, word, lane).
 int fill_dma_source(uint32_t seed, DevMem& buf) {
   std::vector<uint32_t> g(kDmaWords);
@@ -955,8 +919,7 @@ int xs_lane_probe(int dev, int path, uint32_t seed, uint32_t* out, size_t n_word
   if (n_words != n) return kBadArgs;
   XS_CHECK(hipSetDevice(dev));
   size_t smem = 0;
-  if (int rc = lds_bytes(dev, &smem)) return rc;
-  if (smem < kLdsUsed) return kBadArgs;
+  if (int rc = exclusive_lds(g_lane_err, dev, kLdsUsed, &smem)) return rc;
   XS_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_lane_probe), hipFuncAttributeMaxDynamicSharedMemorySize,
                                static_cast<int>(smem)));
   DevMem dma, dump;
@@ -988,18 +951,8 @@ int xs_lane_sweep_info(int dev, int* out4) {
   if (!out4) return kBadArgs;
   XS_CHECK(hipSetDevice(dev));
   size_t smem = 0;
-  if (int rc = lds_bytes(dev, &smem)) return rc;
-  XS_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_lane_sweep), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               static_cast<int>(smem)));
-  hipFuncAttributes a;
-  XS_CHECK(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(k_lane_sweep)));
-  int per_cu = 0;
-  XS_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_lane_sweep, kBlock, smem));
-  out4[0] = a.numRegs;
-  out4[1] = static_cast<int>(a.localSizeBytes);
-  out4[2] = static_cast<int>(smem);
-  out4[3] = per_cu;
-  return 0;
+  if (int rc = exclusive_lds(g_lane_err, dev, 0, &smem)) return rc;
+  return kernel_info(g_lane_err, reinterpret_cast<const void*>(k_lane_sweep), kBlock, smem, out4);
 }
 
 // One sweep launch of `blocks` workgroups (0: 4 per CU). Writes `blocks`
@@ -1008,41 +961,18 @@ int xs_lane_sweep_info(int dev, int* out4) {
 // arguments (nothing is launched), or a negative HIP error.
 int xs_lane_sweep(int dev, int blocks, uint32_t path_mask, uint32_t seed, int inject_xcd, int inject_cu,
                   uint32_t inject_paths, void* records_out, int* n_records, double* ms) {
-  if (bad_mask(path_mask) || (inject_paths & ~kAllPaths) || !records_out) return kBadArgs;
-  if (inject_xcd < -1 || inject_xcd > 15 || inject_cu < -1 || inject_cu > 0xff) return kBadArgs;
-  if (blocks < 0 || blocks > kMaxBlocks) return kBadArgs;
+  if (bad_mask(path_mask) || (inject_paths & ~kAllPaths)) return kBadArgs;
   Expect e;
   expected(path_mask, seed, &e);
-  XS_CHECK(hipSetDevice(dev));
-  hipDeviceProp_t p;
-  XS_CHECK(hipGetDeviceProperties(&p, dev));
-  if (blocks == 0) blocks = 4 * p.multiProcessorCount;
-  if (blocks <= 0 || blocks > kMaxBlocks) return kBadArgs;
-  size_t smem = 0;
-  if (int rc = lds_bytes(dev, &smem)) return rc;
-  if (smem < kLdsUsed) return kBadArgs;
-  XS_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_lane_sweep), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               static_cast<int>(smem)));
-  DevMem rec, dma;
-  if (int rc = fill_dma_source(seed, dma)) return rc;
-  const size_t bytes = static_cast<size_t>(blocks) * sizeof(LaneRecord);
-  XS_CHECK(hipMalloc(&rec.p, bytes));
-  XS_CHECK(hipMemset(rec.p, 0xff, bytes));
-  Event e0, e1;
-  XS_CHECK(hipEventCreate(&e0.e));
-  XS_CHECK(hipEventCreate(&e1.e));
-  XS_CHECK(hipEventRecord(e0.e, 0));
-  hipLaunchKernelGGL(k_lane_sweep, dim3(blocks), dim3(kBlock), smem, 0, rec.as<LaneRecord>(), dma.as<const uint32_t>(),
-                     path_mask, seed, inject_xcd, inject_cu, inject_paths, e);
-  XS_CHECK(hipGetLastError());
-  XS_CHECK(hipEventRecord(e1.e, 0));
-  XS_CHECK(hipEventSynchronize(e1.e));
-  float t = 0.f;
-  XS_CHECK(hipEventElapsedTime(&t, e0.e, e1.e));
-  XS_CHECK(hipMemcpy(records_out, rec.p, bytes, hipMemcpyDeviceToHost));
-  if (n_records) *n_records = blocks;
-  if (ms) *ms = t;
-  return 0;
+  DevMem dma;
+  return launch_sweep(
+      g_lane_err, {dev, blocks, inject_xcd, inject_cu, records_out, n_records, ms},
+      reinterpret_cast<const void*>(k_lane_sweep), kBlock, kLdsUsed, sizeof(LaneRecord),
+      [&](dim3 grid, dim3 block, size_t smem, void* rec) {
+        hipLaunchKernelGGL(k_lane_sweep, grid, block, smem, 0, static_cast<LaneRecord*>(rec), dma.as<const uint32_t>(),
+                           path_mask, seed, inject_xcd, inject_cu, inject_paths, e);
+      },
+      [&] { return fill_dma_source(seed, dma); });
 }
 
 }  // extern "C"

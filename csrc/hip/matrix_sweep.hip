@@ -87,25 +87,16 @@
 #include <type_traits>
 #include <vector>
 
-#include "hip/device_raii.h"
+#include "hip/sweep_common.h"
 
-#define XS_XCHECK(x)                                                                         \
-  do {                                                                                       \
-    hipError_t e_ = (x);                                                                     \
-    if (e_ != hipSuccess) {                                                                  \
-      std::snprintf(g_matrix_err, sizeof g_matrix_err, "%s: %s", #x, hipGetErrorString(e_)); \
-      return -static_cast<int>(e_) - 1;                                                      \
-    }                                                                                        \
-  } while (0)
-
+#define XS_ERR_BUF g_matrix_err
 #define XS_HD __host__ __device__ __forceinline__
 
 namespace {
 
-char g_matrix_err[512];
+xsprobe::ErrBuf g_matrix_err;
 
-using xsprobe::DevMem;
-using xsprobe::Event;
+using namespace xsprobe;
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef uint16_t u16x8 __attribute__((ext_vector_type(8)));
@@ -114,7 +105,6 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef int i32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 enum Fmt : int { kF16, kF32, kF64, kFp8, kBf8, kI8, kMxFp8, kMxBf8, kMxFp6, kMxBf6, kMxFp4, kNumFmt };
 const char kFmtNames[] = "f16,f32,f64,fp8,bf8,i8,mxfp8,mxbf8,mxfp6,mxbf6,mxfp4";
@@ -156,11 +146,8 @@ constexpr int kScaleLo = 125, kScaleSpan = 5;  // E8M0 codes 125..129: 2^-2 .. 2
 // wrong byte select or an A/B swap changes the result.
 constexpr int kOpselA = 2, kOpselB = 1, kDecoy = 120;
 
-constexpr int kBlock = 256;                  // 4 waves: one per SIMD
-constexpr size_t kLdsPerCu = 160u << 10;     // LDS of one gfx950 CU
-constexpr size_t kLdsExclusive = 96u << 10;  // > half a CU's LDS: one sweep workgroup per CU
-constexpr int kMaxBlocks = 1 << 20;
-constexpr int kBadArgs = -1000;
+constexpr int kBlock = 256;          // 4 waves: one per SIMD
+constexpr size_t kLdsUsed = 64 * 4;  // the four waves combine through 16 words each
 constexpr int kBoundBroken = -1001;  // a generator left its stated bound (a bug in this file)
 
 struct MatrixRecord {
@@ -394,17 +381,6 @@ __device__ __forceinline__ int32_t to_fixed(T x, uint32_t& lossy) {
   }
 }
 
-__device__ __forceinline__ uint32_t wsum(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ uint32_t wor(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
-  return v;
-}
-
 template <int F>
 __device__ __forceinline__ void sweep_formats(uint32_t mask, uint32_t inj, int lane, const Expect& expect,
                                               uint32_t (&digest)[kNumFmt], uint32_t& fail) {
@@ -419,22 +395,11 @@ __device__ __forceinline__ void sweep_formats(uint32_t mask, uint32_t inj, int l
         if (((inj >> F) & 1u) && lane == 0 && q == 0) f ^= 1;
         part += static_cast<uint32_t>(f) * (2u * static_cast<uint32_t>(tile_pos<F>(lane, q)) + 1u);
       }
-      digest[F] = wsum(part);
-      if (wor(lossy) || digest[F] != expect.wave[F]) fail |= 1u << F;
+      digest[F] = wave_sum(part);
+      if (wave_or(lossy) || digest[F] != expect.wave[F]) fail |= 1u << F;
     }
     sweep_formats<F + 1>(mask, inj, lane, expect, digest, fail);
   }
-}
-
-__device__ __forceinline__ uint32_t matrix_xcc_id() {
-  uint32_t v;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
-  return v & 0xf;
-}
-__device__ __forceinline__ uint32_t matrix_hw_id() {
-  uint32_t v;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(v));
-  return v;
 }
 
 __global__ __launch_bounds__(kBlock) void k_matrix_sweep(MatrixRecord* __restrict__ records, uint32_t format_mask,
@@ -442,12 +407,11 @@ __global__ __launch_bounds__(kBlock) void k_matrix_sweep(MatrixRecord* __restric
                                                         Expect expect) {
   extern __shared__ uint32_t matrix_lds[];
   const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const uint32_t xcd = matrix_xcc_id();
-  const uint32_t hw = matrix_hw_id();
-  const uint32_t cu = (hw >> 8) & 0xffu;
-  const uint32_t simd = (hw >> 4) & 0x3u;
-  const bool inject = inject_xcd >= 0 && xcd == static_cast<uint32_t>(inject_xcd) &&
-                      (inject_cu < 0 || cu == static_cast<uint32_t>(inject_cu));
+  const uint32_t xcd = xcc_id();
+  const uint32_t hw = hw_id();
+  const uint32_t cu = cu_key(hw);
+  const uint32_t simd = simd_id(hw);
+  const bool inject = inject_selected(inject_xcd, inject_cu, xcd, cu);
   const uint32_t inj = inject && wave == 0 ? inject_formats : 0u;
 
   uint32_t digest[kNumFmt];
@@ -634,15 +598,15 @@ int xs_matrix_tile(int dev, int fmt, double* out) {
   if (fmt < 0 || fmt >= kNumFmt || !out) return kBadArgs;
   const Desc& d = kDesc[fmt];
   const size_t n = static_cast<size_t>(d.tile) * d.tile;
-  XS_XCHECK(hipSetDevice(dev));
+  XS_CHECK(hipSetDevice(dev));
   DevMem buf;
-  XS_XCHECK(hipMalloc(&buf.p, n * 8));
-  XS_XCHECK(hipMemset(buf.p, 0xff, n * 8));
+  XS_CHECK(hipMalloc(&buf.p, n * 8));
+  XS_CHECK(hipMemset(buf.p, 0xff, n * 8));
   with_format(fmt, [&](auto F) { hipLaunchKernelGGL(k_matrix_tile<decltype(F)::value>, dim3(1), dim3(64), 0, 0, buf.p); });
-  XS_XCHECK(hipGetLastError());
-  XS_XCHECK(hipDeviceSynchronize());
+  XS_CHECK(hipGetLastError());
+  XS_CHECK(hipDeviceSynchronize());
   std::vector<uint64_t> raw(n);
-  XS_XCHECK(hipMemcpy(raw.data(), buf.p, n * 8, hipMemcpyDeviceToHost));
+  XS_CHECK(hipMemcpy(raw.data(), buf.p, n * 8, hipMemcpyDeviceToHost));
   for (size_t p = 0; p < n; ++p) {
     if (d.acc == kAccF64)
       out[p] = reinterpret_cast<const double*>(raw.data())[p];
@@ -667,46 +631,20 @@ int xs_matrix_sweep_expected(uint32_t format_mask, uint32_t* out) {
   return 0;
 }
 
-// One sweep launch of `blocks` workgroups. Writes `blocks` 64-byte records to
-// records_out. Returns 0, -1000 for bad arguments (nothing is launched), or a
-// negative HIP error.
+// One sweep launch of `blocks` workgroups; 0 is refused, not taken as "4 per
+// CU". Writes `blocks` 64-byte records to records_out. Returns 0, -1000 for
+// bad arguments (nothing is launched), or a negative HIP error.
 int xs_matrix_sweep(int dev, int blocks, uint32_t format_mask, int inject_xcd, int inject_cu, uint32_t inject_formats,
                     void* records_out, int* n_records, double* ms) {
-  if (bad_mask(format_mask) || (inject_formats & ~kAllFormats) || !records_out) return kBadArgs;
-  if (inject_xcd < -1 || inject_xcd > 15 || inject_cu < -1 || inject_cu > 0xff) return kBadArgs;
-  if (blocks <= 0 || blocks > kMaxBlocks) return kBadArgs;
+  if (bad_mask(format_mask) || (inject_formats & ~kAllFormats) || blocks == 0) return kBadArgs;
   Expect e;
   if (int rc = expected(format_mask, &e)) return rc;
-  XS_XCHECK(hipSetDevice(dev));
-  hipDeviceProp_t p;
-  XS_XCHECK(hipGetDeviceProperties(&p, dev));
-  const size_t lds_max =
-      std::min(std::max<size_t>(p.sharedMemPerBlock, p.maxSharedMemoryPerMultiProcessor), kLdsPerCu) & ~size_t{1023};
-  // More than half a CU's LDS, though only 64 words are used: sweep
-  // workgroups never share a CU.
-  const size_t smem = std::min(kLdsExclusive, lds_max);
-  if (smem < 64 * sizeof(uint32_t)) return kBadArgs;
-  XS_XCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_matrix_sweep),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem)));
-  DevMem rec;
-  const size_t bytes = static_cast<size_t>(blocks) * sizeof(MatrixRecord);
-  XS_XCHECK(hipMalloc(&rec.p, bytes));
-  XS_XCHECK(hipMemset(rec.p, 0xff, bytes));
-  Event e0, e1;
-  XS_XCHECK(hipEventCreate(&e0.e));
-  XS_XCHECK(hipEventCreate(&e1.e));
-  XS_XCHECK(hipEventRecord(e0.e, 0));
-  hipLaunchKernelGGL(k_matrix_sweep, dim3(blocks), dim3(kBlock), smem, 0, rec.as<MatrixRecord>(), format_mask,
-                     inject_xcd, inject_cu, inject_formats, e);
-  XS_XCHECK(hipGetLastError());
-  XS_XCHECK(hipEventRecord(e1.e, 0));
-  XS_XCHECK(hipEventSynchronize(e1.e));
-  float t = 0.f;
-  XS_XCHECK(hipEventElapsedTime(&t, e0.e, e1.e));
-  XS_XCHECK(hipMemcpy(records_out, rec.p, bytes, hipMemcpyDeviceToHost));
-  if (n_records) *n_records = blocks;
-  if (ms) *ms = t;
-  return 0;
+  return launch_sweep(g_matrix_err, {dev, blocks, inject_xcd, inject_cu, records_out, n_records, ms},
+                      reinterpret_cast<const void*>(k_matrix_sweep), kBlock, kLdsUsed, sizeof(MatrixRecord),
+                      [&](dim3 grid, dim3 block, size_t smem, void* rec) {
+                        hipLaunchKernelGGL(k_matrix_sweep, grid, block, smem, 0, static_cast<MatrixRecord*>(rec),
+                                           format_mask, inject_xcd, inject_cu, inject_formats, e);
+                      });
 }
 
 }  // extern "C"

@@ -39,32 +39,23 @@
 #include <cstring>
 #include <vector>
 
-#include "hip/device_raii.h"
+#define XS_ERR_RC(e) (-1)  // this file's ABI: every HIP error is -1
+#include "hip/sweep_common.h"
+
+#define XS_ERR_BUF g_mfma_err
 
 namespace {
 
-char g_mfma_err[512];
+xsprobe::ErrBuf g_mfma_err;
 
-#define XS_MCHECK(x)                                                                    \
-  do {                                                                                  \
-    hipError_t e_ = (x);                                                                \
-    if (e_ != hipSuccess) {                                                             \
-      std::snprintf(g_mfma_err, sizeof g_mfma_err, "%s: %s", #x, hipGetErrorString(e_)); \
-      return -1;                                                                        \
-    }                                                                                   \
-  } while (0)
+using xsprobe::kBadArgs;
+using xsprobe::xcc_id;
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kPeakBlock = 256;  // 4 waves: one per SIMD
 constexpr int kAcc = 4;          // independent accumulators per wave
-
-__device__ __forceinline__ uint32_t xcc_id() {
-  uint32_t v;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
-  return v & 0xf;
-}
 
 __global__ __launch_bounds__(64) void k_mfma_tile(const __bf16* __restrict__ A, const __bf16* __restrict__ B,
                                                   float* __restrict__ C, int K) {
@@ -88,7 +79,6 @@ constexpr int kCounterStride = 32;          // unsigned per XCD counter: one 128
 constexpr int kMaxTileK = 4096;             // xs_mfma_tile_op: A and B of 256 KiB each
 constexpr int kMaxCheckedBlocks = 4096;     // xs_mfma_peak_op: 64 KiB of accumulators per workgroup
 constexpr uint32_t kDidNotRun = 0x80000000u;  // xcd_of_block flag of a workgroup that exited
-constexpr int kBadArgs = -1000;
 constexpr int kIdleXcd = -1002;
 
 // One counter per XCD (thread 0 of a workgroup that runs adds 1 to its XCD's),
@@ -163,7 +153,7 @@ inline bool mask_ok(uint32_t xcd_mask) { return xcd_mask != 0 && !(xcd_mask & ~0
 // Reads the eight per-XCD counters of one completed launch into per_xcd.
 int fetch_counters(const unsigned* d_active, unsigned per_xcd[kMaxXcds]) {
   unsigned h[kMaxXcds * kCounterStride];
-  XS_MCHECK(hipMemcpy(h, d_active, sizeof h, hipMemcpyDeviceToHost));
+  XS_CHECK(hipMemcpy(h, d_active, sizeof h, hipMemcpyDeviceToHost));
   for (int x = 0; x < kMaxXcds; ++x) per_xcd[x] = h[x * kCounterStride];
   return 0;
 }
@@ -185,19 +175,19 @@ int xs_mfma_max_k() { return kMaxTileK; }
 int xs_mfma_tile_op(int dev, const uint16_t* a_bits, const uint16_t* b_bits, int K, float* c_out) {
   if (!tile_k_ok(K)) return kBadArgs;
   if (!a_bits || !b_bits || !c_out) return -1001;
-  XS_MCHECK(hipSetDevice(dev));
+  XS_CHECK(hipSetDevice(dev));
   const size_t ab = static_cast<size_t>(32) * K * sizeof(uint16_t);
   xsprobe::DevMem da, db, dc;
-  XS_MCHECK(hipMalloc(&da.p, ab));
-  XS_MCHECK(hipMalloc(&db.p, ab));
-  XS_MCHECK(hipMalloc(&dc.p, 32 * 32 * sizeof(float)));
-  XS_MCHECK(hipMemcpy(da.p, a_bits, ab, hipMemcpyHostToDevice));
-  XS_MCHECK(hipMemcpy(db.p, b_bits, ab, hipMemcpyHostToDevice));
-  XS_MCHECK(hipMemset(dc.p, 0xff, 32 * 32 * sizeof(float)));
+  XS_CHECK(hipMalloc(&da.p, ab));
+  XS_CHECK(hipMalloc(&db.p, ab));
+  XS_CHECK(hipMalloc(&dc.p, 32 * 32 * sizeof(float)));
+  XS_CHECK(hipMemcpy(da.p, a_bits, ab, hipMemcpyHostToDevice));
+  XS_CHECK(hipMemcpy(db.p, b_bits, ab, hipMemcpyHostToDevice));
+  XS_CHECK(hipMemset(dc.p, 0xff, 32 * 32 * sizeof(float)));
   hipLaunchKernelGGL(k_mfma_tile, dim3(1), dim3(64), 0, 0, da.as<const __bf16>(), db.as<const __bf16>(),
                      dc.as<float>(), K);
-  XS_MCHECK(hipGetLastError());
-  XS_MCHECK(hipMemcpy(c_out, dc.p, 32 * 32 * sizeof(float), hipMemcpyDeviceToHost));
+  XS_CHECK(hipGetLastError());
+  XS_CHECK(hipMemcpy(c_out, dc.p, 32 * 32 * sizeof(float), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -257,27 +247,27 @@ int xs_mfma_peak_op(int dev, int iters, uint32_t xcd_mask, int blocks, float* ac
                     unsigned* active_per_xcd_out) {
   if (!mask_ok(xcd_mask) || iters <= 0 || blocks < 0 || blocks > kMaxCheckedBlocks) return kBadArgs;
   if (!acc_out || !xcd_of_block_out || !active_per_xcd_out) return -1001;
-  XS_MCHECK(hipSetDevice(dev));
+  XS_CHECK(hipSetDevice(dev));
   hipDeviceProp_t p;
-  XS_MCHECK(hipGetDeviceProperties(&p, dev));
+  XS_CHECK(hipGetDeviceProperties(&p, dev));
   if (blocks == 0) blocks = 8 * p.multiProcessorCount;
   if (blocks > kMaxCheckedBlocks) return kBadArgs;
   const size_t acc_bytes = static_cast<size_t>(blocks) * kPeakBlock * kAcc * 16 * sizeof(float);
   const size_t xcd_bytes = static_cast<size_t>(blocks) * sizeof(uint32_t);
   xsprobe::DevMem active_mem, acc_mem, xcd_mem;
-  XS_MCHECK(hipMalloc(&active_mem.p, sizeof(unsigned) * kMaxXcds * kCounterStride));
-  XS_MCHECK(hipMalloc(&acc_mem.p, acc_bytes));
-  XS_MCHECK(hipMalloc(&xcd_mem.p, xcd_bytes));
-  XS_MCHECK(hipMemset(active_mem.p, 0, sizeof(unsigned) * kMaxXcds * kCounterStride));
-  XS_MCHECK(hipMemset(acc_mem.p, 0xff, acc_bytes));
-  XS_MCHECK(hipMemset(xcd_mem.p, 0xff, xcd_bytes));
+  XS_CHECK(hipMalloc(&active_mem.p, sizeof(unsigned) * kMaxXcds * kCounterStride));
+  XS_CHECK(hipMalloc(&acc_mem.p, acc_bytes));
+  XS_CHECK(hipMalloc(&xcd_mem.p, xcd_bytes));
+  XS_CHECK(hipMemset(active_mem.p, 0, sizeof(unsigned) * kMaxXcds * kCounterStride));
+  XS_CHECK(hipMemset(acc_mem.p, 0xff, acc_bytes));
+  XS_CHECK(hipMemset(xcd_mem.p, 0xff, xcd_bytes));
   hipLaunchKernelGGL(k_mfma_peak<true>, dim3(blocks), dim3(kPeakBlock), 0, 0, iters, xcd_mask,
                      active_mem.as<unsigned>(), static_cast<float*>(nullptr), acc_mem.as<float>(),
                      xcd_mem.as<uint32_t>());
-  XS_MCHECK(hipGetLastError());
-  XS_MCHECK(hipDeviceSynchronize());
-  XS_MCHECK(hipMemcpy(acc_out, acc_mem.p, acc_bytes, hipMemcpyDeviceToHost));
-  XS_MCHECK(hipMemcpy(xcd_of_block_out, xcd_mem.p, xcd_bytes, hipMemcpyDeviceToHost));
+  XS_CHECK(hipGetLastError());
+  XS_CHECK(hipDeviceSynchronize());
+  XS_CHECK(hipMemcpy(acc_out, acc_mem.p, acc_bytes, hipMemcpyDeviceToHost));
+  XS_CHECK(hipMemcpy(xcd_of_block_out, xcd_mem.p, xcd_bytes, hipMemcpyDeviceToHost));
   return fetch_counters(active_mem.as<unsigned>(), active_per_xcd_out);
 }
 
@@ -296,23 +286,23 @@ int xs_mfma_peak_op(int dev, int iters, uint32_t xcd_mask, int blocks, float* ac
 int xs_mfma_peak(int dev, int iters, uint32_t xcd_mask, int blocks, double* tflops, double* ms_out,
                  int* active_blocks, unsigned* active_per_xcd, double* flops_out) {
   if (!mask_ok(xcd_mask)) return kBadArgs;
-  XS_MCHECK(hipSetDevice(dev));
+  XS_CHECK(hipSetDevice(dev));
   hipDeviceProp_t p;
-  XS_MCHECK(hipGetDeviceProperties(&p, dev));
+  XS_CHECK(hipGetDeviceProperties(&p, dev));
   if (blocks <= 0) blocks = 8 * p.multiProcessorCount;
   if (iters <= 0) iters = 4096;
   xsprobe::DevMem active_mem, sink_mem;
   const size_t ctr_bytes = sizeof(unsigned) * kMaxXcds * kCounterStride;
-  XS_MCHECK(hipMalloc(&active_mem.p, ctr_bytes));
-  XS_MCHECK(hipMalloc(&sink_mem.p, blocks * sizeof(float)));
+  XS_CHECK(hipMalloc(&active_mem.p, ctr_bytes));
+  XS_CHECK(hipMalloc(&sink_mem.p, blocks * sizeof(float)));
   unsigned* d_active = active_mem.as<unsigned>();
   float* d_sink = sink_mem.as<float>();
   xsprobe::Stream stream;
-  XS_MCHECK(hipStreamCreate(&stream.s));
+  XS_CHECK(hipStreamCreate(&stream.s));
   hipStream_t s = stream.s;
   xsprobe::Event ev0, ev1;
-  XS_MCHECK(hipEventCreate(&ev0.e));
-  XS_MCHECK(hipEventCreate(&ev1.e));
+  XS_CHECK(hipEventCreate(&ev0.e));
+  XS_CHECK(hipEventCreate(&ev1.e));
   hipEvent_t e0 = ev0.e, e1 = ev1.e;
   auto go = [&] {
     hipLaunchKernelGGL(k_mfma_peak<false>, dim3(blocks), dim3(kPeakBlock), 0, s, iters, xcd_mask, d_active, d_sink,
@@ -323,26 +313,26 @@ int xs_mfma_peak(int dev, int iters, uint32_t xcd_mask, int blocks, double* tflo
   // (profiles/r4za_probe_warm_ab.jsonl). The HBM probes are memory-bound and
   // read the same with or without it (same file), so they keep their short one.
   float warm_ms = 0.f;
-  XS_MCHECK(hipMemsetAsync(d_active, 0, ctr_bytes, s));
-  XS_MCHECK(hipEventRecord(e0, s));
+  XS_CHECK(hipMemsetAsync(d_active, 0, ctr_bytes, s));
+  XS_CHECK(hipEventRecord(e0, s));
   go();
-  XS_MCHECK(hipGetLastError());
-  XS_MCHECK(hipEventRecord(e1, s));
-  XS_MCHECK(hipEventSynchronize(e1));
-  XS_MCHECK(hipEventElapsedTime(&warm_ms, e0, e1));
+  XS_CHECK(hipGetLastError());
+  XS_CHECK(hipEventRecord(e1, s));
+  XS_CHECK(hipEventSynchronize(e1));
+  XS_CHECK(hipEventElapsedTime(&warm_ms, e0, e1));
   const char* env = std::getenv("XS_PROBE_WARM_MS");  // as the HBM probes; 0 = one launch
   const float target = env ? static_cast<float>(std::atof(env)) : 20.f;
   const int warm = target <= 0.f ? 0 : warm_ms > 0.f ? std::min(64, static_cast<int>(target / warm_ms) + 1) : 4;
   for (int w = 0; w < warm; ++w) go();
-  XS_MCHECK(hipGetLastError());
-  XS_MCHECK(hipMemsetAsync(d_active, 0, ctr_bytes, s));
-  XS_MCHECK(hipEventRecord(e0, s));
+  XS_CHECK(hipGetLastError());
+  XS_CHECK(hipMemsetAsync(d_active, 0, ctr_bytes, s));
+  XS_CHECK(hipEventRecord(e0, s));
   go();
-  XS_MCHECK(hipGetLastError());
-  XS_MCHECK(hipEventRecord(e1, s));
-  XS_MCHECK(hipEventSynchronize(e1));
+  XS_CHECK(hipGetLastError());
+  XS_CHECK(hipEventRecord(e1, s));
+  XS_CHECK(hipEventSynchronize(e1));
   float ms = 0.f;
-  XS_MCHECK(hipEventElapsedTime(&ms, e0, e1));
+  XS_CHECK(hipEventElapsedTime(&ms, e0, e1));
   unsigned per_xcd[kMaxXcds];
   if (int rc = fetch_counters(d_active, per_xcd)) return rc;
   unsigned active = 0;

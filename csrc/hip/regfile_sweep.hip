@@ -70,30 +70,18 @@
 #include <cstdint>
 #include <cstdio>
 
-#include "hip/device_raii.h"
+#include "hip/sweep_common.h"
 
-#define XS_CHECK(x)                                                                          \
-  do {                                                                                       \
-    hipError_t e_ = (x);                                                                     \
-    if (e_ != hipSuccess) {                                                                  \
-      std::snprintf(g_regfile_err, sizeof g_regfile_err, "%s: %s", #x, hipGetErrorString(e_)); \
-      return -static_cast<int>(e_) - 1;                                                      \
-    }                                                                                        \
-  } while (0)
+#define XS_ERR_BUF g_regfile_err
 
 namespace {
 
-char g_regfile_err[512];
+xsprobe::ErrBuf g_regfile_err;
 
-using xsprobe::DevMem;
-using xsprobe::Event;
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+using namespace xsprobe;
 
 constexpr int kBlock = 256;  // 4 waves: one per SIMD
 constexpr int kCells = 512;  // VGPR + AGPR entries per lane
-constexpr int kMaxBlocks = 1 << 20;
-constexpr int kBadArgs = -1000;
 constexpr uint32_t kNone = 0xffffffffu;
 
 enum : uint32_t { kFailVgpr = 1, kFailAgpr = 2 };
@@ -104,38 +92,6 @@ struct RegfileRecord {
   uint32_t digest, bad_simds, reserved[6];
 };
 static_assert(sizeof(RegfileRecord) == 64, "one 64-byte record per workgroup");
-
-__host__ __device__ __forceinline__ uint32_t rotl32(uint32_t x, int s) {
-  s &= 31;
-  return s ? (x << s) | (x >> (32 - s)) : x;
-}
-
-__device__ __forceinline__ uint32_t regfile_xcc_id() {
-  uint32_t v;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
-  return v & 0xf;
-}
-__device__ __forceinline__ uint32_t regfile_hw_id() {
-  uint32_t v;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(v));
-  return v;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_or(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, static_cast<uint32_t>(__shfl_xor(v, o, 64)));
-  return v;
-}
 
 // ---- the text of the statement ---------------------------------------------
 // Assembler symbols: xs_s = first scratch register of the phase, xs_n = the
@@ -224,12 +180,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1))) 
   // `wave` is an operand of the statement, which pins its readfirstlane ahead
   // of it (threadIdx.x would otherwise stay live in v0 and spill).
   uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint32_t xcd = regfile_xcc_id();
-  const uint32_t hw = regfile_hw_id();
-  const uint32_t cu = (hw >> 8) & 0xffu;
-  const uint32_t simd = (hw >> 4) & 0x3u;
-  const bool selected = inject_xcd >= 0 && xcd == static_cast<uint32_t>(inject_xcd) &&
-                        (inject_cu < 0 || cu == static_cast<uint32_t>(inject_cu));
+  const uint32_t xcd = xcc_id();
+  const uint32_t hw = hw_id();
+  const uint32_t cu = cu_key(hw);
+  const uint32_t simd = simd_id(hw);
+  const bool selected = inject_selected(inject_xcd, inject_cu, xcd, cu);
   const uint32_t injreg =
       __builtin_amdgcn_readfirstlane(selected && inject_reg >= 0 ? static_cast<uint32_t>(inject_reg) : kNone);
   const uint32_t injmask = __builtin_amdgcn_readfirstlane(1u << (inject_bit & 31));
@@ -344,15 +299,7 @@ int xs_regfile_sweep_expected(uint32_t seed, uint32_t* out) {
 int xs_regfile_sweep_info(int dev, int* out3) {
   if (!out3) return kBadArgs;
   XS_CHECK(hipSetDevice(dev));
-  hipFuncAttributes a;
-  XS_CHECK(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(k_regfile_sweep)));
-  int active = 0;
-  XS_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&active, reinterpret_cast<const void*>(k_regfile_sweep), kBlock,
-                                                        0));
-  out3[0] = a.numRegs;
-  out3[1] = static_cast<int>(a.localSizeBytes);
-  out3[2] = active;
-  return 0;
+  return kernel_info(g_regfile_err, reinterpret_cast<const void*>(k_regfile_sweep), kBlock, 0, out3);
 }
 
 // One sweep launch of `blocks` workgroups (0: 4 per CU). Writes `blocks`
@@ -362,35 +309,15 @@ int xs_regfile_sweep_info(int dev, int* out3) {
 // for bad arguments (nothing is launched), or a negative HIP error.
 int xs_regfile_sweep(int dev, int blocks, uint32_t seed, int inject_xcd, int inject_cu, int inject_reg, int inject_bit,
                      int poison_reg, void* records_out, int* n_records, double* ms) {
-  if (!records_out || blocks < 0 || blocks > kMaxBlocks) return kBadArgs;
-  if (inject_xcd < -1 || inject_xcd > 15 || inject_cu < -1 || inject_cu > 0xff) return kBadArgs;
   if (inject_reg < -1 || inject_reg >= kCells || inject_bit < 0 || inject_bit > 31) return kBadArgs;
   if (poison_reg < -1 || poison_reg > 255) return kBadArgs;
-  XS_CHECK(hipSetDevice(dev));
-  hipDeviceProp_t p;
-  XS_CHECK(hipGetDeviceProperties(&p, dev));
-  if (blocks == 0) blocks = 4 * p.multiProcessorCount;
-  if (blocks <= 0 || blocks > kMaxBlocks) return kBadArgs;
-  DevMem rec;
-  const size_t bytes = static_cast<size_t>(blocks) * sizeof(RegfileRecord);
-  XS_CHECK(hipMalloc(&rec.p, bytes));
-  XS_CHECK(hipMemset(rec.p, 0xff, bytes));
-  Event e0, e1;
-  XS_CHECK(hipEventCreate(&e0.e));
-  XS_CHECK(hipEventCreate(&e1.e));
   const uint32_t expect = expected_digest(seed);
-  XS_CHECK(hipEventRecord(e0.e, 0));
-  hipLaunchKernelGGL(k_regfile_sweep, dim3(blocks), dim3(kBlock), 0, 0, rec.as<RegfileRecord>(), seed, inject_xcd,
-                     inject_cu, inject_reg, inject_bit, poison_reg, expect);
-  XS_CHECK(hipGetLastError());
-  XS_CHECK(hipEventRecord(e1.e, 0));
-  XS_CHECK(hipEventSynchronize(e1.e));
-  float t = 0.f;
-  XS_CHECK(hipEventElapsedTime(&t, e0.e, e1.e));
-  XS_CHECK(hipMemcpy(records_out, rec.p, bytes, hipMemcpyDeviceToHost));
-  if (n_records) *n_records = blocks;
-  if (ms) *ms = t;
-  return 0;
+  return launch_sweep(g_regfile_err, {dev, blocks, inject_xcd, inject_cu, records_out, n_records, ms},
+                      reinterpret_cast<const void*>(k_regfile_sweep), kBlock, 0, sizeof(RegfileRecord),
+                      [&](dim3 grid, dim3 block, size_t smem, void* rec) {
+                        hipLaunchKernelGGL(k_regfile_sweep, grid, block, smem, 0, static_cast<RegfileRecord*>(rec), seed,
+                                           inject_xcd, inject_cu, inject_reg, inject_bit, poison_reg, expect);
+                      });
 }
 
 }  // extern "C"

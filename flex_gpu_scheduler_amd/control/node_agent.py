@@ -48,6 +48,37 @@ MEMORY_PARTITION_LABEL = "amd.com/gpu.memory-partition"
 HIVE_LABEL = "amd.com/xgmi.hive"
 
 
+@dataclass(frozen=True)
+class FaultKind:
+    """How one kind of fault in GpuHealth.detail travels to the topology
+    annotation, where it stands under the same key. `per_xcd`: the value is
+    {XCD id: list or dict} (int keys in the agent, strings in the annotation)
+    and an XCD's empty entry is dropped; otherwise it is one dict for the GPU.
+    `withholds_gpu`: a GPU that has one is withheld as a whole."""
+    per_xcd: bool
+    withholds_gpu: bool = False
+
+
+FAULT_KINDS = {
+    # The matrix formats a faulty XCD mis-computes (the matrix-format sweep):
+    # {xcd: [format, ...]}. Informational, as the next two are: the XCD is
+    # fenced through xcdFaults; these are for operators and RMA tooling.
+    "matrixFaults": FaultKind(per_xcd=True),
+    # What the register-file sweep found: {xcd: {"files", "cells", "flipMask", "simds"}}.
+    "registerFaults": FaultKind(per_xcd=True),
+    # The cross-lane and LDS paths a faulty XCD gets wrong (the lane sweep): {xcd: [path, ...]}.
+    "laneFaults": FaultKind(per_xcd=True),
+    # What the HBM sweep found on the GPU. The sweep knows a fault by its
+    # virtual address, which cannot be tied to the HBM slice of one compute
+    # partition, so there is no partial fence for memory.
+    "hbmFaults": FaultKind(per_xcd=False, withholds_gpu=True),
+}
+
+
+def _fault_value(v):
+    return dict(v) if isinstance(v, dict) else list(v)
+
+
 def _now() -> str:
     return datetime.now(timezone.utc).strftime("%Y-%m-%dT%H:%M:%SZ")
 
@@ -99,18 +130,9 @@ class NodeAgent:
         self.unhealthy: set[int] = set()
         # GPU index -> physical XCD ids a GpuHealth verdict named as bad.
         self.unhealthy_xcds: dict[int, set[int]] = {}
-        # GPU index -> {XCD id: matrix formats it mis-computes}, from
-        # GpuHealth.detail["matrixFaults"] (the matrix-format sweep).
-        self.matrix_faults: dict[int, dict[int, list[str]]] = {}
-        # GPU index -> {XCD id: {"files", "cells", "flipMask", "simds"}}, from
-        # GpuHealth.detail["registerFaults"] (the register-file sweep).
-        self.register_faults: dict[int, dict[int, dict]] = {}
-        # GPU index -> {XCD id: lane-sweep paths it gets wrong}, from
-        # GpuHealth.detail["laneFaults"] (the lane sweep).
-        self.lane_faults: dict[int, dict[int, list[str]]] = {}
-        # GPU index -> what the HBM sweep found wrong, from
-        # GpuHealth.detail["hbmFaults"]; such a GPU is withheld as a whole.
-        self.hbm_faults: dict[int, dict] = {}
+        # Annotation key of FAULT_KINDS -> {GPU index: that kind's value}, from
+        # the GpuHealth.detail of the last probe; {} for a kind with no fault.
+        self.faults: dict[str, dict[int, dict]] = {k: {} for k in FAULT_KINDS}
         self._stop = threading.Event()
         self._threads: list[threading.Thread] = []
         self.host: HostInfo | None = None
@@ -129,25 +151,16 @@ class NodeAgent:
         marks the XCDs of a partitioned one."""
         return self._probe_health(host)[:2]
 
-    def _probe_health(self, host: HostInfo) -> tuple[set[int], dict[int, set[int]], dict[int, dict[int, list[str]]],
-                                                     dict[int, dict], dict[int, dict[int, dict]],
-                                                     dict[int, dict[int, list[str]]]]:
-        """probe_health plus the matrix formats each bad XCD got wrong, the
-        HBM faults per GPU, what the register-file sweep found per bad XCD and
-        the lane-sweep paths each bad XCD got wrong.
+    def _probe_health(self, host: HostInfo) -> tuple[set[int], dict[int, set[int]], dict[str, dict[int, dict]]]:
+        """probe_health plus the faults of every kind of FAULT_KINDS per GPU.
 
-        An HBM fault (detail["hbmFaults"]) withholds the whole GPU, partitioned
-        or not, and even when the same verdict names bad XCDs: the sweep knows
-        a fault by its virtual address, which cannot be tied to the HBM slice
-        of one compute partition, so there is no partial fence for memory."""
+        A kind that withholds the GPU (an HBM fault) does so whether the GPU
+        is partitioned or not, and even when the same verdict names bad XCDs."""
+        faults: dict[str, dict[int, dict]] = {k: {} for k in FAULT_KINDS}
         if self.health_fn is None:
-            return set(), {}, {}, {}, {}, {}
+            return set(), {}, faults
         bad: set[int] = set()
         xcds: dict[int, set[int]] = {}
-        formats: dict[int, dict[int, list[str]]] = {}
-        hbm: dict[int, dict] = {}
-        registers: dict[int, dict[int, dict]] = {}
-        lanes: dict[int, dict[int, list[str]]] = {}
         # HIP ordinals follow the KFD node order of the GPUs this process can
         # open; GPUs whose KFD node is hidden (other containers' devices) are
         # not probed. With no KFD info at all (fake hosts) use the index.
@@ -156,30 +169,25 @@ class NodeAgent:
         for ordinal, g in targets:
             try:
                 r = self.health_fn(ordinal)
-                if isinstance(r, GpuHealth):
-                    mf = {int(x): list(f) for x, f in (r.detail.get("matrixFaults") or {}).items() if f}
-                    if mf:
-                        formats[g.index] = mf
-                    if r.detail.get("hbmFaults"):
-                        hbm[g.index] = dict(r.detail["hbmFaults"])
-                    rf = {int(x): dict(f) for x, f in (r.detail.get("registerFaults") or {}).items() if f}
-                    if rf:
-                        registers[g.index] = rf
-                    lf = {int(x): list(f) for x, f in (r.detail.get("laneFaults") or {}).items() if f}
-                    if lf:
-                        lanes[g.index] = lf
+                withheld = False
+                for key, kind in FAULT_KINDS.items() if isinstance(r, GpuHealth) else ():
+                    v = r.detail.get(key) or {}
+                    v = {int(x): _fault_value(f) for x, f in v.items() if f} if kind.per_xcd else dict(v)
+                    if v:
+                        faults[key][g.index] = v
+                        withheld |= kind.withholds_gpu
                 if isinstance(r, GpuHealth) and r.bad_xcds:
                     xcds[g.index] = set(r.bad_xcds)
-                    if g.partitions == 1 or g.index in hbm:
+                    if g.partitions == 1 or withheld:
                         bad.add(g.index)
-                elif g.index in hbm:
+                elif withheld:
                     bad.add(g.index)
                 elif not (r.ok if isinstance(r, GpuHealth) else r):
                     bad.add(g.index)
             except Exception as e:  # noqa: BLE001
                 log.warning("health probe GPU %d failed: %s", g.index, e)
                 bad.add(g.index)
-        return bad, xcds, formats, hbm, registers, lanes
+        return bad, xcds, faults
 
     @staticmethod
     def _fenced(gpus, xcd_faults) -> dict[int, tuple[int, int]]:
@@ -215,10 +223,7 @@ class NodeAgent:
 
     def build_node(self, host: HostInfo, unhealthy: set[int] = frozenset(),
                    xcd_faults: dict[int, set[int]] | None = None,
-                   matrix_faults: dict[int, dict[int, list[str]]] | None = None,
-                   hbm_faults: dict[int, dict] | None = None,
-                   register_faults: dict[int, dict[int, dict]] | None = None,
-                   lane_faults: dict[int, dict[int, list[str]]] | None = None) -> dict:
+                   faults: dict[str, dict[int, dict]] | None = None) -> dict:
         healthy = [g for g in host.gpus if g.index not in unhealthy]
         infos = [g.to_gpu_info() for g in healthy]
         mem_kib = max(0, host.memory_bytes // 1024 - self.reserved_memory_gib * (1 << 20))
@@ -242,34 +247,17 @@ class NodeAgent:
                          computePartition=g.compute_partition, xgmiLinks=len(g.xgmi_links),
                          xgmiLinkMBps=max((lk.bandwidth_mbps for lk in g.xgmi_links), default=0))
         topo["unhealthy"] = sorted(unhealthy)
-        faults = {str(i): sorted(x) for i, x in sorted((xcd_faults or {}).items()) if x}
-        if faults:
-            topo["xcdFaults"] = faults
-        # Which matrix formats each faulty XCD mis-computes: informational (the
-        # XCD is fenced through xcdFaults), for operators and RMA tooling.
-        formats = {str(i): {str(x): list(f) for x, f in sorted(per.items()) if f}
-                   for i, per in sorted((matrix_faults or {}).items())}
-        formats = {i: per for i, per in formats.items() if per}
-        if formats:
-            topo["matrixFaults"] = formats
-        # Which register files each faulty XCD reads back wrong: informational,
-        # as matrixFaults is.
-        regs = {str(i): {str(x): dict(f) for x, f in sorted(per.items()) if f}
-                for i, per in sorted((register_faults or {}).items())}
-        regs = {i: per for i, per in regs.items() if per}
-        if regs:
-            topo["registerFaults"] = regs
-        # Which cross-lane and LDS paths each faulty XCD gets wrong:
-        # informational, as matrixFaults is.
-        lanes = {str(i): {str(x): list(f) for x, f in sorted(per.items()) if f}
-                 for i, per in sorted((lane_faults or {}).items())}
-        lanes = {i: per for i, per in lanes.items() if per}
-        if lanes:
-            topo["laneFaults"] = lanes
-        # What the HBM sweep found on a GPU (which is withheld as a whole).
-        hbm = {str(i): dict(f) for i, f in sorted((hbm_faults or {}).items()) if f}
-        if hbm:
-            topo["hbmFaults"] = hbm
+        fenced_xcds = {str(i): sorted(x) for i, x in sorted((xcd_faults or {}).items()) if x}
+        if fenced_xcds:
+            topo["xcdFaults"] = fenced_xcds
+        for key, kind in FAULT_KINDS.items():
+            per_gpu = {}
+            for i, v in sorted((faults or {}).get(key, {}).items()):
+                v = {str(x): _fault_value(f) for x, f in sorted(v.items()) if f} if kind.per_xcd else dict(v)
+                if v:
+                    per_gpu[str(i)] = v
+            if per_gpu:
+                topo[key] = per_gpu
         node["metadata"]["annotations"][TOPOLOGY_ANNOTATION] = json.dumps(topo, sort_keys=True)
         if self.bandwidth:
             node["metadata"]["annotations"][BANDWIDTH_ANNOTATION] = json.dumps(
@@ -361,16 +349,13 @@ class NodeAgent:
 
     def sync(self) -> HostInfo:
         host = self.host_fn()
-        (self.unhealthy, self.unhealthy_xcds, self.matrix_faults, self.hbm_faults,
-         self.register_faults, self.lane_faults) = self._probe_health(host)
+        self.unhealthy, self.unhealthy_xcds, self.faults = self._probe_health(host)
         self.measure_bandwidth(host)
         for dp in self.device_plugins:
             dp.host = host
             dp.set_unhealthy(self.unhealthy)
             dp.set_unhealthy_xcds(self.unhealthy_xcds)
-        self._upsert("nodes", self.build_node(host, self.unhealthy, self.unhealthy_xcds, self.matrix_faults,
-                                              self.hbm_faults, self.register_faults, self.lane_faults),
-                     keep_spec=True)
+        self._upsert("nodes", self.build_node(host, self.unhealthy, self.unhealthy_xcds, self.faults), keep_spec=True)
         self._upsert("noderesourcetopologies", self.build_nrt(host, self.unhealthy, self.unhealthy_xcds),
                      keep_spec=False)
         self.host = host
@@ -411,11 +396,9 @@ class NodeAgent:
 
     def _heartbeat_and_resync(self) -> None:
         host = self.host_fn()
-        unhealthy, xcds, formats, hbm, registers, lanes = self._probe_health(host)
+        unhealthy, xcds, faults = self._probe_health(host)
         changed = (self.host is None or [g.to_gpu_info() for g in host.gpus] != [g.to_gpu_info() for g in self.host.gpus]
-                   or unhealthy != self.unhealthy or xcds != self.unhealthy_xcds or formats != self.matrix_faults
-                   or hbm != self.hbm_faults or registers != self.register_faults
-                   or lanes != self.lane_faults)
+                   or unhealthy != self.unhealthy or xcds != self.unhealthy_xcds or faults != self.faults)
         if changed:
             self.sync()
         else:
@@ -472,53 +455,44 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
     p = probe()
     last: dict[int, tuple[float, object]] = {}  # dev -> (monotonic time, sweep verdict)
 
+    def register_fault(v: dict) -> dict:
+        return {"files": list(v["failed_files"]), "cells": int(v["bad_cells"]), "flipMask": v["flip_mask"],
+                "simds": sum(len(sm) for sm in v["bad_simds"].values())} if v["failed_files"] else {}
+
+    # In the order they run: enabled, the probe's method, its keywords, the
+    # fault of one XCD from its entry of the summary (empty: none; None: the
+    # sweep publishes no fault kind), the label of the log line, and the keys
+    # of the verdict's detail for the summary and for {xcd: fault}.
+    per_cu_sweeps = [
+        (sweep, "cu_sweep", dict(sweep_args or {}), None, "cu", "sweep", None),
+        (matrix, "matrix_sweep", dict(formats=matrix_formats, **(matrix_args or {})),
+         lambda v: list(v["failed_formats"]), "matrix", "matrixSweep", "matrixFaults"),
+        (regfile, "regfile_sweep", dict(regfile_args or {}), register_fault, "register", "registerSweep",
+         "registerFaults"),
+        (lane, "lane_sweep", dict(paths=lane_paths, **(lane_args or {})),
+         lambda v: list(v["failed_paths"]), "lane", "laneSweep", "laneFaults"),
+    ]
+
     def sweep_verdict(dev: int):
         now = time.monotonic()
         if dev in last and now - last[dev][0] < sweep_period_s:
             return last[dev][1]
         bad: set[int] = set()
         detail: dict = {}
-        if sweep:
-            s = p.cu_sweep(dev, **(sweep_args or {}))["summary"]
+        for on, run, keywords, fault_of, label, summary_key, faults_key in per_cu_sweeps:
+            if not on:
+                continue
+            s = getattr(p, run)(dev, **keywords)["summary"]
+            # The cu sweep names no fault kind: its log line shows the bad XCDs.
+            found = {int(x): fault_of(v) for x, v in s["xcds"].items() if fault_of(v)} if fault_of else s["bad_xcds"]
             log.log(logging.WARNING if s["bad_xcds"] else logging.INFO,
-                    "cu sweep GPU %d: %d CUs on %d XCDs in %.2f ms (%d launch(es)), covered=%s uncovered=%s "
-                    "bad_xcds=%s", dev, s["cus_seen"], len(s["xcds"]), s["ms"], s["rounds"], s["covered"],
-                    {x: n for x, n in s["uncovered"].items() if n}, s["bad_xcds"])
+                    "%s sweep GPU %d: %d CUs on %d XCDs in %.2f ms (%d launch(es)), covered=%s uncovered=%s "
+                    "%s=%s", label, dev, s["cus_seen"], len(s["xcds"]), s["ms"], s["rounds"], s["covered"],
+                    {x: n for x, n in s["uncovered"].items() if n}, "bad_xcds" if fault_of is None else "faults", found)
             bad |= set(s["bad_xcds"])
-            detail["sweep"] = s
-        if matrix:
-            m = p.matrix_sweep(dev, formats=matrix_formats, **(matrix_args or {}))["summary"]
-            faults = {int(x): list(v["failed_formats"]) for x, v in m["xcds"].items() if v["failed_formats"]}
-            log.log(logging.WARNING if m["bad_xcds"] else logging.INFO,
-                    "matrix sweep GPU %d: %d CUs on %d XCDs in %.2f ms (%d launch(es)), covered=%s uncovered=%s "
-                    "faults=%s", dev, m["cus_seen"], len(m["xcds"]), m["ms"], m["rounds"], m["covered"],
-                    {x: n for x, n in m["uncovered"].items() if n}, faults)
-            bad |= set(m["bad_xcds"])
-            detail["matrixSweep"] = m
-            detail["matrixFaults"] = faults
-        if regfile:
-            g = p.regfile_sweep(dev, **(regfile_args or {}))["summary"]
-            reg_faults = {int(x): {"files": list(v["failed_files"]), "cells": int(v["bad_cells"]),
-                                   "flipMask": v["flip_mask"],
-                                   "simds": sum(len(sm) for sm in v["bad_simds"].values())}
-                          for x, v in g["xcds"].items() if v["failed_files"]}
-            log.log(logging.WARNING if g["bad_xcds"] else logging.INFO,
-                    "register sweep GPU %d: %d CUs on %d XCDs in %.2f ms (%d launch(es)), covered=%s uncovered=%s "
-                    "faults=%s", dev, g["cus_seen"], len(g["xcds"]), g["ms"], g["rounds"], g["covered"],
-                    {x: n for x, n in g["uncovered"].items() if n}, reg_faults)
-            bad |= set(g["bad_xcds"])
-            detail["registerSweep"] = g
-            detail["registerFaults"] = reg_faults
-        if lane:
-            n = p.lane_sweep(dev, paths=lane_paths, **(lane_args or {}))["summary"]
-            lane_faults = {int(x): list(v["failed_paths"]) for x, v in n["xcds"].items() if v["failed_paths"]}
-            log.log(logging.WARNING if n["bad_xcds"] else logging.INFO,
-                    "lane sweep GPU %d: %d CUs on %d XCDs in %.2f ms (%d launch(es)), covered=%s uncovered=%s "
-                    "faults=%s", dev, n["cus_seen"], len(n["xcds"]), n["ms"], n["rounds"], n["covered"],
-                    {x: u for x, u in n["uncovered"].items() if u}, lane_faults)
-            bad |= set(n["bad_xcds"])
-            detail["laneSweep"] = n
-            detail["laneFaults"] = lane_faults
+            detail[summary_key] = s
+            if faults_key:
+                detail[faults_key] = found
         hbm_faults: dict = {}
         if hbm:
             h = None

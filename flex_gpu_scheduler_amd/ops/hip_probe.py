@@ -22,6 +22,7 @@ from __future__ import annotations
 
 import ctypes
 import json
+import struct
 from dataclasses import dataclass
 from pathlib import Path
 
@@ -43,6 +44,7 @@ MFMA_IDLE_XCD = -1002
 MFMA_PEAK_BLOCK = 256  # threads per k_mfma_peak workgroup: 4 waves
 MFMA_PEAK_ACC = 4  # independent 32x32 accumulators per wave
 MFMA_DID_NOT_RUN = 1 << 31  # xs_mfma_peak_op: flag of a workgroup that exited
+MFMA_WORDING = {-1001: "null buffer"}  # return codes _probe_error words itself
 
 
 @dataclass
@@ -67,7 +69,6 @@ DEFAULT_BYTES = 1 << 30
 # k_cu_sweep (csrc/hip/cu_sweep.hip)
 SWEEP_ENGINES = {1: "mfma", 2: "valu", 4: "lds"}  # fail bit -> digest of that engine
 SWEEP_LDS_MAX = 160 << 10
-SWEEP_BAD_ARGS = -1000
 
 # k_matrix_sweep (csrc/hip/matrix_sweep.hip): one 64-byte record per workgroup,
 # {xcd, cu, simd_mask, fail, one digest per format, 0}.
@@ -94,6 +95,7 @@ HBM_SWEEP_LOG_CAP = 32
 HBM_SWEEP_STRIPES = 16
 HBM_SWEEP_BAD_CHUNKS = 64
 HBM_BAD_BUFFER = -1001
+HBM_WORDING = {HBM_BAD_BUFFER: "null or mis-aligned buffer"}  # return codes _probe_error words itself
 # xs_hbm_sweep could not allocate even its first chunk: nothing was tested.
 # The GPU is unswept, never failed.
 HBM_UNSWEPT = -1003
@@ -142,6 +144,36 @@ assert ctypes.sizeof(_HbmSweepSummary) == 144 + 16 * HBM_SWEEP_BAD_CHUNKS
 def _hbm_log(entries) -> list[dict]:
     return [{"v": int(e.v), "expected": [int(w) for w in e.expected], "actual": [int(w) for w in e.actual],
              "xcd": int(e.xcd), "pass": int(e.pass_)} for e in entries]
+
+
+def _probe_error(last_error, rc: int, what: str, wording: dict | None = None) -> ProbeError:
+    """The ProbeError of return code `rc` of `what`. `last_error` is the
+    xs_*_last_error of the file that returned it, asked only for a code that
+    neither BAD_ARGS nor `wording` ({rc: text}) puts into words."""
+    detail = {BAD_ARGS: "bad arguments", **(wording or {})}.get(rc)
+    if detail is None:
+        detail = last_error().decode(errors="replace")
+    e = ProbeError(f"{what} failed ({rc}): {detail}")
+    e.rc = rc
+    return e
+
+
+def _name_mask(names: list[str], chosen, what: str) -> int:
+    """The bits of `chosen` (one name, several, or None for all) in `names`' order."""
+    if chosen is None:
+        return (1 << len(names)) - 1
+    mask = 0
+    for f in [chosen] if isinstance(chosen, str) else chosen:
+        if f not in names:
+            raise ValueError(f"unknown {what} {f!r}; known: {', '.join(names)}")
+        mask |= 1 << names.index(f)
+    return mask
+
+
+def _inject_target(t: tuple | None) -> tuple[int, int]:
+    """(xcd, cu key) of an `inject` / `poison` tuple as the C ABI takes them:
+    -1 for no XCD (no tuple) and for every CU of the XCD (None)."""
+    return (-1, -1) if t is None else (int(t[0]), -1 if t[1] is None else int(t[1]))
 
 
 class HipProbe:
@@ -244,12 +276,6 @@ class HipProbe:
         L.xs_hbm_sweep.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint64,
                                    ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
 
-    def _err(self, rc: int, what: str) -> ProbeError:
-        detail = "bad arguments" if rc == BAD_ARGS else self.lib.xs_last_error().decode(errors="replace")
-        e = ProbeError(f"{what} failed ({rc}): {detail}")
-        e.rc = rc
-        return e
-
     def device_count(self) -> int:
         return int(self.lib.xs_device_count())
 
@@ -257,7 +283,7 @@ class HipProbe:
         buf = ctypes.create_string_buffer(4096)
         rc = self.lib.xs_device_props(dev, buf, len(buf))
         if rc < 0:
-            raise self._err(rc, "device_props")
+            raise _probe_error(self.lib.xs_last_error, rc, "device_props")
         return json.loads(buf.value.decode())
 
     def hbm_bandwidth(self, dev: int = 0, nbytes: int = DEFAULT_BYTES, iters: int = 20, cu_limit: int = 0,
@@ -267,7 +293,7 @@ class HipProbe:
         rc = self.lib.xs_hbm_bandwidth_d(dev, nbytes, iters, cu_limit, MODES[mode], variant, ctypes.byref(g),
                                          ctypes.byref(ms), d)
         if rc != 0:
-            raise self._err(rc, "hbm_bandwidth")
+            raise _probe_error(self.lib.xs_last_error, rc, "hbm_bandwidth")
         return Bandwidth(mode, nbytes, g.value, ms.value, cu_limit, d[0], d[1])
 
     @staticmethod
@@ -317,7 +343,7 @@ class HipProbe:
                 variant: int = 0, grid: int = 0, fold=None) -> None:
         rc = self.lib.xs_stream_op_g(dev, mode, a, b, c, nbytes, seed, scale, variant, grid, fold)
         if rc != 0:
-            raise self._err(rc, "stream_op")
+            raise _probe_error(self.lib.xs_last_error, rc, "stream_op")
 
     def read_fold(self, src, variant: int = 0, grid: int = 0) -> tuple[int, int]:
         """k_read, checked instantiation: (XOR of every 32-bit word of `src`,
@@ -368,7 +394,7 @@ class HipProbe:
         rc = self.lib.xs_pinned_op_g(dst.device.index or 0, 2 if src is not None else 1, ps or None, pd, n, xcd_mask,
                                      grid, None)
         if rc != 0:
-            raise self._err(rc, "pinned_op")
+            raise _probe_error(self.lib.xs_last_error, rc, "pinned_op")
 
     def pinned_read_fold(self, src, xcd_mask: int = 0x1, grid: int = 0) -> tuple[int, int]:
         """k_pinned's read mode, checked instantiation: (XOR of every 32-bit
@@ -377,7 +403,7 @@ class HipProbe:
         fold = (ctypes.c_ulonglong * 2)()
         rc = self.lib.xs_pinned_op_g(src.device.index or 0, 0, ps, None, n, xcd_mask, grid, fold)
         if rc != 0:
-            raise self._err(rc, "pinned_op")
+            raise _probe_error(self.lib.xs_last_error, rc, "pinned_op")
         return int(fold[0]), int(fold[1])
 
     def checksum(self, buf) -> int:
@@ -391,7 +417,7 @@ class HipProbe:
         out = ctypes.c_ulonglong()
         rc = self.lib.xs_checksum_op(buf.device.index or 0, buf.data_ptr(), nbytes, ctypes.byref(out))
         if rc != 0:
-            raise self._err(rc, "checksum_op")
+            raise _probe_error(self.lib.xs_last_error, rc, "checksum_op")
         return int(out.value)
 
     def segment_op(self, buf, mode: str = "read", seg_bytes: int = 128, stride_bytes: int = 4096, touches: int = 1,
@@ -407,7 +433,7 @@ class HipProbe:
         rc = self.lib.xs_segment_op(buf.device.index or 0, MODES[mode], int(nontemporal), seg_bytes, stride_bytes,
                                     touches, p, fold)
         if rc != 0:
-            raise self._err(rc, "segment_op")
+            raise _probe_error(self.lib.xs_last_error, rc, "segment_op")
         return (int(fold[0]), int(fold[1])) if fold is not None else None
 
     def hbm_bandwidth_xcd(self, dev: int = 0, xcd_mask: int = 0x1, nbytes: int = DEFAULT_BYTES, iters: int = 10,
@@ -417,7 +443,7 @@ class HipProbe:
         rc = self.lib.xs_hbm_bandwidth_xcd_d(dev, nbytes, iters, xcd_mask, MODES[mode], ctypes.byref(g),
                                              ctypes.byref(ms), d)
         if rc != 0:
-            raise self._err(rc, "hbm_bandwidth_xcd")
+            raise _probe_error(self.lib.xs_last_error, rc, "hbm_bandwidth_xcd")
         return Bandwidth(mode, nbytes, g.value, ms.value, bin(xcd_mask).count("1") * 32, d[0], d[1])
 
     def partition_table(self, dev: int = 0, nbytes: int = DEFAULT_BYTES, iters: int = 10) -> dict:
@@ -463,7 +489,7 @@ class HipProbe:
         rc = self.lib.xs_segment_access(dev, MODES[mode], int(nontemporal), seg_bytes, stride_bytes, touches, iters,
                                         out)
         if rc != 0:
-            raise self._err(rc, "segment_access")
+            raise _probe_error(self.lib.xs_last_error, rc, "segment_access")
         return {"kernel": "k_segments", "mode": mode, "nontemporal": nontemporal, "seg_bytes": seg_bytes,
                 "stride_bytes": stride_bytes, "touches": touches, "ms": round(out[0], 4),
                 "bytes_per_dispatch": int(out[1]), "lines128_per_dispatch": int(out[2])}
@@ -473,14 +499,14 @@ class HipProbe:
         cus = ctypes.c_int()
         rc = self.lib.xs_xcd_census(dev, blocks, hist, ctypes.byref(cus))
         if rc < 0:
-            raise self._err(rc, "xcd_census")
+            raise _probe_error(self.lib.xs_last_error, rc, "xcd_census")
         return {"distinct_xcds": rc, "blocks_per_xcd": list(hist), "distinct_cu_slots": cus.value}
 
     def health(self, dev: int = 0, nbytes: int = 64 << 20) -> dict:
         d, h = ctypes.c_ulonglong(), ctypes.c_ulonglong()
         rc = self.lib.xs_health_check(dev, nbytes, ctypes.byref(d), ctypes.byref(h))
         if rc < 0:
-            raise self._err(rc, "health_check")
+            raise _probe_error(self.lib.xs_last_error, rc, "health_check")
         return {"healthy": rc == 0, "device_sum": d.value, "host_sum": h.value}
 
 
@@ -490,7 +516,7 @@ class HipProbe:
         p, n = self._dev_buf(buf, "buf", granular=False)
         rc = self.lib.xs_pattern_op(buf.device.index or 0, p, n)
         if rc != 0:
-            raise self._err(rc, "pattern_op")
+            raise _probe_error(self.lib.xs_last_error, rc, "pattern_op")
 
     def health_verify(self, buf) -> dict:
         """The health check's verdict over a device tensor: k_checksum's sum
@@ -499,16 +525,8 @@ class HipProbe:
         d, h = ctypes.c_ulonglong(), ctypes.c_ulonglong()
         rc = self.lib.xs_health_verify(buf.device.index or 0, p, n, ctypes.byref(d), ctypes.byref(h))
         if rc < 0:
-            raise self._err(rc, "health_verify")
+            raise _probe_error(self.lib.xs_last_error, rc, "health_verify")
         return {"healthy": rc == 0, "device_sum": d.value, "host_sum": h.value}
-
-    def _mfma_err(self, rc: int, what: str) -> ProbeError:
-        detail = {BAD_ARGS: "bad arguments", -1001: "null buffer"}.get(rc)
-        if detail is None:
-            detail = self.lib.xs_mfma_last_error().decode(errors="replace")
-        e = ProbeError(f"{what} failed ({rc}): {detail}")
-        e.rc = rc
-        return e
 
     def mfma_check(self, dev: int = 0, k: int = 64) -> dict:
         """C[32x32] = A·B through v_mfma_f32_32x32x16_bf16 on exact integers.
@@ -516,7 +534,7 @@ class HipProbe:
         rc BAD_ARGS otherwise)."""
         rc = self.lib.xs_mfma_check(dev, k)
         if rc < 0:
-            raise self._mfma_err(rc, "mfma_check")
+            raise _probe_error(self.lib.xs_mfma_last_error, rc, "mfma_check", MFMA_WORDING)
         return {"healthy": rc == 0, "mismatches": int(rc), "k": k}
 
     def mfma_max_k(self) -> int:
@@ -529,7 +547,7 @@ class HipProbe:
         a, b = np.zeros((32, max(k, 0)), np.int32), np.zeros((max(k, 0), 32), np.int32)
         rc = self.lib.xs_mfma_inputs(k, a.ctypes.data, b.ctypes.data)
         if rc != 0:
-            raise self._mfma_err(rc, "mfma_inputs")
+            raise _probe_error(self.lib.xs_mfma_last_error, rc, "mfma_inputs", MFMA_WORDING)
         return a, b
 
     def mfma_compare(self, k: int, c, cap: int = 32) -> tuple[int, list[int]]:
@@ -544,7 +562,7 @@ class HipProbe:
         idx = np.full(max(cap, 1), -1, np.int32)
         rc = self.lib.xs_mfma_compare(k, c.ctypes.data, idx.ctypes.data, cap)
         if rc < 0:
-            raise self._mfma_err(rc, "mfma_compare")
+            raise _probe_error(self.lib.xs_mfma_last_error, rc, "mfma_compare", MFMA_WORDING)
         return int(rc), [int(i) for i in idx[:min(rc, cap)]]
 
     def mfma_tile(self, a_bits, b_bits, dev: int = 0):
@@ -561,7 +579,7 @@ class HipProbe:
         c = np.zeros((32, 32), np.float32)
         rc = self.lib.xs_mfma_tile_op(dev, a.ctypes.data, b.ctypes.data, a.shape[1], c.ctypes.data)
         if rc != 0:
-            raise self._mfma_err(rc, "mfma_tile_op")
+            raise _probe_error(self.lib.xs_mfma_last_error, rc, "mfma_tile_op", MFMA_WORDING)
         return c
 
     def mfma_peak_op(self, dev: int = 0, xcd_mask: int = 0xFF, iters: int = 1, blocks: int = 0) -> dict:
@@ -577,7 +595,7 @@ class HipProbe:
         per = (ctypes.c_uint * 8)()
         rc = self.lib.xs_mfma_peak_op(dev, iters, xcd_mask, n, acc.ctypes.data, xcd.ctypes.data, per)
         if rc != 0:
-            raise self._mfma_err(rc, "mfma_peak_op")
+            raise _probe_error(self.lib.xs_mfma_last_error, rc, "mfma_peak_op", MFMA_WORDING)
         return {"acc": acc, "xcd": (xcd & 0xF).astype(np.int64), "ran": (xcd & MFMA_DID_NOT_RUN) == 0,
                 "raw_xcd": xcd, "active_per_xcd": [int(v) for v in per], "iters": iters, "xcd_mask": xcd_mask}
 
@@ -591,10 +609,50 @@ class HipProbe:
         rc = self.lib.xs_mfma_peak(dev, iters, xcd_mask, blocks, ctypes.byref(tf), ctypes.byref(ms), ctypes.byref(act),
                                    per, ctypes.byref(fl))
         if rc != 0:
-            raise self._mfma_err(rc, "mfma_peak")
+            raise _probe_error(self.lib.xs_mfma_last_error, rc, "mfma_peak", MFMA_WORDING)
         return {"tflops": tf.value, "ms": ms.value, "active_blocks": act.value, "xcd_mask": xcd_mask,
                 "active_per_xcd": [int(v) for v in per], "flops": fl.value, "iters": iters if iters > 0 else 4096}
 
+
+    # ------------------------------------------------------ the per-CU sweeps
+    def _sweep_until_covered(self, name: str, dev: int, blocks: int, max_rounds: int, words: int, launch, expected,
+                             decode, summarize) -> dict:
+        """The launch policy of every per-CU sweep. A launch whose grid could
+        cover the device (`blocks` 0 = 4 per CU) is repeated while some CU has
+        not been seen, at most `max_rounds` launches in all; records accumulate.
+
+        `launch(blocks, buf, n, ms)` calls xs_<name> into `buf` (`words` uint32
+        per record) and returns its code; `expected()` is the host's digests,
+        asked for once, after the first launch; `decode(w, expected)` makes the
+        record of one workgroup's words, failing it where a digest differs
+        from the host's even if the device-side comparator (on the same CU)
+        passed it; `summarize(records, compute_units)` is the verdict.
+        Returns {"records", "summary": the verdict plus rounds, ms, blocks}."""
+        cus = int(self.props(dev)["computeUnits"])
+        n_blocks = blocks if blocks != 0 else 4 * cus
+        want = None
+        records: list[dict] = []
+        total_ms, rounds = 0.0, 0
+        summary: dict = {}
+        for _ in range(max(1, max_rounds if n_blocks >= cus else 1)):
+            buf = (ctypes.c_uint32 * (words * max(1, n_blocks)))()
+            n, ms = ctypes.c_int(), ctypes.c_double()
+            rc = launch(n_blocks, buf, ctypes.byref(n), ctypes.byref(ms))
+            if rc != 0:
+                raise _probe_error(getattr(self.lib, f"xs_{name}_last_error"), rc, name)
+            if want is None:
+                want = expected()
+            rounds += 1
+            total_ms += ms.value
+            # struct splits the buffer into one tuple of words per record far
+            # faster than slicing the ctypes array does.
+            rows = struct.iter_unpack(f"{words}I", bytes(buf)[:4 * words * n.value])
+            records += [decode(w, want) for w in rows]
+            summary = summarize(records, cus)
+            if summary["covered"]:
+                break
+        summary.update(rounds=rounds, ms=total_ms, blocks=n_blocks)
+        return {"records": records, "summary": summary}
 
     # ------------------------------------------------------------- CU sweep
     def cu_sweep_max_lds(self, dev: int = 0) -> int:
@@ -609,7 +667,7 @@ class HipProbe:
         out = (ctypes.c_uint32 * 3)()
         rc = self.lib.xs_cu_sweep_expected(k, lds_bytes, out)
         if rc != 0:
-            raise _sweep_error(self, rc, "cu_sweep_expected")
+            raise _probe_error(self.lib.xs_cu_sweep_last_error, rc, "cu_sweep_expected")
         return {"mfma": out[0], "valu": out[1], "lds": out[2]}
 
     def cu_sweep(self, dev: int = 0, blocks: int = 0, k: int = 64, lds_bytes: int | None = None,
@@ -623,43 +681,23 @@ class HipProbe:
         repeated while some CU has not been seen, at most `max_rounds`
         launches in all; records accumulate. Returns {"records": [...],
         "summary": summarize_sweep(...) plus rounds, ms, blocks}."""
-        props = self.props(dev)
-        cus = int(props["computeUnits"])
         if lds_bytes is None:
             lds_bytes = self.cu_sweep_max_lds(dev)
-        n_blocks = blocks if blocks != 0 else 4 * cus
-        ix, ic, ie = -1, -1, 0
-        if inject is not None:
-            ix, ic, ie = int(inject[0]), -1 if inject[1] is None else int(inject[1]), int(inject[2])
-        expected = None
-        records: list[dict] = []
-        total_ms, rounds = 0.0, 0
-        summary: dict = {}
-        for _ in range(max(1, max_rounds if n_blocks >= cus else 1)):
-            buf = (ctypes.c_uint32 * (8 * max(1, n_blocks)))()
-            n, ms = ctypes.c_int(), ctypes.c_double()
-            rc = self.lib.xs_cu_sweep(dev, n_blocks, k, lds_bytes, ix, ic, ie, buf, ctypes.byref(n), ctypes.byref(ms))
-            if rc != 0:
-                raise _sweep_error(self, rc, "cu_sweep")
-            if expected is None:
-                expected = self.cu_sweep_expected(k, lds_bytes)
-            rounds += 1
-            total_ms += ms.value
-            for i in range(n.value):
-                w = buf[8 * i:8 * i + 8]
-                rec = {"xcd": w[0], "cu": w[1], "simd_mask": w[2], "fail": w[3], "mfma": w[4], "valu": w[5],
-                       "lds": w[6]}
-                # A digest that differs from the host's is a failure even if
-                # the device-side comparator (on the same CU) passed it.
-                for bit, name in SWEEP_ENGINES.items():
-                    if rec[name] != expected[name]:
-                        rec["fail"] |= bit
-                records.append(rec)
-            summary = summarize_sweep(records, cus)
-            if summary["covered"]:
-                break
-        summary.update(rounds=rounds, ms=total_ms, blocks=n_blocks, k=k, lds_bytes=lds_bytes)
-        return {"records": records, "summary": summary}
+        (ix, ic), ie = _inject_target(inject), 0 if inject is None else int(inject[2])
+
+        def decode(w, expected):
+            rec = {"xcd": w[0], "cu": w[1], "simd_mask": w[2], "fail": w[3], "mfma": w[4], "valu": w[5], "lds": w[6]}
+            for bit, name in SWEEP_ENGINES.items():
+                if rec[name] != expected[name]:
+                    rec["fail"] |= bit
+            return rec
+
+        out = self._sweep_until_covered(
+            "cu_sweep", dev, blocks, max_rounds, 8,
+            lambda nb, *out: self.lib.xs_cu_sweep(dev, nb, k, lds_bytes, ix, ic, ie, *out),
+            lambda: self.cu_sweep_expected(k, lds_bytes), decode, summarize_sweep)
+        out["summary"].update(k=k, lds_bytes=lds_bytes)
+        return out
 
     # --------------------------------------------------------- matrix sweep
     def matrix_formats(self) -> list[str]:
@@ -667,15 +705,7 @@ class HipProbe:
         return self.lib.xs_matrix_formats().decode().split(",")
 
     def _matrix_mask(self, formats) -> int:
-        names = self.matrix_formats()
-        if formats is None:
-            return (1 << len(names)) - 1
-        mask = 0
-        for f in [formats] if isinstance(formats, str) else formats:
-            if f not in names:
-                raise ValueError(f"unknown matrix format {f!r}; known: {', '.join(names)}")
-            mask |= 1 << names.index(f)
-        return mask
+        return _name_mask(self.matrix_formats(), formats, "matrix format")
 
     def matrix_shape(self, fmt: str) -> dict:
         """`tile` (the result is tile x tile), `k` (both K-steps), `blocks`
@@ -685,7 +715,7 @@ class HipProbe:
         self._matrix_mask([fmt])
         rc = self.lib.xs_matrix_shape(self.matrix_formats().index(fmt), out)
         if rc != 0:
-            raise _matrix_error(self, rc, "matrix_shape")
+            raise _probe_error(self.lib.xs_matrix_sweep_last_error, rc, "matrix_shape")
         return {"tile": out[0], "k": out[1], "blocks": out[2], "accumulator": ("f32", "f64", "i32")[out[3]],
                 "frac": out[4]}
 
@@ -705,7 +735,7 @@ class HipProbe:
         rc = self.lib.xs_matrix_inputs(self.matrix_formats().index(fmt), a.ctypes.data, b.ctypes.data,
                                        sa.ctypes.data if nb else None, sb.ctypes.data if nb else None)
         if rc != 0:
-            raise _matrix_error(self, rc, "matrix_inputs")
+            raise _probe_error(self.lib.xs_matrix_sweep_last_error, rc, "matrix_inputs")
         return {"a": a, "b": b, "a_scale": sa, "b_scale": sb, **sh}
 
     def matrix_tile(self, dev: int, fmt: str):
@@ -717,7 +747,7 @@ class HipProbe:
         out = np.zeros((sh["tile"], sh["tile"]), np.float64)
         rc = self.lib.xs_matrix_tile(dev, self.matrix_formats().index(fmt), out.ctypes.data)
         if rc != 0:
-            raise _matrix_error(self, rc, "matrix_tile")
+            raise _probe_error(self.lib.xs_matrix_sweep_last_error, rc, "matrix_tile")
         return out.astype(np.int64) if sh["accumulator"] == "i32" else out
 
     def matrix_sweep_expected(self, formats=None) -> dict:
@@ -728,7 +758,7 @@ class HipProbe:
         out = (ctypes.c_uint32 * len(names))()
         rc = self.lib.xs_matrix_sweep_expected(mask, out)
         if rc != 0:
-            raise _matrix_error(self, rc, "matrix_sweep_expected")
+            raise _probe_error(self.lib.xs_matrix_sweep_last_error, rc, "matrix_sweep_expected")
         return {n: out[i] for i, n in enumerate(names) if mask >> i & 1}
 
     def matrix_sweep(self, dev: int = 0, formats=None, blocks: int = 0, inject: tuple | None = None,
@@ -744,41 +774,24 @@ class HipProbe:
         ms, blocks, formats}."""
         names = self.matrix_formats()
         mask = self._matrix_mask(formats)
-        cus = int(self.props(dev)["computeUnits"])
-        n_blocks = blocks if blocks != 0 else 4 * cus
-        ix, ic, im = -1, -1, 0
-        if inject is not None:
-            ix, ic, im = int(inject[0]), -1 if inject[1] is None else int(inject[1]), self._matrix_mask(inject[2])
-        expected = None
-        records: list[dict] = []
-        total_ms, rounds = 0.0, 0
-        summary: dict = {}
-        for _ in range(max(1, max_rounds if n_blocks >= cus else 1)):
-            buf = (ctypes.c_uint32 * (MATRIX_RECORD_WORDS * max(1, n_blocks)))()
-            n, ms = ctypes.c_int(), ctypes.c_double()
-            rc = self.lib.xs_matrix_sweep(dev, n_blocks, mask, ix, ic, im, buf, ctypes.byref(n), ctypes.byref(ms))
-            if rc != 0:
-                raise _matrix_error(self, rc, "matrix_sweep")
-            if expected is None:
-                expected = self.matrix_sweep_expected([f for i, f in enumerate(names) if mask >> i & 1])
-            rounds += 1
-            total_ms += ms.value
-            for i in range(n.value):
-                w = buf[MATRIX_RECORD_WORDS * i:MATRIX_RECORD_WORDS * (i + 1)]
-                rec = {"xcd": w[0], "cu": w[1], "simd_mask": w[2], "fail": w[3],
-                       "digests": {f: w[4 + b] for b, f in enumerate(names)}}
-                # A digest that differs from the host's is a failure even if
-                # the device-side comparator (on the same CU) passed it.
-                for b, f in enumerate(names):
-                    if rec["digests"][f] != expected.get(f, 0):
-                        rec["fail"] |= 1 << b
-                records.append(rec)
-            summary = summarize_matrix_sweep(records, cus, names)
-            if summary["covered"]:
-                break
-        summary.update(rounds=rounds, ms=total_ms, blocks=n_blocks,
-                       formats=[f for i, f in enumerate(names) if mask >> i & 1])
-        return {"records": records, "summary": summary}
+        selected = [f for i, f in enumerate(names) if mask >> i & 1]
+        (ix, ic), im = _inject_target(inject), 0 if inject is None else self._matrix_mask(inject[2])
+
+        def decode(w, expected):
+            rec = {"xcd": w[0], "cu": w[1], "simd_mask": w[2], "fail": w[3],
+                   "digests": {f: w[4 + b] for b, f in enumerate(names)}}
+            for b, f in enumerate(names):
+                if rec["digests"][f] != expected.get(f, 0):
+                    rec["fail"] |= 1 << b
+            return rec
+
+        out = self._sweep_until_covered(
+            "matrix_sweep", dev, blocks, max_rounds, MATRIX_RECORD_WORDS,
+            lambda nb, *out: self.lib.xs_matrix_sweep(dev, nb, mask, ix, ic, im, *out),
+            lambda: self.matrix_sweep_expected(selected), decode,
+            lambda records, cus: summarize_matrix_sweep(records, cus, names))
+        out["summary"].update(formats=selected)
+        return out
 
     # -------------------------------------------------- register-file sweep
     def regfile_sweep_expected(self, seed: int = REGFILE_SEED) -> int:
@@ -786,7 +799,7 @@ class HipProbe:
         out = ctypes.c_uint32()
         rc = self.lib.xs_regfile_sweep_expected(seed, ctypes.byref(out))
         if rc != 0:
-            raise _regfile_error(self, rc, "regfile_sweep_expected")
+            raise _probe_error(self.lib.xs_regfile_sweep_last_error, rc, "regfile_sweep_expected")
         return int(out.value)
 
     def regfile_sweep_info(self, dev: int = 0) -> dict:
@@ -796,7 +809,7 @@ class HipProbe:
         out = (ctypes.c_int * 3)()
         rc = self.lib.xs_regfile_sweep_info(dev, out)
         if rc != 0:
-            raise _regfile_error(self, rc, "regfile_sweep_info")
+            raise _probe_error(self.lib.xs_regfile_sweep_last_error, rc, "regfile_sweep_info")
         return {"num_regs": out[0], "scratch_bytes": out[1], "blocks_per_cu": out[2]}
 
     def regfile_sweep(self, dev: int = 0, blocks: int = 0, seed: int = REGFILE_SEED, inject: tuple | None = None,
@@ -815,46 +828,29 @@ class HipProbe:
         Relaunched while some CU has not been seen, as cu_sweep does. Returns
         {"records": [...], "summary": summarize_regfile_sweep(...) plus rounds,
         ms, blocks, seed}."""
-        cus = int(self.props(dev)["computeUnits"])
-        n_blocks = blocks if blocks != 0 else 4 * cus
-        ix, ic, ir, ib, pr = -1, -1, -1, 0, -1
+        (ix, ic), ir, ib, pr = _inject_target(inject), -1, 0, -1
         if inject is not None:
-            ix, ic, ir, ib = int(inject[0]), -1 if inject[1] is None else int(inject[1]), int(inject[2]), int(inject[3])
+            ir, ib = int(inject[2]), int(inject[3])
         if poison is not None:
-            px, pc, pr = int(poison[0]), -1 if poison[1] is None else int(poison[1]), int(poison[2])
+            px, pc = _inject_target(poison)
             if inject is not None and (px, pc) != (ix, ic):
                 raise ValueError("regfile_sweep: inject and poison select different workgroups")
-            ix, ic = px, pc
-        expected = None
-        records: list[dict] = []
-        total_ms, rounds = 0.0, 0
-        summary: dict = {}
-        for _ in range(max(1, max_rounds if n_blocks >= cus else 1)):
-            buf = (ctypes.c_uint32 * (REGFILE_RECORD_WORDS * max(1, n_blocks)))()
-            n, ms = ctypes.c_int(), ctypes.c_double()
-            rc = self.lib.xs_regfile_sweep(dev, n_blocks, seed, ix, ic, ir, ib, pr, buf, ctypes.byref(n),
-                                           ctypes.byref(ms))
-            if rc != 0:
-                raise _regfile_error(self, rc, "regfile_sweep")
-            if expected is None:
-                expected = self.regfile_sweep_expected(seed)
-            rounds += 1
-            total_ms += ms.value
-            for i in range(n.value):
-                w = buf[REGFILE_RECORD_WORDS * i:REGFILE_RECORD_WORDS * (i + 1)]
-                rec = {"xcd": w[0], "cu": w[1], "simd_mask": w[2], "fail": w[3], "bad_vgpr": w[4], "bad_agpr": w[5],
-                       "first": w[6], "flip": w[7], "digest": w[8], "bad_simds": w[9]}
-                # A digest that differs from the host's with no cell named is a
-                # failure of both files even if the device-side comparator
-                # (on the same CU) passed it.
-                if not rec["fail"] and rec["digest"] != expected:
-                    rec["fail"] = 3
-                records.append(rec)
-            summary = summarize_regfile_sweep(records, cus)
-            if summary["covered"]:
-                break
-        summary.update(rounds=rounds, ms=total_ms, blocks=n_blocks, seed=seed)
-        return {"records": records, "summary": summary}
+            ix, ic, pr = px, pc, int(poison[2])
+
+        def decode(w, expected):
+            rec = {"xcd": w[0], "cu": w[1], "simd_mask": w[2], "fail": w[3], "bad_vgpr": w[4], "bad_agpr": w[5],
+                   "first": w[6], "flip": w[7], "digest": w[8], "bad_simds": w[9]}
+            # With no cell named, a digest that differs is a failure of both files.
+            if not rec["fail"] and rec["digest"] != expected:
+                rec["fail"] = 3
+            return rec
+
+        out = self._sweep_until_covered(
+            "regfile_sweep", dev, blocks, max_rounds, REGFILE_RECORD_WORDS,
+            lambda nb, *out: self.lib.xs_regfile_sweep(dev, nb, seed, ix, ic, ir, ib, pr, *out),
+            lambda: self.regfile_sweep_expected(seed), decode, summarize_regfile_sweep)
+        out["summary"].update(seed=seed)
+        return out
 
     # ----------------------------------------------------------- lane sweep
     def lane_paths(self) -> list[str]:
@@ -862,15 +858,7 @@ class HipProbe:
         return self.lib.xs_lane_paths().decode().split(",")
 
     def _lane_mask(self, paths) -> int:
-        names = self.lane_paths()
-        if paths is None:
-            return (1 << len(names)) - 1
-        mask = 0
-        for f in [paths] if isinstance(paths, str) else paths:
-            if f not in names:
-                raise ValueError(f"unknown lane path {f!r}; known: {', '.join(names)}")
-            mask |= 1 << names.index(f)
-        return mask
+        return _name_mask(self.lane_paths(), paths, "lane path")
 
     def lane_shape(self, path: str) -> dict:
         """`steps` of one path and the `words` every thread receives per step."""
@@ -878,7 +866,7 @@ class HipProbe:
         out = (ctypes.c_int * 2)()
         rc = self.lib.xs_lane_shape(self.lane_paths().index(path), out)
         if rc != 0:
-            raise _lane_error(self, rc, "lane_shape")
+            raise _probe_error(self.lib.xs_lane_sweep_last_error, rc, "lane_shape")
         return {"steps": out[0], "words": out[1]}
 
     def lane_probe(self, dev: int, path: str, seed: int = LANE_SEED):
@@ -890,7 +878,7 @@ class HipProbe:
         out = np.zeros((sh["steps"], sh["words"], LANE_BLOCK), np.uint32)
         rc = self.lib.xs_lane_probe(dev, self.lane_paths().index(path), seed, out.ctypes.data, out.size)
         if rc != 0:
-            raise _lane_error(self, rc, "lane_probe")
+            raise _probe_error(self.lib.xs_lane_sweep_last_error, rc, "lane_probe")
         return out
 
     def lane_sweep_expected(self, paths=None, seed: int = LANE_SEED) -> dict:
@@ -901,7 +889,7 @@ class HipProbe:
         out = (ctypes.c_uint32 * len(names))()
         rc = self.lib.xs_lane_sweep_expected(mask, seed, out)
         if rc != 0:
-            raise _lane_error(self, rc, "lane_sweep_expected")
+            raise _probe_error(self.lib.xs_lane_sweep_last_error, rc, "lane_sweep_expected")
         return {n: out[i] for i, n in enumerate(names) if mask >> i & 1}
 
     def lane_sweep_info(self, dev: int = 0) -> dict:
@@ -911,7 +899,7 @@ class HipProbe:
         out = (ctypes.c_int * 4)()
         rc = self.lib.xs_lane_sweep_info(dev, out)
         if rc != 0:
-            raise _lane_error(self, rc, "lane_sweep_info")
+            raise _probe_error(self.lib.xs_lane_sweep_last_error, rc, "lane_sweep_info")
         return {"num_regs": out[0], "scratch_bytes": out[1], "lds_bytes": out[2], "blocks_per_cu": out[3]}
 
     def lane_sweep(self, dev: int = 0, blocks: int = 0, paths=None, seed: int = LANE_SEED,
@@ -927,42 +915,25 @@ class HipProbe:
         ms, blocks, paths, seed}."""
         names = self.lane_paths()
         mask = self._lane_mask(paths)
-        cus = int(self.props(dev)["computeUnits"])
-        n_blocks = blocks if blocks != 0 else 4 * cus
-        ix, ic, im = -1, -1, 0
-        if inject is not None:
-            ix, ic, im = int(inject[0]), -1 if inject[1] is None else int(inject[1]), self._lane_mask(inject[2])
-        expected = None
-        records: list[dict] = []
-        total_ms, rounds = 0.0, 0
-        summary: dict = {}
-        for _ in range(max(1, max_rounds if n_blocks >= cus else 1)):
-            buf = (ctypes.c_uint32 * (LANE_RECORD_WORDS * max(1, n_blocks)))()
-            n, ms = ctypes.c_int(), ctypes.c_double()
-            rc = self.lib.xs_lane_sweep(dev, n_blocks, mask, seed, ix, ic, im, buf, ctypes.byref(n), ctypes.byref(ms))
-            if rc != 0:
-                raise _lane_error(self, rc, "lane_sweep")
-            if expected is None:
-                expected = self.lane_sweep_expected([f for i, f in enumerate(names) if mask >> i & 1], seed)
-            rounds += 1
-            total_ms += ms.value
-            for i in range(n.value):
-                w = buf[LANE_RECORD_WORDS * i:LANE_RECORD_WORDS * (i + 1)]
-                rec = {"xcd": w[0], "cu": w[1], "simd_mask": w[2], "fail": w[3],
-                       "bad": {f: w[4 + b] for b, f in enumerate(names)},
-                       "digests": {f: w[12 + b] for b, f in enumerate(names)}, "bad_simds": w[20]}
-                # A digest that differs from the host's is a failure even if
-                # the device-side comparator (on the same CU) passed it.
-                for b, f in enumerate(names):
-                    if rec["digests"][f] != expected.get(f, 0):
-                        rec["fail"] |= 1 << b
-                records.append(rec)
-            summary = summarize_lane_sweep(records, cus, names)
-            if summary["covered"]:
-                break
-        summary.update(rounds=rounds, ms=total_ms, blocks=n_blocks, seed=seed,
-                       paths=[f for i, f in enumerate(names) if mask >> i & 1])
-        return {"records": records, "summary": summary}
+        selected = [f for i, f in enumerate(names) if mask >> i & 1]
+        (ix, ic), im = _inject_target(inject), 0 if inject is None else self._lane_mask(inject[2])
+
+        def decode(w, expected):
+            rec = {"xcd": w[0], "cu": w[1], "simd_mask": w[2], "fail": w[3],
+                   "bad": {f: w[4 + b] for b, f in enumerate(names)},
+                   "digests": {f: w[12 + b] for b, f in enumerate(names)}, "bad_simds": w[20]}
+            for b, f in enumerate(names):
+                if rec["digests"][f] != expected.get(f, 0):
+                    rec["fail"] |= 1 << b
+            return rec
+
+        out = self._sweep_until_covered(
+            "lane_sweep", dev, blocks, max_rounds, LANE_RECORD_WORDS,
+            lambda nb, *out: self.lib.xs_lane_sweep(dev, nb, mask, seed, ix, ic, im, *out),
+            lambda: self.lane_sweep_expected(selected, seed), decode,
+            lambda records, cus: summarize_lane_sweep(records, cus, names))
+        out["summary"].update(seed=seed, paths=selected)
+        return out
 
     # ------------------------------------------------------------ HBM sweep
     def hbm_sweep_pattern(self, first_vec: int, nvec: int, seed: int = HBM_SWEEP_SEED, inverted: bool = False):
@@ -973,7 +944,7 @@ class HipProbe:
         out = np.zeros((nvec, 4), np.uint32)
         rc = self.lib.xs_hbm_sweep_pattern(first_vec, nvec, seed, int(inverted), out.ctypes.data)
         if rc != 0:
-            raise _hbm_error(self, rc, "hbm_sweep_pattern")
+            raise _probe_error(self.lib.xs_hbm_sweep_last_error, rc, "hbm_sweep_pattern", HBM_WORDING)
         return out
 
     def hbm_sweep_op(self, buf, pass_: int, first_vec: int = 0, seed: int = HBM_SWEEP_SEED,
@@ -991,7 +962,7 @@ class HipProbe:
         rc = self.lib.xs_hbm_sweep_op(buf.device.index or 0, pass_, p, n, first_vec, seed, grid,
                                       ctypes.addressof(res) if pass_ != 0 else None)
         if rc != 0:
-            raise _hbm_error(self, rc, "hbm_sweep_op")
+            raise _probe_error(self.lib.xs_hbm_sweep_last_error, rc, "hbm_sweep_op", HBM_WORDING)
         if pass_ == 0:
             return None
         fold = 0
@@ -1022,7 +993,7 @@ class HipProbe:
         rc = self.lib.xs_hbm_sweep(dev, nbytes, chunk_bytes, seed, iv, iw, im, ip, ctypes.addressof(s),
                                    ctypes.addressof(log))
         if rc != 0:
-            raise _hbm_error(self, rc, "hbm_sweep")
+            raise _probe_error(self.lib.xs_hbm_sweep_last_error, rc, "hbm_sweep", HBM_WORDING)
         raw = {"bytes_requested": int(s.bytes_requested), "bytes_tested": int(s.bytes_tested),
                "chunk_bytes": int(s.chunk_bytes), "chunks": int(s.chunks), "short": bool(s.short),
                "vectors_read": int(s.vectors_read), "fold": [int(f) for f in s.fold],
@@ -1034,15 +1005,6 @@ class HipProbe:
                               for b in s.bad_chunk[:min(int(s.bad_chunks), HBM_SWEEP_BAD_CHUNKS)]},
                "log": _hbm_log(log[:int(s.log_entries)])}
         return {"raw": raw, "summary": summarize_hbm_sweep(raw)}
-
-
-def _hbm_error(p: HipProbe, rc: int, what: str) -> ProbeError:
-    detail = {BAD_ARGS: "bad arguments", HBM_BAD_BUFFER: "null or mis-aligned buffer"}.get(rc)
-    if detail is None:
-        detail = p.lib.xs_hbm_sweep_last_error().decode(errors="replace")
-    e = ProbeError(f"{what} failed ({rc}): {detail}")
-    e.rc = rc
-    return e
 
 
 def summarize_hbm_sweep(raw: dict) -> dict:
@@ -1087,13 +1049,6 @@ def summarize_hbm_sweep(raw: dict) -> dict:
             "healthy": bad == 0}
 
 
-def _sweep_error(p: HipProbe, rc: int, what: str) -> ProbeError:
-    detail = "bad arguments" if rc == SWEEP_BAD_ARGS else p.lib.xs_cu_sweep_last_error().decode(errors="replace")
-    e = ProbeError(f"{what} failed ({rc}): {detail}")
-    e.rc = rc
-    return e
-
-
 def summarize_sweep(records: list[dict], compute_units: int) -> dict:
     """Aggregate k_cu_sweep records ({"xcd", "cu", "fail", ...}; one per
     workgroup, a CU may appear many times) into a verdict per XCD.
@@ -1121,35 +1076,25 @@ def summarize_sweep(records: list[dict], compute_units: int) -> dict:
             "uncovered": uncovered, "cus_seen": sum(len(v) for v in seen.values())}
 
 
-def _matrix_error(p: HipProbe, rc: int, what: str) -> ProbeError:
-    detail = "bad arguments" if rc == BAD_ARGS else p.lib.xs_matrix_sweep_last_error().decode(errors="replace")
-    e = ProbeError(f"{what} failed ({rc}): {detail}")
-    e.rc = rc
-    return e
+def _name_fail_bits(s: dict, key: str, names: list[str]) -> dict:
+    """Adds to a summarize_sweep verdict, under `key`, the names of the fail
+    bits that are set (`names` in bit order): per XCD and overall."""
+    def named(bits: int) -> list[str]:
+        return [f for b, f in enumerate(names) if bits >> b & 1]
+
+    every = 0
+    for v in s["xcds"].values():
+        v[key] = named(v["fail_bits"])
+        every |= v["fail_bits"]
+    s[key] = named(every)
+    return s
 
 
 def summarize_matrix_sweep(records: list[dict], compute_units: int, formats: list[str]) -> dict:
     """summarize_sweep over k_matrix_sweep records, whose fail bits are format
     bits (`formats` names them in bit order): adds `failed_formats` per XCD
     and overall."""
-    s = summarize_sweep(records, compute_units)
-
-    def names(bits: int) -> list[str]:
-        return [f for b, f in enumerate(formats) if bits >> b & 1]
-
-    every = 0
-    for v in s["xcds"].values():
-        v["failed_formats"] = names(v["fail_bits"])
-        every |= v["fail_bits"]
-    s["failed_formats"] = names(every)
-    return s
-
-
-def _regfile_error(p: HipProbe, rc: int, what: str) -> ProbeError:
-    detail = "bad arguments" if rc == BAD_ARGS else p.lib.xs_regfile_sweep_last_error().decode(errors="replace")
-    e = ProbeError(f"{what} failed ({rc}): {detail}")
-    e.rc = rc
-    return e
+    return _name_fail_bits(summarize_sweep(records, compute_units), "failed_formats", formats)
 
 
 def summarize_regfile_sweep(records: list[dict], compute_units: int) -> dict:
@@ -1158,11 +1103,7 @@ def summarize_regfile_sweep(records: list[dict], compute_units: int) -> dict:
     `failed_files`, `bad_cells` (mis-compared (cell, lane) pairs; of the worst
     record of a CU that ran more than one workgroup) and `flip_mask` (hex, the
     bits that flipped); per XCD also `bad_simds` = {cu: [SIMD id, ...]}."""
-    s = summarize_sweep(records, compute_units)
-
-    def files(bits: int) -> list[str]:
-        return [f for b, f in enumerate(REGFILE_FILES) if bits >> b & 1]
-
+    s = _name_fail_bits(summarize_sweep(records, compute_units), "failed_files", REGFILE_FILES)
     cells: dict[tuple[int, int], int] = {}
     flips: dict[int, int] = {}
     simds: dict[int, dict[int, int]] = {}
@@ -1174,14 +1115,10 @@ def summarize_regfile_sweep(records: list[dict], compute_units: int) -> dict:
         flips[x] = flips.get(x, 0) | int(r.get("flip", 0))
         per = simds.setdefault(x, {})
         per[c] = per.get(c, 0) | int(r.get("bad_simds", 0))
-    every = 0
     for x, v in s["xcds"].items():
-        v["failed_files"] = files(v["fail_bits"])
         v["bad_cells"] = sum(n for (xx, _), n in cells.items() if xx == x)
         v["flip_mask"] = f"0x{flips.get(x, 0):08x}"
         v["bad_simds"] = {c: [i for i in range(4) if m >> i & 1] for c, m in sorted(simds.get(x, {}).items())}
-        every |= v["fail_bits"]
-    s["failed_files"] = files(every)
     s["bad_cells"] = sum(cells.values())
     flip = 0
     for f in flips.values():
@@ -1190,28 +1127,11 @@ def summarize_regfile_sweep(records: list[dict], compute_units: int) -> dict:
     return s
 
 
-def _lane_error(p: HipProbe, rc: int, what: str) -> ProbeError:
-    detail = "bad arguments" if rc == BAD_ARGS else p.lib.xs_lane_sweep_last_error().decode(errors="replace")
-    e = ProbeError(f"{what} failed ({rc}): {detail}")
-    e.rc = rc
-    return e
-
-
 def summarize_lane_sweep(records: list[dict], compute_units: int, paths: list[str]) -> dict:
     """summarize_sweep over k_lane_sweep records, whose fail bits are path
     bits (`paths` names them in bit order): adds `failed_paths` per XCD and
     overall."""
-    s = summarize_sweep(records, compute_units)
-
-    def names(bits: int) -> list[str]:
-        return [f for b, f in enumerate(paths) if bits >> b & 1]
-
-    every = 0
-    for v in s["xcds"].values():
-        v["failed_paths"] = names(v["fail_bits"])
-        every |= v["fail_bits"]
-    s["failed_paths"] = names(every)
-    return s
+    return _name_fail_bits(summarize_sweep(records, compute_units), "failed_paths", paths)
 
 
 _probe: HipProbe | None = None

@@ -266,13 +266,13 @@ def test_agent_withholds_the_whole_gpu_of_an_hbm_fault(store):
     host = fake_host(2, "CPX")
     clean = agent_on(store, host, lambda dev: True)
     full = dict(alloc_of(store))
-    assert clean.hbm_faults == {} and "hbmFaults" not in topo_of(store)
+    assert clean.faults["hbmFaults"] == {} and "hbmFaults" not in topo_of(store)
 
     def health(dev):  # bad XCDs in the same verdict: still the whole GPU, not a partition
         return GpuHealth(False, {5}, {"hbmFaults": HBM_FAULTS}) if dev == 0 else True
 
     agent = agent_on(store, host, health)
-    assert agent.unhealthy == {0} and agent.hbm_faults == {0: HBM_FAULTS} and agent.unhealthy_xcds == {0: {5}}
+    assert agent.unhealthy == {0} and agent.faults["hbmFaults"] == {0: HBM_FAULTS} and agent.unhealthy_xcds == {0: {5}}
     alloc = alloc_of(store)
     assert int(alloc[GPU_XCD]) == int(full[GPU_XCD]) - 8
     assert int(alloc[GPU_MEMORY]) == int(full[GPU_MEMORY]) - host.gpus[0].hbm_gib
@@ -302,11 +302,11 @@ def test_agent_drops_the_key_when_the_fault_clears_and_resyncs_on_change(store):
     worse = dict(HBM_FAULTS, badVectors=9, badBits=12)
     verdict["v"] = GpuHealth(False, (), {"hbmFaults": worse})
     agent._heartbeat_and_resync()
-    assert topo_of(store)["hbmFaults"] == {"0": worse} and agent.hbm_faults == {0: worse}
+    assert topo_of(store)["hbmFaults"] == {"0": worse} and agent.faults["hbmFaults"] == {0: worse}
     verdict["v"] = GpuHealth(True, (), {"hbmFaults": {}})
     agent._heartbeat_and_resync()
     topo = topo_of(store)
-    assert "hbmFaults" not in topo and topo["unhealthy"] == [] and agent.hbm_faults == {}
+    assert "hbmFaults" not in topo and topo["unhealthy"] == [] and agent.faults["hbmFaults"] == {}
     plain = NodeAgent(LocalClient(store), "n", host_fn=lambda: fake_host(1, "CPX"), publish_metrics=False)
     want = plain.build_node(fake_host(1, "CPX"))["metadata"]["annotations"][TOPOLOGY_ANNOTATION]
     assert store.get("nodes", "", "n")["metadata"]["annotations"][TOPOLOGY_ANNOTATION] == want

@@ -222,7 +222,7 @@ def test_agent_publishes_lane_faults_and_fences_the_partition(store):
     assert topo["xcdFaults"] == {"0": [5]} and topo["unhealthy"] == []
     assert topo["laneFaults"] == {"0": {"5": ["ldstr", "ldsdma"]}}
     assert topo["matrixFaults"] == {"0": {"5": ["fp8"]}}
-    assert agent.lane_faults == {0: {5: ["ldstr", "ldsdma"]}} and agent.unhealthy_xcds == {0: {5}}
+    assert agent.faults["laneFaults"] == {0: {5: ["ldstr", "ldsdma"]}} and agent.unhealthy_xcds == {0: {5}}
     alloc = store.get("nodes", "", "n")["status"]["allocatable"]
     assert alloc[GPU_XCD] == "15"  # only the partition that owns XCD 5 is fenced
 
@@ -243,13 +243,13 @@ def test_agent_withholds_an_spx_gpu_with_a_lane_fault(store):
 
 def test_agent_fails_a_partition_device_on_a_plain_bool(store):
     agent = agent_on(store, fake_host(2, "CPX"), lambda dev: dev != 1)  # what hip_health_fn returns there
-    assert agent.unhealthy == {1} and agent.lane_faults == {} and "laneFaults" not in topo_of(store)
+    assert agent.unhealthy == {1} and agent.faults["laneFaults"] == {} and "laneFaults" not in topo_of(store)
 
 
 def test_agent_omits_the_key_when_there_is_none(store):
     agent = agent_on(store, fake_host(2, "CPX"), lambda dev: GpuHealth(False, {1}) if dev == 0 else True)
     assert "laneFaults" not in topo_of(store) and topo_of(store)["xcdFaults"] == {"0": [1]}
-    assert agent.lane_faults == {}
+    assert agent.faults["laneFaults"] == {}
     agent = agent_on(store, fake_host(2, "CPX"), lambda dev: GpuHealth(True, (), {"laneFaults": {}}))
     assert "laneFaults" not in topo_of(store) and "xcdFaults" not in topo_of(store)
     plain = NodeAgent(LocalClient(store), "n", host_fn=lambda: fake_host(2, "CPX"), publish_metrics=False)

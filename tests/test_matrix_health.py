@@ -170,14 +170,14 @@ def test_agent_publishes_matrix_faults_next_to_xcd_faults(store):
     topo = topo_of(store)
     assert topo["xcdFaults"] == {"0": [5]}
     assert topo["matrixFaults"] == {"0": {"5": ["fp8", "mxfp4"]}}
-    assert agent.matrix_faults == {0: {5: ["fp8", "mxfp4"]}} and agent.unhealthy_xcds == {0: {5}}
+    assert agent.faults["matrixFaults"] == {0: {5: ["fp8", "mxfp4"]}} and agent.unhealthy_xcds == {0: {5}}
     assert store.get("nodes", "", "n")["status"]["allocatable"][GPU_XCD] == "15"
 
 
 def test_agent_omits_the_key_when_there_is_none(store):
     agent = agent_on(store, fake_host(2, "CPX"), lambda dev: GpuHealth(False, {1}) if dev == 0 else True)
     assert "matrixFaults" not in topo_of(store) and topo_of(store)["xcdFaults"] == {"0": [1]}
-    assert agent.matrix_faults == {}
+    assert agent.faults["matrixFaults"] == {}
     agent = agent_on(store, fake_host(2, "CPX"), lambda dev: GpuHealth(True, (), {"matrixFaults": {}}))
     assert "matrixFaults" not in topo_of(store) and "xcdFaults" not in topo_of(store)
     plain = NodeAgent(LocalClient(store), "n", host_fn=lambda: fake_host(2, "CPX"), publish_metrics=False)

@@ -253,7 +253,7 @@ def test_agent_publishes_register_faults_next_to_xcd_faults(store):
     assert topo["xcdFaults"] == {"0": [5]}
     assert topo["registerFaults"] == {"0": {"5": FAULT}}
     assert topo["matrixFaults"] == {"0": {"5": ["fp8"]}}
-    assert agent.register_faults == {0: {5: FAULT}} and agent.unhealthy_xcds == {0: {5}}
+    assert agent.faults["registerFaults"] == {0: {5: FAULT}} and agent.unhealthy_xcds == {0: {5}}
     assert store.get("nodes", "", "n")["status"]["allocatable"][GPU_XCD] == "15"
 
 
@@ -267,7 +267,7 @@ def test_agent_withholds_an_spx_gpu_with_a_register_fault(store):
 def test_agent_omits_the_key_when_there_is_none(store):
     agent = agent_on(store, fake_host(2, "CPX"), lambda dev: GpuHealth(False, {1}) if dev == 0 else True)
     assert "registerFaults" not in topo_of(store) and topo_of(store)["xcdFaults"] == {"0": [1]}
-    assert agent.register_faults == {}
+    assert agent.faults["registerFaults"] == {}
     agent = agent_on(store, fake_host(2, "CPX"), lambda dev: GpuHealth(True, (), {"registerFaults": {}}))
     assert "registerFaults" not in topo_of(store) and "xcdFaults" not in topo_of(store)
     plain = NodeAgent(LocalClient(store), "n", host_fn=lambda: fake_host(2, "CPX"), publish_metrics=False)
