@@ -2,10 +2,11 @@
 // reductions, the error check, and the host side of a per-CU sweep launch.
 //
 // A per-CU sweep (cu_sweep.hip, matrix_sweep.hip, regfile_sweep.hip,
-// lane_sweep.hip) is one launch of 256-thread workgroups of which no two fit
-// on a CU, 4 per CU by default, each leaving one record whose first four
-// words are {xcd, cu key, simd mask, fail bits}. The kernels differ; how such
-// a launch is validated, sized, timed and read back is launch_sweep() below.
+// lane_sweep.hip, valu_sweep.hip) is one launch of 256-thread workgroups of
+// which no two fit on a CU, 4 per CU by default, each leaving one record whose
+// first four words are {xcd, cu key, simd mask, fail bits}. The kernels
+// differ; how such a launch is validated, sized, timed and read back is
+// launch_sweep() below.
 //
 // Two things a new sweep decides on purpose when it fills a SweepCall, because
 // the existing ones differ and their callers rely on it:

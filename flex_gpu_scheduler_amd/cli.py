@@ -346,7 +346,9 @@ def health_fn_args(args) -> dict:
     reserve (hbm_gib None), else that many GiB.
     --health-register-sweep: absent -> no regfile key.
     --health-lane-sweep: absent -> no lane keys, bare -> every path
-    (lane_paths None), else a comma list."""
+    (lane_paths None), else a comma list.
+    --health-valu-sweep: absent -> no valu keys, bare -> every unit
+    (valu_units None), else a comma list."""
     m = args.health_matrix_sweep
     formats = None if m in (None, "all") else [f.strip() for f in m.split(",") if f.strip()]
     kw = {"sweep": args.health_sweep, "sweep_period_s": args.health_sweep_period, "matrix": m is not None,
@@ -359,6 +361,9 @@ def health_fn_args(args) -> dict:
     ln = getattr(args, "health_lane_sweep", None)
     if ln is not None:
         kw.update(lane=True, lane_paths=None if ln == "all" else [f.strip() for f in ln.split(",") if f.strip()])
+    vu = getattr(args, "health_valu_sweep", None)
+    if vu is not None:
+        kw.update(valu=True, valu_units=None if vu == "all" else [f.strip() for f in vu.split(",") if f.strip()])
     return kw
 
 
@@ -378,7 +383,8 @@ def cmd_node_agent(args) -> int:
                       health_fn=(hip_health_fn(**health_fn_args(args))
                                  if args.health_probe or args.health_sweep or args.health_matrix_sweep is not None
                                  or args.health_hbm_sweep is not None or args.health_register_sweep
-                                 or args.health_lane_sweep is not None else None),
+                                 or args.health_lane_sweep is not None
+                                 or getattr(args, "health_valu_sweep", None) is not None else None),
                       bandwidth_fn=hip_bandwidth_fn() if args.bandwidth_probe else None,
                       kubelet_managed=args.kubelet_managed).start()
     if args.device_plugin:
@@ -559,6 +565,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "DMA LDS paths) run on every CU (a comma list selects some; default all); a bad XCD is fenced "
                         "like --health-sweep's and its paths are published as laneFaults. Implies --health-probe; "
                         "independent of the other sweeps")
+    p.add_argument("--health-valu-sweep", nargs="?", const="all", default=None, metavar="UNITS",
+                   help="health probe plus the VALU sweep: the f32, f64, f16, int, bit, dot, cvt and trans units of the "
+                        "vector ALU (each instruction under its own mnemonic, on hashed operands, against a host-computed "
+                        "table) run on every SIMD of every CU (a comma list selects some; default all); a bad XCD is "
+                        "fenced like --health-sweep's and its units are published as valuFaults. Implies "
+                        "--health-probe; independent of the other sweeps")
     p.add_argument("--health-sweep-period", type=float, default=600.0, metavar="SECONDS",
                    help="reuse a sweep's verdict this long before sweeping the GPU again")
     p.add_argument("--bandwidth-probe", action="store_true",

@@ -17,7 +17,8 @@ exporter + metrics-server:
     on a DPX/QPX/CPX GPU (`xcdFaults` in the topology annotation), and the
     matrix formats such an XCD gets wrong are published as `matrixFaults`
     and the register files it reads back wrong as `registerFaults` and the
-    cross-lane and LDS paths it moves data wrongly through as `laneFaults`;
+    cross-lane and LDS paths it moves data wrongly through as `laneFaults`
+    and the vector-ALU units it mis-computes as `valuFaults`;
     a verdict that carries an HBM fault (the HBM sweep) withholds the whole
     GPU, partitioned or not, and is published as `hbmFaults`;
   * samples load (gpu/telemetry.py) and publishes its WatcherMetrics document
@@ -68,6 +69,8 @@ FAULT_KINDS = {
     "registerFaults": FaultKind(per_xcd=True),
     # The cross-lane and LDS paths a faulty XCD gets wrong (the lane sweep): {xcd: [path, ...]}.
     "laneFaults": FaultKind(per_xcd=True),
+    # The vector-ALU units a faulty XCD mis-computes (the VALU sweep): {xcd: [unit, ...]}.
+    "valuFaults": FaultKind(per_xcd=True),
     # What the HBM sweep found on the GPU. The sweep knows a fault by its
     # virtual address, which cannot be tied to the HBM slice of one compute
     # partition, so there is no partial fence for memory.
@@ -415,7 +418,8 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
                   matrix_args: dict | None = None, hbm: bool = False, hbm_gib: float | None = None,
                   hbm_args: dict | None = None, regfile: bool = False,
                   regfile_args: dict | None = None, lane: bool = False, lane_paths: list | None = None,
-                  lane_args: dict | None = None) -> Callable[[int], "bool | GpuHealth"]:
+                  lane_args: dict | None = None, valu: bool = False, valu_units: list | None = None,
+                  valu_args: dict | None = None) -> Callable[[int], "bool | GpuHealth"]:
     """Health callback backed by the HIP probes (HBM pattern + checksum and an
     MFMA tile check per GPU).
 
@@ -431,6 +435,11 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
     values through the DPP shifters, the permlane swaps, readlane / writelane,
     the LDS crossbar and the wide, sub-dword, transposed, atomic and DMA LDS
     paths of every CU; detail["laneFaults"] = {xcd: [path, ...]}.
+    `valu`: also run the VALU sweep (HipProbe.valu_sweep over `valu_units`,
+    None for all; `valu_args` are its other keywords), which issues the f32,
+    f64, f16, wide-integer, bit-field, dot, conversion and transcendental
+    instructions of every SIMD on hashed operands; detail["valuFaults"] =
+    {xcd: [unit, ...]}, the step names are in detail["valuSweep"].
     The callback runs on every heartbeat, so the sweeps' verdict is reused for
     `sweep_period_s`. On a device that shows all 8 XCDs the verdict is a
     GpuHealth naming the bad physical XCDs of any of these sweeps, with
@@ -471,6 +480,8 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
          "registerFaults"),
         (lane, "lane_sweep", dict(paths=lane_paths, **(lane_args or {})),
          lambda v: list(v["failed_paths"]), "lane", "laneSweep", "laneFaults"),
+        (valu, "valu_sweep", dict(units=valu_units, **(valu_args or {})),
+         lambda v: list(v["failed_units"]), "valu", "valuSweep", "valuFaults"),
     ]
 
     def sweep_verdict(dev: int):
@@ -489,6 +500,8 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
                     "%s sweep GPU %d: %d CUs on %d XCDs in %.2f ms (%d launch(es)), covered=%s uncovered=%s "
                     "%s=%s", label, dev, s["cus_seen"], len(s["xcds"]), s["ms"], s["rounds"], s["covered"],
                     {x: n for x, n in s["uncovered"].items() if n}, "bad_xcds" if fault_of is None else "faults", found)
+            if s.get("failed_steps"):
+                log.warning("%s sweep GPU %d: failed steps %s", label, dev, s["failed_steps"])
             bad |= set(s["bad_xcds"])
             detail[summary_key] = s
             if faults_key:
@@ -529,7 +542,7 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
         # HBM pattern/checksum and an exact-integer MFMA tile: a GPU whose matrix
         # cores mis-compute is withheld even if its memory checks out.
         ok = bool(p.health(dev)["healthy"]) and bool(p.mfma_check(dev)["healthy"])
-        if not (sweep or matrix or hbm or regfile or lane) or not ok:
+        if not (sweep or matrix or hbm or regfile or lane or valu) or not ok:
             return ok
         return sweep_verdict(dev)
 

@@ -1,6 +1,7 @@
 """ctypes front-end for the HIP/CDNA4 device probes (csrc/hip/hbm_probe.hip,
 csrc/hip/mfma_probe.hip, csrc/hip/cu_sweep.hip, csrc/hip/matrix_sweep.hip,
-csrc/hip/hbm_sweep.hip, csrc/hip/regfile_sweep.hip, csrc/hip/lane_sweep.hip).
+csrc/hip/hbm_sweep.hip, csrc/hip/regfile_sweep.hip, csrc/hip/lane_sweep.hip,
+csrc/hip/valu_sweep.hip).
 
 The probes are what the node agent runs before advertising an MI355X as
 schedulable: device properties, HBM streaming bandwidth (optionally with a
@@ -16,7 +17,9 @@ bits that read back wrong, and a sweep of every SIMD's whole VGPR/AGPR file
 that names the register file, the cells and the SIMDs that read back wrong,
 and a sweep of every CU's cross-lane network (DPP, permlane swaps, readlane /
 writelane, the LDS crossbar) and wide, sub-dword, transposed, atomic and DMA
-LDS paths that names the paths a CU gets wrong.
+LDS paths that names the paths a CU gets wrong, and a sweep of every SIMD's
+vector ALU (float, packed, wide-integer, bit-field, dot, conversion and
+transcendental instructions) that names the units and steps a CU gets wrong.
 """
 from __future__ import annotations
 
@@ -88,6 +91,13 @@ REGFILE_NO_CELL = 0xFFFF  # `first` of a record without a mis-compare
 LANE_RECORD_WORDS = 32
 LANE_SEED = 0x1B873593
 LANE_BLOCK = 256  # threads per workgroup: the last axis of a probe's dump
+
+# k_valu_sweep (csrc/hip/valu_sweep.hip): one 128-byte record per workgroup;
+# words 22..27 are bits over the global step index of the steps that mis-compared.
+VALU_RECORD_WORDS = 32
+VALU_SEED = 0x1B873593
+VALU_ROUNDS = 2  # operand sets per step; measured in profiles/valu_sweep_defaults.md
+VALU_BLOCK = 256
 
 # k_hbm_fill / k_hbm_verify (csrc/hip/hbm_sweep.hip)
 HBM_SWEEP_SEED = 0x5EED1E55
@@ -268,6 +278,21 @@ class HipProbe:
         L.xs_lane_sweep.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int,
                                     ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int),
                                     ctypes.POINTER(ctypes.c_double)]
+        L.xs_valu_sweep_last_error.restype = ctypes.c_char_p
+        L.xs_valu_units.restype = ctypes.c_char_p
+        L.xs_valu_steps.restype = ctypes.c_char_p
+        L.xs_valu_steps.argtypes = [ctypes.c_int]
+        L.xs_valu_shape.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        L.xs_valu_expected.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                       ctypes.c_size_t]
+        L.xs_valu_probe.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                    ctypes.c_size_t]
+        L.xs_valu_sweep_expected.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                             ctypes.POINTER(ctypes.c_uint32)]
+        L.xs_valu_sweep_info.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        L.xs_valu_sweep.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                    ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p,
+                                    ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]
         L.xs_hbm_sweep_last_error.restype = ctypes.c_char_p
         L.xs_hbm_sweep_pattern.argtypes = [ctypes.c_uint64, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int,
                                            ctypes.c_void_p]
@@ -935,6 +960,111 @@ class HipProbe:
         out["summary"].update(seed=seed, paths=selected)
         return out
 
+    # ----------------------------------------------------------- VALU sweep
+    def valu_units(self) -> list[str]:
+        """Unit names of the VALU sweep; the index is the unit's bit."""
+        return self.lib.xs_valu_units().decode().split(",")
+
+    def _valu_mask(self, units) -> int:
+        return _name_mask(self.valu_units(), units, "VALU unit")
+
+    def valu_steps(self, unit: str | None = None) -> list[str]:
+        """Step names of one unit in order; None: of every unit, in the order
+        of the record's step bits."""
+        names = self.valu_units()
+        if unit is None:
+            return [s for u in names for s in self.valu_steps(u)]
+        self._valu_mask([unit])
+        return self.lib.xs_valu_steps(names.index(unit)).decode().split(",")
+
+    def valu_shape(self, unit: str) -> dict:
+        """`steps` of one unit and the result `words` every thread gets per round."""
+        self._valu_mask([unit])
+        out = (ctypes.c_int * 2)()
+        rc = self.lib.xs_valu_shape(self.valu_units().index(unit), out)
+        if rc != 0:
+            raise _probe_error(self.lib.xs_valu_sweep_last_error, rc, "valu_shape")
+        return {"steps": out[0], "words": out[1]}
+
+    def _valu_dump(self, what: str, unit: str, rounds: int, call):
+        import numpy as np
+
+        sh = self.valu_shape(unit)
+        out = np.zeros((max(int(rounds), 0), sh["words"], VALU_BLOCK), np.uint32)
+        rc = call(self.valu_units().index(unit), out)
+        if rc != 0:
+            raise _probe_error(self.lib.xs_valu_sweep_last_error, rc, what)
+        return out
+
+    def valu_expected(self, unit: str, seed: int = VALU_SEED, rounds: int = VALU_ROUNDS):
+        """What every thread of a healthy SIMD gets from `unit`, computed on
+        the host: uint32 [rounds, words, 256]. No device call."""
+        return self._valu_dump("valu_expected", unit, rounds, lambda u, out: self.lib.xs_valu_expected(
+            u, seed, rounds, out.ctypes.data, out.size))
+
+    def valu_probe(self, dev: int, unit: str, seed: int = VALU_SEED, rounds: int = VALU_ROUNDS):
+        """k_valu_probe: one workgroup runs `unit` and stores every result:
+        uint32 [rounds, words, 256] (thread = 64 x wave + lane)."""
+        return self._valu_dump("valu_probe", unit, rounds, lambda u, out: self.lib.xs_valu_probe(
+            dev, u, seed, rounds, out.ctypes.data, out.size))
+
+    def valu_sweep_expected(self, units=None, seed: int = VALU_SEED, rounds: int = VALU_ROUNDS) -> dict:
+        """The workgroup digest a healthy CU leaves per selected unit,
+        computed on the host from the step table."""
+        names = self.valu_units()
+        mask = self._valu_mask(units)
+        out = (ctypes.c_uint32 * len(names))()
+        rc = self.lib.xs_valu_sweep_expected(mask, seed, rounds, out)
+        if rc != 0:
+            raise _probe_error(self.lib.xs_valu_sweep_last_error, rc, "valu_sweep_expected")
+        return {n: out[i] for i, n in enumerate(names) if mask >> i & 1}
+
+    def valu_sweep_info(self, dev: int = 0) -> dict:
+        """What the runtime reports for k_valu_sweep: `num_regs`,
+        `scratch_bytes` per lane, `lds_bytes` per workgroup and `blocks_per_cu`
+        (workgroups that fit on a CU at once)."""
+        out = (ctypes.c_int * 4)()
+        rc = self.lib.xs_valu_sweep_info(dev, out)
+        if rc != 0:
+            raise _probe_error(self.lib.xs_valu_sweep_last_error, rc, "valu_sweep_info")
+        return {"num_regs": out[0], "scratch_bytes": out[1], "lds_bytes": out[2], "blocks_per_cu": out[3]}
+
+    def valu_sweep(self, dev: int = 0, blocks: int = 0, units=None, seed: int = VALU_SEED,
+                   rounds: int = VALU_ROUNDS, inject: tuple | None = None, max_rounds: int = 4) -> dict:
+        """k_valu_sweep: every selected unit (None: all) of the vector ALU
+        runs `rounds` operand sets per step on every CU a workgroup lands on.
+        `inject` = (xcd, cu key or None for every CU of that XCD, [unit
+        names]): those workgroups flip one bit of one result of those units
+        (tests the comparator on a healthy GPU). `blocks` 0: 4 per CU.
+
+        Relaunched (at most `max_rounds` launches) while some CU has not been
+        seen, as cu_sweep does. Returns {"records": [...], "summary":
+        summarize_valu_sweep(...) plus rounds (launches), ms, blocks, units,
+        operand_rounds, seed}."""
+        names = self.valu_units()
+        steps = self.valu_steps()
+        mask = self._valu_mask(units)
+        selected = [f for i, f in enumerate(names) if mask >> i & 1]
+        (ix, ic), im = _inject_target(inject), 0 if inject is None else self._valu_mask(inject[2])
+
+        def decode(w, expected):
+            rec = {"xcd": w[0], "cu": w[1], "simd_mask": w[2], "fail": w[3],
+                   "bad": {f: w[4 + b] for b, f in enumerate(names)},
+                   "digests": {f: w[12 + b] for b, f in enumerate(names)}, "bad_simds": w[20],
+                   "bad_steps": [s for g, s in enumerate(steps) if w[22 + g // 32] >> (g % 32) & 1]}
+            for b, f in enumerate(names):
+                if rec["digests"][f] != expected.get(f, 0):
+                    rec["fail"] |= 1 << b
+            return rec
+
+        out = self._sweep_until_covered(
+            "valu_sweep", dev, blocks, max_rounds, VALU_RECORD_WORDS,
+            lambda nb, *out: self.lib.xs_valu_sweep(dev, nb, mask, seed, rounds, ix, ic, im, *out),
+            lambda: self.valu_sweep_expected(selected, seed, rounds), decode,
+            lambda records, cus: summarize_valu_sweep(records, cus, names))
+        out["summary"].update(seed=seed, units=selected, operand_rounds=rounds)
+        return out
+
     # ------------------------------------------------------------ HBM sweep
     def hbm_sweep_pattern(self, first_vec: int, nvec: int, seed: int = HBM_SWEEP_SEED, inverted: bool = False):
         """The sweep's pattern for 16-byte vectors [first_vec, first_vec +
@@ -1132,6 +1262,22 @@ def summarize_lane_sweep(records: list[dict], compute_units: int, paths: list[st
     bits (`paths` names them in bit order): adds `failed_paths` per XCD and
     overall."""
     return _name_fail_bits(summarize_sweep(records, compute_units), "failed_paths", paths)
+
+
+def summarize_valu_sweep(records: list[dict], compute_units: int, units: list[str]) -> dict:
+    """summarize_sweep over k_valu_sweep records, whose fail bits are unit
+    bits (`units` names them in bit order): adds `failed_units` per XCD and
+    overall, and `failed_steps` (the names in the records' `bad_steps`, in
+    first-seen order) per XCD and overall."""
+    s = _name_fail_bits(summarize_sweep(records, compute_units), "failed_units", units)
+    steps: dict[int, list[str]] = {}
+    for r in records:
+        if int(r.get("fail", 0)):
+            steps.setdefault(int(r["xcd"]), []).extend(r.get("bad_steps", []))
+    for x, v in s["xcds"].items():
+        v["failed_steps"] = list(dict.fromkeys(steps.get(x, [])))
+    s["failed_steps"] = list(dict.fromkeys(n for x in sorted(steps) for n in steps[x]))
+    return s
 
 
 _probe: HipProbe | None = None
