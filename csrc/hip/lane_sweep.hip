@@ -12,8 +12,7 @@
 // sub-dword, transposed, atomic and DMA paths of LDS. Everything is data
 // movement or exact integer arithmetic: one right answer, no tolerance.
 //
-// Values. fmix32 is the murmur3 finaliser (a bijection of 32 bits):
-//   h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16.
+// Values. fmix32 is the murmur3 finaliser, a bijection of 32 bits (part_sweep.h).
 //   src(p, s, w, l) = fmix32(seed ^ (p << 24 | s << 12 | w << 6 | l))
 //   aux(p, s, w, l) = fmix32(seed ^ (1 << 28 | p << 24 | s << 12 | w << 6 | l))
 // p = path, s = step, l = lane (0..63), w = 4 * wave + word (a step has at
@@ -135,16 +134,13 @@
 // Comparison. Each lane computes what it must receive with integer VALU only
 // (the hash of the source lane under the map), counts mismatches per path and
 // accumulates D_p += got * (2 idx + 1), idx = (step * words + word) * 256 + t.
-// The 256 threads' counts and digests are combined through plain ds_write_b32
-// / ds_read_b32 and a barrier and summed by thread 0: no shuffle, DPP or
-// permute, so the sweep does not lean on what it tests. The workgroup digest
-// of each selected path is compared on the device with the host's; a digest
-// mismatch with no counted mismatch sets the path's fail bit too.
+// part_sweep.h's reduce_parts() makes the record of the 256 threads' counts
+// and digests, with plain LDS words and a barrier: no shuffle, DPP or permute,
+// so the sweep does not lean on what it tests.
 //
-// Record (128 bytes per workgroup, vector stores): xcd, cu, simd_mask, fail
-// (bit = path), eight bad counts, eight digests (0 for a path not selected),
-// bad_simds (SIMD ids whose wave mis-compared), eleven reserved words. xcd is
-// HW_REG_XCC_ID, cu is bits [15:8] of HW_REG_HW_ID, as in cu_sweep.hip.
+// Record (128 bytes per workgroup): part_sweep.h's head with a path per part,
+// eleven reserved words. xcd is HW_REG_XCC_ID, cu is bits [15:8] of
+// HW_REG_HW_ID, as in cu_sweep.hip.
 //
 // Injection (testing the comparator and the localisation on a healthy GPU): a
 // workgroup on inject_xcd whose CU key is inject_cu (or any, with -1) flips
@@ -169,7 +165,7 @@
 #include <utility>
 #include <vector>
 
-#include "hip/sweep_common.h"
+#include "hip/part_sweep.h"
 
 #define XS_ERR_BUF g_lane_err
 #define XS_HD __host__ __device__ __forceinline__
@@ -193,11 +189,10 @@ struct Shape {
 };
 constexpr Shape kShape[kNumPaths] = {{75, 1}, {4, 2}, {133, 1}, {137, 1}, {112, 4}, {32, 2}, {13, 4}, {6, 4}};
 
-constexpr int kBlock = 256;  // 4 waves: one per SIMD
+constexpr int kBlock = kPartBlock;
 
 // LDS layout in bytes from the start of the allocation.
-constexpr uint32_t kRedWords = 2 * kNumPaths + 2;            // per thread: bad[8], digest[8], bad simd, simd
-constexpr uint32_t kRedBytes = kRedWords * kBlock * 4;       // [quantity][thread]
+constexpr uint32_t kRedBytes = part_reduction_words(kNumPaths, 0) * 4;
 constexpr uint32_t kTileOff = kRedBytes;                     // per wave: 4 KiB
 constexpr uint32_t kTileBytes = 4096;
 constexpr uint32_t kAtomOff = kTileOff + 4 * kTileBytes;     // per thread: 8 B
@@ -213,26 +208,14 @@ constexpr int kDmaSteps = 6;
 constexpr size_t kDmaWords = static_cast<size_t>(kDmaSteps) * 4 * 64 * 4;
 
 struct LaneRecord {
-  uint32_t xcd, cu, simd_mask, fail;
-  uint32_t bad[kNumPaths];
-  uint32_t digest[kNumPaths];
-  uint32_t bad_simds, reserved[11];
+  PartRecordHead<kNumPaths> head;
+  uint32_t reserved[11];
 };
 static_assert(sizeof(LaneRecord) == 128, "one 128-byte record per workgroup");
 
-struct Expect {
-  uint32_t digest[kNumPaths];  // workgroup digest of a healthy CU; 0 when not selected
-};
+using Expect = PartExpect<kNumPaths>;
 
 // ------------------------------------------------------------------- values
-XS_HD uint32_t fmix32(uint32_t h) {
-  h ^= h >> 16;
-  h *= 0x85ebca6bu;
-  h ^= h >> 13;
-  h *= 0xc2b2ae35u;
-  h ^= h >> 16;
-  return h;
-}
 // t = 64 * wave + lane; the word field of the key is 4 * wave + word.
 XS_HD uint32_t srcv(uint32_t seed, uint32_t p, uint32_t s, uint32_t word, uint32_t t) {
   return fmix32(seed ^ (p << 24 | s << 12 | (4u * (t >> 6) + word) << 6 | (t & 63u)));
@@ -433,17 +416,9 @@ struct Ctx {
   uint32_t* dump;  // k_lane_probe only
 };
 
-struct Tally {
-  uint32_t bad = 0, digest = 0;
-};
-
 template <int P>
 XS_D void take(const Ctx& c, Tally& y, uint32_t step, uint32_t word, uint32_t got, uint32_t expect) {
-  const uint32_t idx = (step * kShape[P].words + word) * kBlock + c.t;
-  if (((c.inj >> P) & 1u) && idx == 0) got ^= 1u;
-  if (c.dump) c.dump[idx] = got;
-  y.bad += got != expect;
-  y.digest += got * (2u * idx + 1u);
+  take_word(y, c.dump, (step * kShape[P].words + word) * kBlock + c.t, got, expect, (c.inj >> P) & 1u);
 }
 
 // The value leaves the compiler's sight here, so the instruction that made it
@@ -800,42 +775,9 @@ __global__ __launch_bounds__(kBlock) void k_lane_sweep(LaneRecord* __restrict__ 
   Tally y[kNumPaths];
   run_paths(c, path_mask, lane_lds, dma_src, y);
 
-  // The reduction: plain LDS words and a barrier, summed by thread 0. The
-  // markers bound it for tests/test_lane_codeobject.py.
+  // The markers bound the reduction for tests/test_lane_codeobject.py.
   asm volatile("; lane_sweep reduction begin" ::: "memory");
-  __syncthreads();
-  uint32_t any = 0;
-#pragma unroll
-  for (int p = 0; p < kNumPaths; ++p) {
-    lane_lds[p * kBlock + t] = y[p].bad;
-    lane_lds[(kNumPaths + p) * kBlock + t] = y[p].digest;
-    any |= y[p].bad;
-  }
-  lane_lds[2 * kNumPaths * kBlock + t] = any ? 1u << simd : 0u;
-  lane_lds[(2 * kNumPaths + 1) * kBlock + t] = 1u << simd;
-  __syncthreads();
-  if (t == 0) {
-    uint32_t sum[kRedWords] = {};
-    for (int u = 0; u < kBlock; ++u) {
-#pragma unroll
-      for (uint32_t q = 0; q < 2 * kNumPaths; ++q) sum[q] += lane_lds[q * kBlock + u];
-      sum[2 * kNumPaths] |= lane_lds[2 * kNumPaths * kBlock + u];
-      sum[2 * kNumPaths + 1] |= lane_lds[(2 * kNumPaths + 1) * kBlock + u];
-    }
-    uint32_t fail = 0;
-#pragma unroll
-    for (int p = 0; p < kNumPaths; ++p)
-      if (((path_mask >> p) & 1u) && (sum[p] || sum[kNumPaths + p] != expect.digest[p])) fail |= 1u << p;
-    u32x4* out = reinterpret_cast<u32x4*>(&records[blockIdx.x]);
-    out[0] = u32x4{xcd, cu, sum[2 * kNumPaths + 1], fail};
-    out[1] = u32x4{sum[0], sum[1], sum[2], sum[3]};
-    out[2] = u32x4{sum[4], sum[5], sum[6], sum[7]};
-    out[3] = u32x4{sum[8], sum[9], sum[10], sum[11]};
-    out[4] = u32x4{sum[12], sum[13], sum[14], sum[15]};
-    out[5] = u32x4{sum[2 * kNumPaths], 0u, 0u, 0u};
-    out[6] = u32x4{0u, 0u, 0u, 0u};
-    out[7] = u32x4{0u, 0u, 0u, 0u};
-  }
+  reduce_parts<kNumPaths, 0>(lane_lds, t, simd, y, nullptr, path_mask, expect, xcd, cu, &records[blockIdx.x]);
   asm volatile("; lane_sweep reduction end" ::: "memory");
 }
 
@@ -881,8 +823,6 @@ void expected(uint32_t path_mask, uint32_t seed, Expect* e) {
   for (int p = 0; p < kNumPaths; ++p) e->digest[p] = (path_mask >> p) & 1u ? all[p] : 0u;
 }
 
-bool bad_mask(uint32_t m) { return m == 0 || (m & ~kAllPaths); }
-
 // The LDS-DMA source: [step][wave][64][4] of src(ldsdma, step, word, lane).
 int fill_dma_source(uint32_t seed, DevMem& buf) {
   std::vector<uint32_t> g(kDmaWords);
@@ -917,27 +857,20 @@ int xs_lane_probe(int dev, int path, uint32_t seed, uint32_t* out, size_t n_word
   if (path < 0 || path >= kNumPaths || !out) return kBadArgs;
   const size_t n = static_cast<size_t>(kShape[path].steps) * kShape[path].words * kBlock;
   if (n_words != n) return kBadArgs;
-  XS_CHECK(hipSetDevice(dev));
-  size_t smem = 0;
-  if (int rc = exclusive_lds(g_lane_err, dev, kLdsUsed, &smem)) return rc;
-  XS_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_lane_probe), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               static_cast<int>(smem)));
-  DevMem dma, dump;
-  if (int rc = fill_dma_source(seed, dma)) return rc;
-  XS_CHECK(hipMalloc(&dump.p, n * 4));
-  XS_CHECK(hipMemset(dump.p, 0xff, n * 4));
-  hipLaunchKernelGGL(k_lane_probe, dim3(1), dim3(kBlock), smem, 0, dump.as<uint32_t>(), dma.as<const uint32_t>(), path,
-                     seed);
-  XS_CHECK(hipGetLastError());
-  XS_CHECK(hipDeviceSynchronize());
-  XS_CHECK(hipMemcpy(out, dump.p, n * 4, hipMemcpyDeviceToHost));
-  return 0;
+  DevMem dma;
+  return launch_probe(
+      g_lane_err, dev, reinterpret_cast<const void*>(k_lane_probe), kBlock, kLdsUsed, out, n,
+      [&](dim3 grid, dim3 block, size_t smem, void* dump) {
+        hipLaunchKernelGGL(k_lane_probe, grid, block, smem, 0, static_cast<uint32_t*>(dump), dma.as<const uint32_t>(),
+                           path, seed);
+      },
+      [&] { return fill_dma_source(seed, dma); });
 }
 
 // Host only. out8[p] = the workgroup digest a healthy CU leaves for path p, 0
 // for a path outside path_mask.
 int xs_lane_sweep_expected(uint32_t path_mask, uint32_t seed, uint32_t* out8) {
-  if (bad_mask(path_mask) || !out8) return kBadArgs;
+  if (bad_part_mask(path_mask, kAllPaths) || !out8) return kBadArgs;
   Expect e;
   expected(path_mask, seed, &e);
   for (int p = 0; p < kNumPaths; ++p) out8[p] = e.digest[p];
@@ -948,11 +881,7 @@ int xs_lane_sweep_expected(uint32_t path_mask, uint32_t seed, uint32_t* out8) {
 // lane, scratch bytes per lane, dynamic LDS bytes per workgroup, workgroups
 // that fit on a CU at once}.
 int xs_lane_sweep_info(int dev, int* out4) {
-  if (!out4) return kBadArgs;
-  XS_CHECK(hipSetDevice(dev));
-  size_t smem = 0;
-  if (int rc = exclusive_lds(g_lane_err, dev, 0, &smem)) return rc;
-  return kernel_info(g_lane_err, reinterpret_cast<const void*>(k_lane_sweep), kBlock, smem, out4);
+  return sweep_info(g_lane_err, dev, reinterpret_cast<const void*>(k_lane_sweep), kBlock, true, out4);
 }
 
 // One sweep launch of `blocks` workgroups (0: 4 per CU). Writes `blocks`
@@ -961,7 +890,7 @@ int xs_lane_sweep_info(int dev, int* out4) {
 // arguments (nothing is launched), or a negative HIP error.
 int xs_lane_sweep(int dev, int blocks, uint32_t path_mask, uint32_t seed, int inject_xcd, int inject_cu,
                   uint32_t inject_paths, void* records_out, int* n_records, double* ms) {
-  if (bad_mask(path_mask) || (inject_paths & ~kAllPaths)) return kBadArgs;
+  if (bad_part_mask(path_mask, kAllPaths) || (inject_paths & ~kAllPaths)) return kBadArgs;
   Expect e;
   expected(path_mask, seed, &e);
   DevMem dma;

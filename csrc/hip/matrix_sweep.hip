@@ -87,7 +87,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "hip/sweep_common.h"
+#include "hip/part_sweep.h"
 
 #define XS_ERR_BUF g_matrix_err
 #define XS_HD __host__ __device__ __forceinline__
@@ -559,8 +559,6 @@ int expected(uint32_t format_mask, Expect* e) {
   return 0;
 }
 
-bool bad_mask(uint32_t m) { return m == 0 || (m & ~kAllFormats); }
-
 }  // namespace
 
 extern "C" {
@@ -621,7 +619,7 @@ int xs_matrix_tile(int dev, int fmt, double* out) {
 // Host only. out[f] = the workgroup digest a healthy CU leaves for format f,
 // 0 for a format outside format_mask (out holds one word per format).
 int xs_matrix_sweep_expected(uint32_t format_mask, uint32_t* out) {
-  if (bad_mask(format_mask) || !out) return kBadArgs;
+  if (bad_part_mask(format_mask, kAllFormats) || !out) return kBadArgs;
   Expect e;
   if (int rc = expected(format_mask, &e)) return rc;
   for (int f = 0; f < kNumFmt; ++f) {
@@ -636,7 +634,7 @@ int xs_matrix_sweep_expected(uint32_t format_mask, uint32_t* out) {
 // bad arguments (nothing is launched), or a negative HIP error.
 int xs_matrix_sweep(int dev, int blocks, uint32_t format_mask, int inject_xcd, int inject_cu, uint32_t inject_formats,
                     void* records_out, int* n_records, double* ms) {
-  if (bad_mask(format_mask) || (inject_formats & ~kAllFormats) || blocks == 0) return kBadArgs;
+  if (bad_part_mask(format_mask, kAllFormats) || (inject_formats & ~kAllFormats) || blocks == 0) return kBadArgs;
   Expect e;
   if (int rc = expected(format_mask, &e)) return rc;
   return launch_sweep(g_matrix_err, {dev, blocks, inject_xcd, inject_cu, records_out, n_records, ms},

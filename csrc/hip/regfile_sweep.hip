@@ -297,9 +297,7 @@ int xs_regfile_sweep_expected(uint32_t seed, uint32_t* out) {
 // out3 = {numRegs as the runtime reports it, scratch bytes per lane, active
 // 256-thread workgroups per CU}.
 int xs_regfile_sweep_info(int dev, int* out3) {
-  if (!out3) return kBadArgs;
-  XS_CHECK(hipSetDevice(dev));
-  return kernel_info(g_regfile_err, reinterpret_cast<const void*>(k_regfile_sweep), kBlock, 0, out3);
+  return sweep_info(g_regfile_err, dev, reinterpret_cast<const void*>(k_regfile_sweep), kBlock, false, out3);
 }
 
 // One sweep launch of `blocks` workgroups (0: 4 per CU). Writes `blocks`

@@ -138,6 +138,17 @@ inline int kernel_info(ErrBuf& err, const void* kernel, int block, size_t smem, 
   return 0;
 }
 
+// An xs_*_sweep_info: kernel_info() of a sweep kernel on `dev`, launched with
+// exclusive_lds() when `exclusive` is set and with no dynamic LDS otherwise.
+inline int sweep_info(ErrBuf& err, int dev, const void* kernel, int threads, bool exclusive, int* out) {
+  if (!out) return kBadArgs;
+  XS_CHECK(hipSetDevice(dev));
+  size_t smem = 0;
+  if (exclusive)
+    if (int rc = exclusive_lds(err, dev, 0, &smem)) return rc;
+  return kernel_info(err, kernel, threads, smem, out);
+}
+
 // The arguments every xs_*_sweep takes.
 struct SweepCall {
   int dev, blocks;  // blocks 0: 4 per CU
@@ -195,6 +206,16 @@ int launch_sweep(ErrBuf& err, const SweepCall& c, const void* kernel, int thread
   if (c.n_records) *c.n_records = blocks;
   if (c.ms) *c.ms = t;
   return 0;
+}
+
+// One workgroup of a sweep's probe kernel, which stores every word it
+// received: a sweep launch of one workgroup whose record is the dump of
+// `n_words`, copied to `out`.
+template <typename Launch, typename Prepare = NoPrepare>
+int launch_probe(ErrBuf& err, int dev, const void* kernel, int threads, size_t lds_used, uint32_t* out,
+                 size_t n_words, Launch&& launch, Prepare&& prepare = Prepare{}) {
+  return launch_sweep(err, {dev, 1, -1, -1, out, nullptr, nullptr}, kernel, threads, lds_used, n_words * 4, launch,
+                      prepare);
 }
 
 #undef XS_ERR_BUF

@@ -85,16 +85,14 @@
 // for everything else) and uploads it: [unit][round][row][256], row = the
 // words of the unit's steps in order. The device compares by integer equality,
 // counts mismatches per unit and accumulates D_u += got * (2 idx + 1), idx =
-// (round * rows_u + row) * 256 + t (lane_sweep.hip's rule). Counts and digests
-// are combined through plain ds_write_b32 / ds_read_b32 and a barrier and
-// summed by thread 0. A digest that differs from the host's sets the fail bit
-// too. The comparator leans on global loads, v_cmp_eq_u32 and the integer
-// VALU that builds operands: a fault there is a mis-compare, not a pass.
+// (round * rows_u + row) * 256 + t (lane_sweep.hip's rule); part_sweep.h's
+// reduce_parts() makes the workgroup's record of them. The comparator leans
+// on global loads, v_cmp_eq_u32 and the integer VALU that builds operands: a
+// fault there is a mis-compare, not a pass.
 //
-// Record (128 bytes per workgroup, vector stores): xcd, cu, simd_mask, fail
-// (bit = unit), eight bad counts, eight digests (0 when not selected),
-// bad_simds, a reserved word, and six words of bits over the global step index
-// (the order of VALU_STEPS) of the steps that mis-compared.
+// Record (128 bytes per workgroup): part_sweep.h's head with a unit per part, a
+// reserved word, and six words of bits over the global step index (the order
+// of VALU_STEPS) of the steps that mis-compared.
 //
 // Injection: a workgroup on inject_xcd whose CU key is inject_cu (any with
 // -1; -1 for inject_xcd means none; values below -1 are refused) flips bit 0
@@ -127,7 +125,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "hip/sweep_common.h"
+#include "hip/part_sweep.h"
 
 #define XS_ERR_BUF g_valu_err
 #define XS_HD __host__ __device__ __forceinline__
@@ -144,7 +142,7 @@ using namespace xsprobe;
 constexpr int kNumUnits = 8;
 const char kUnitNames[] = "f32,f64,f16,int,bit,dot,cvt,trans";
 constexpr uint32_t kAllUnits = (1u << kNumUnits) - 1;
-constexpr int kBlock = 256;
+constexpr int kBlock = kPartBlock;
 constexpr int kMaxRounds = 64;
 
 enum Kind : int {
@@ -163,14 +161,6 @@ XS_HD constexpr bool is64(int k) {
 }
 
 // ------------------------------------------------------------------ operands
-XS_HD uint32_t fmix32(uint32_t h) {
-  h ^= h >> 16;
-  h *= 0x85ebca6bu;
-  h ^= h >> 13;
-  h *= 0xc2b2ae35u;
-  h ^= h >> 16;
-  return h;
-}
 XS_HD uint32_t hashv(uint32_t seed, uint32_t u, uint32_t s, uint32_t r, uint32_t o, uint32_t t) {
   return fmix32(seed ^ (u << 28 | s << 20 | r << 12 | o << 8 | t));
 }
@@ -963,31 +953,23 @@ static_assert(units_in_order(), "VALU_STEPS lists the units in order, none empty
 // Words of the expected table before unit u's: [unit][round][row][256].
 XS_HD size_t table_offset(int u, uint32_t rounds) { return static_cast<size_t>(rows_before(u)) * rounds * kBlock; }
 
-constexpr uint32_t kRedWords = 2 * kNumUnits + 2 + 6;  // per thread: bad[8], digest[8], bad simd, simd, step mask[6]
-constexpr uint32_t kLdsUsed = kRedWords * kBlock * 4;
+constexpr uint32_t kLdsUsed = part_reduction_words(kNumUnits, 6) * 4;  // the step mask is reduced too
 
 struct ValuRecord {
-  uint32_t xcd, cu, simd_mask, fail;
-  uint32_t bad[kNumUnits];
-  uint32_t digest[kNumUnits];
-  uint32_t bad_simds, reserved;
+  PartRecordHead<kNumUnits> head;
+  uint32_t reserved;
   uint32_t bad_steps[6];
   uint32_t pad[4];
 };
 static_assert(sizeof(ValuRecord) == 128, "one 128-byte record per workgroup");
 
-struct Expect {
-  uint32_t digest[kNumUnits];
-};
+using Expect = PartExpect<kNumUnits>;
 
 // ------------------------------------------------------------------- device
 struct Ctx {
   uint32_t seed, t, rounds, inj;
   const uint32_t* want;  // the whole expected table
   uint32_t* dump;        // k_valu_probe only
-};
-struct Tally {
-  uint32_t bad = 0, digest = 0;
 };
 
 template <int K>
@@ -1017,13 +999,7 @@ XS_D void run_step(const Ctx& c, Tally& y, uint32_t (&stepbad)[6], uint32_t r, F
 #pragma unroll
   for (int w = 0; w < si.words; ++w) {
     const uint32_t idx = (r * rows + row + w) * kBlock + c.t;
-    uint32_t got = static_cast<uint32_t>(v >> (32 * w));
-    if (((c.inj >> u) & 1u) && idx == 0) got ^= 1u;
-    if (c.dump) c.dump[idx] = got;
-    const uint32_t ne = got != want[idx];
-    miss |= ne;
-    y.bad += ne;
-    y.digest += got * (2u * idx + 1u);
+    miss |= take_word(y, c.dump, idx, static_cast<uint32_t>(v >> (32 * w)), want[idx], (c.inj >> u) & 1u);
   }
   if (miss) stepbad[G / 32] |= 1u << (G % 32);
 }
@@ -1074,42 +1050,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(2))) voi
   uint32_t stepbad[6] = {};
   run_units(c, unit_mask, y, stepbad);
 
-  // The reduction: plain LDS words and a barrier, summed by thread 0.
-  __syncthreads();
-  uint32_t any = 0;
-#pragma unroll
-  for (int p = 0; p < kNumUnits; ++p) {
-    valu_lds[p * kBlock + t] = y[p].bad;
-    valu_lds[(kNumUnits + p) * kBlock + t] = y[p].digest;
-    any |= y[p].bad;
-  }
-  valu_lds[2 * kNumUnits * kBlock + t] = any ? 1u << simd : 0u;
-  valu_lds[(2 * kNumUnits + 1) * kBlock + t] = 1u << simd;
-#pragma unroll
-  for (int q = 0; q < 6; ++q) valu_lds[(2 * kNumUnits + 2 + q) * kBlock + t] = stepbad[q];
-  __syncthreads();
-  if (t == 0) {
-    uint32_t sum[kRedWords] = {};
-    for (int u = 0; u < kBlock; ++u) {
-#pragma unroll
-      for (uint32_t q = 0; q < 2 * kNumUnits; ++q) sum[q] += valu_lds[q * kBlock + u];
-#pragma unroll
-      for (uint32_t q = 2 * kNumUnits; q < kRedWords; ++q) sum[q] |= valu_lds[q * kBlock + u];
-    }
-    uint32_t fail = 0;
-#pragma unroll
-    for (int p = 0; p < kNumUnits; ++p)
-      if (((unit_mask >> p) & 1u) && (sum[p] || sum[kNumUnits + p] != expect.digest[p])) fail |= 1u << p;
-    u32x4* out = reinterpret_cast<u32x4*>(&records[blockIdx.x]);
-    out[0] = u32x4{xcd, cu, sum[2 * kNumUnits + 1], fail};
-    out[1] = u32x4{sum[0], sum[1], sum[2], sum[3]};
-    out[2] = u32x4{sum[4], sum[5], sum[6], sum[7]};
-    out[3] = u32x4{sum[8], sum[9], sum[10], sum[11]};
-    out[4] = u32x4{sum[12], sum[13], sum[14], sum[15]};
-    out[5] = u32x4{sum[2 * kNumUnits], 0u, sum[18], sum[19]};
-    out[6] = u32x4{sum[20], sum[21], sum[22], sum[23]};
-    out[7] = u32x4{0u, 0u, 0u, 0u};
-  }
+  reduce_parts<kNumUnits, 6>(valu_lds, t, simd, y, stepbad, unit_mask, expect, xcd, cu, &records[blockIdx.x]);
 }
 
 // One workgroup; dump holds rounds x rows x 256 words of unit `unit`.
@@ -1196,7 +1137,6 @@ const Table& table(uint32_t seed, uint32_t rounds) {
   return g_table;
 }
 
-bool bad_mask(uint32_t m) { return m == 0 || (m & ~kAllUnits); }
 bool bad_rounds(uint32_t r) { return r < 1 || r > kMaxRounds; }
 
 int upload_table(uint32_t seed, uint32_t rounds, DevMem& buf, Expect* e, uint32_t mask) {
@@ -1254,23 +1194,20 @@ int xs_valu_probe(int dev, int unit, uint32_t seed, uint32_t rounds, uint32_t* o
   if (unit < 0 || unit >= kNumUnits || !out || bad_rounds(rounds)) return kBadArgs;
   const size_t n = static_cast<size_t>(unit_rows(unit)) * rounds * kBlock;
   if (n_words != n) return kBadArgs;
-  XS_CHECK(hipSetDevice(dev));
-  DevMem want, dump;
-  if (int rc = upload_table(seed, rounds, want, nullptr, 0)) return rc;
-  XS_CHECK(hipMalloc(&dump.p, n * 4));
-  XS_CHECK(hipMemset(dump.p, 0xff, n * 4));
-  hipLaunchKernelGGL(k_valu_probe, dim3(1), dim3(kBlock), 0, 0, dump.as<uint32_t>(), want.as<const uint32_t>(), unit,
-                     seed, rounds);
-  XS_CHECK(hipGetLastError());
-  XS_CHECK(hipDeviceSynchronize());
-  XS_CHECK(hipMemcpy(out, dump.p, n * 4, hipMemcpyDeviceToHost));
-  return 0;
+  DevMem want;
+  return launch_probe(
+      g_valu_err, dev, reinterpret_cast<const void*>(k_valu_probe), kBlock, 0, out, n,
+      [&](dim3 grid, dim3 block, size_t smem, void* dump) {
+        hipLaunchKernelGGL(k_valu_probe, grid, block, smem, 0, static_cast<uint32_t*>(dump), want.as<const uint32_t>(),
+                           unit, seed, rounds);
+      },
+      [&] { return upload_table(seed, rounds, want, nullptr, 0); });
 }
 
 // Host only. out8[u] = the workgroup digest a healthy CU leaves for unit u, 0
 // for a unit outside unit_mask.
 int xs_valu_sweep_expected(uint32_t unit_mask, uint32_t seed, uint32_t rounds, uint32_t* out8) {
-  if (bad_mask(unit_mask) || bad_rounds(rounds) || !out8) return kBadArgs;
+  if (bad_part_mask(unit_mask, kAllUnits) || bad_rounds(rounds) || !out8) return kBadArgs;
   std::lock_guard<std::mutex> g(g_table_mu);
   const Table& tb = table(seed, rounds);
   for (int u = 0; u < kNumUnits; ++u) out8[u] = (unit_mask >> u) & 1u ? tb.digest[u] : 0u;
@@ -1281,11 +1218,7 @@ int xs_valu_sweep_expected(uint32_t unit_mask, uint32_t seed, uint32_t rounds, u
 // lane, scratch bytes per lane, dynamic LDS bytes per workgroup, workgroups
 // that fit on a CU at once}.
 int xs_valu_sweep_info(int dev, int* out4) {
-  if (!out4) return kBadArgs;
-  XS_CHECK(hipSetDevice(dev));
-  size_t smem = 0;
-  if (int rc = exclusive_lds(g_valu_err, dev, 0, &smem)) return rc;
-  return kernel_info(g_valu_err, reinterpret_cast<const void*>(k_valu_sweep), kBlock, smem, out4);
+  return sweep_info(g_valu_err, dev, reinterpret_cast<const void*>(k_valu_sweep), kBlock, true, out4);
 }
 
 // One sweep launch of `blocks` workgroups (0: 4 per CU). Writes `blocks`
@@ -1294,7 +1227,7 @@ int xs_valu_sweep_info(int dev, int* out4) {
 // launched), or a negative HIP error.
 int xs_valu_sweep(int dev, int blocks, uint32_t unit_mask, uint32_t seed, uint32_t rounds, int inject_xcd,
                   int inject_cu, uint32_t inject_units, void* records_out, int* n_records, double* ms) {
-  if (bad_mask(unit_mask) || bad_rounds(rounds) || (inject_units & ~kAllUnits)) return kBadArgs;
+  if (bad_part_mask(unit_mask, kAllUnits) || bad_rounds(rounds) || (inject_units & ~kAllUnits)) return kBadArgs;
   Expect e;
   DevMem want;
   return launch_sweep(

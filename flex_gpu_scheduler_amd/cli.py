@@ -339,32 +339,37 @@ def _gib_or_all(s: str):
     return gib
 
 
+def _part_list_flag(args, kind: str, parts: str) -> dict:
+    """hip_health_fn's keywords <kind> and <kind>_<parts> from the comma-list
+    flag --health-<kind>-sweep: none when it is absent, every part (None) when
+    it is bare, else the list."""
+    v = getattr(args, f"health_{kind}_sweep", None)
+    if v is None:
+        return {}
+    return {kind: True, f"{kind}_{parts}": None if v == "all" else [f.strip() for f in v.split(",") if f.strip()]}
+
+
 def health_fn_args(args) -> dict:
     """hip_health_fn's keywords from the node-agent flags.
-    --health-matrix-sweep: absent -> None, bare -> "all", else a comma list.
+    --health-matrix-sweep, --health-lane-sweep, --health-valu-sweep: as
+    _part_list_flag says, but the matrix keys are always there (False, None).
     --health-hbm-sweep: absent -> no hbm keys, bare -> all free HBM less the
     reserve (hbm_gib None), else that many GiB.
-    --health-register-sweep: absent -> no regfile key.
-    --health-lane-sweep: absent -> no lane keys, bare -> every path
-    (lane_paths None), else a comma list.
-    --health-valu-sweep: absent -> no valu keys, bare -> every unit
-    (valu_units None), else a comma list."""
-    m = args.health_matrix_sweep
-    formats = None if m in (None, "all") else [f.strip() for f in m.split(",") if f.strip()]
-    kw = {"sweep": args.health_sweep, "sweep_period_s": args.health_sweep_period, "matrix": m is not None,
-          "matrix_formats": formats}
+    --health-register-sweep: absent -> no regfile key."""
+    kw = {"sweep": args.health_sweep, "sweep_period_s": args.health_sweep_period, "matrix": False,
+          "matrix_formats": None, **_part_list_flag(args, "matrix", "formats")}
     h = getattr(args, "health_hbm_sweep", None)
     if h is not None:
         kw.update(hbm=True, hbm_gib=None if h == "all" else float(h))
     if getattr(args, "health_register_sweep", False):
         kw.update(regfile=True)
-    ln = getattr(args, "health_lane_sweep", None)
-    if ln is not None:
-        kw.update(lane=True, lane_paths=None if ln == "all" else [f.strip() for f in ln.split(",") if f.strip()])
-    vu = getattr(args, "health_valu_sweep", None)
-    if vu is not None:
-        kw.update(valu=True, valu_units=None if vu == "all" else [f.strip() for f in vu.split(",") if f.strip()])
+    kw.update(**_part_list_flag(args, "lane", "paths"), **_part_list_flag(args, "valu", "units"))
     return kw
+
+
+def wants_health_fn(args) -> bool:
+    """--health-probe, or a sweep flag, which implies it: a sweep's switch is the only True among the keywords."""
+    return args.health_probe or any(v is True for v in health_fn_args(args).values())
 
 
 def cmd_node_agent(args) -> int:
@@ -380,11 +385,7 @@ def cmd_node_agent(args) -> int:
                       heartbeat=args.heartbeat, telemetry_period=args.telemetry_period,
                       publish_metrics=not args.no_telemetry, reserved_cpu=args.reserved_cpu,
                       reserved_memory_gib=args.reserved_memory_gib,
-                      health_fn=(hip_health_fn(**health_fn_args(args))
-                                 if args.health_probe or args.health_sweep or args.health_matrix_sweep is not None
-                                 or args.health_hbm_sweep is not None or args.health_register_sweep
-                                 or args.health_lane_sweep is not None
-                                 or getattr(args, "health_valu_sweep", None) is not None else None),
+                      health_fn=hip_health_fn(**health_fn_args(args)) if wants_health_fn(args) else None,
                       bandwidth_fn=hip_bandwidth_fn() if args.bandwidth_probe else None,
                       kubelet_managed=args.kubelet_managed).start()
     if args.device_plugin:

@@ -60,17 +60,43 @@ class FaultKind:
     withholds_gpu: bool = False
 
 
+def _register_fault(v: dict) -> dict:
+    return {"files": list(v["failed_files"]), "cells": int(v["bad_cells"]), "flipMask": v["flip_mask"],
+            "simds": sum(len(sm) for sm in v["bad_simds"].values())} if v["failed_files"] else {}
+
+
+@dataclass(frozen=True)
+class SweepKind:
+    """One per-CU sweep of hip_health_fn, whose parameter `enabled_by` switches
+    it on, <enabled_by>_args being the keywords of the probe's `method` and
+    <enabled_by>_<selection> the parts for its keyword `selection`. `label`
+    starts its log line; `summary_key` and `faults_key` are the keys of the
+    verdict's detail for the summary and for {xcd: fault}; `fault_of` reads
+    one XCD's fault (empty: none) from its entry of the summary. The CU sweep
+    names no fault kind: its log line shows the bad XCDs."""
+    enabled_by: str
+    method: str
+    label: str
+    summary_key: str
+    selection: str | None = None
+    faults_key: str | None = None
+    fault_of: Callable[[dict], "list | dict"] | None = None
+
+
+# In the order they run; hip_health_fn's docstring has the shape of each fault.
+SWEEP_KINDS = (
+    SweepKind("sweep", "cu_sweep", "cu", "sweep"),
+    SweepKind("matrix", "matrix_sweep", "matrix", "matrixSweep", "formats", "matrixFaults",
+              lambda v: list(v["failed_formats"])),
+    SweepKind("regfile", "regfile_sweep", "register", "registerSweep", None, "registerFaults", _register_fault),
+    SweepKind("lane", "lane_sweep", "lane", "laneSweep", "paths", "laneFaults", lambda v: list(v["failed_paths"])),
+    SweepKind("valu", "valu_sweep", "valu", "valuSweep", "units", "valuFaults", lambda v: list(v["failed_units"])),
+)
+
 FAULT_KINDS = {
-    # The matrix formats a faulty XCD mis-computes (the matrix-format sweep):
-    # {xcd: [format, ...]}. Informational, as the next two are: the XCD is
+    # What the per-CU sweeps found on a faulty XCD. Informational: the XCD is
     # fenced through xcdFaults; these are for operators and RMA tooling.
-    "matrixFaults": FaultKind(per_xcd=True),
-    # What the register-file sweep found: {xcd: {"files", "cells", "flipMask", "simds"}}.
-    "registerFaults": FaultKind(per_xcd=True),
-    # The cross-lane and LDS paths a faulty XCD gets wrong (the lane sweep): {xcd: [path, ...]}.
-    "laneFaults": FaultKind(per_xcd=True),
-    # The vector-ALU units a faulty XCD mis-computes (the VALU sweep): {xcd: [unit, ...]}.
-    "valuFaults": FaultKind(per_xcd=True),
+    **{k.faults_key: FaultKind(per_xcd=True) for k in SWEEP_KINDS if k.faults_key},
     # What the HBM sweep found on the GPU. The sweep knows a fault by its
     # virtual address, which cannot be tied to the HBM slice of one compute
     # partition, so there is no partial fence for memory.
@@ -423,28 +449,17 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
     """Health callback backed by the HIP probes (HBM pattern + checksum and an
     MFMA tile check per GPU).
 
-    `sweep`: also run the CU sweep (HipProbe.cu_sweep, `sweep_args` are its
-    keywords), which checks MFMA, VALU and LDS on every CU. `matrix`: also run
-    the matrix-format sweep (HipProbe.matrix_sweep over `matrix_formats`, None
-    for all; `matrix_args` are its other keywords), which runs f16, f32, f64,
-    fp8, bf8, i8 and the block-scaled MX formats on every CU. `regfile`: also
-    run the register-file sweep (HipProbe.regfile_sweep, `regfile_args` are its
-    keywords), which writes and reads back every VGPR and AGPR of every SIMD.
-    `lane`: also run the lane sweep (HipProbe.lane_sweep over `lane_paths`,
-    None for all; `lane_args` are its other keywords), which moves hashed
-    values through the DPP shifters, the permlane swaps, readlane / writelane,
-    the LDS crossbar and the wide, sub-dword, transposed, atomic and DMA LDS
-    paths of every CU; detail["laneFaults"] = {xcd: [path, ...]}.
-    `valu`: also run the VALU sweep (HipProbe.valu_sweep over `valu_units`,
-    None for all; `valu_args` are its other keywords), which issues the f32,
-    f64, f16, wide-integer, bit-field, dot, conversion and transcendental
-    instructions of every SIMD on hashed operands; detail["valuFaults"] =
-    {xcd: [unit, ...]}, the step names are in detail["valuSweep"].
+    Each kind of SWEEP_KINDS has a switch `<kind>` that also runs that per-CU
+    sweep of HipProbe (`sweep`: the CU sweep), `<kind>_args` for its keywords
+    and, where it sweeps named parts, `<kind>_<parts>` to select some (None for
+    all). Its summary and, the CU sweep apart, its {xcd: fault} go into the
+    verdict's detail under the kind's keys. A fault is the list of the failed
+    formats, paths or units; of `regfile`, {"files": [...], "cells": n,
+    "flipMask": "0x...", "simds": n}. The VALU sweep's failed steps are in
+    detail["valuSweep"].
     The callback runs on every heartbeat, so the sweeps' verdict is reused for
     `sweep_period_s`. On a device that shows all 8 XCDs the verdict is a
-    GpuHealth naming the bad physical XCDs of any of these sweeps, with
-    detail["matrixFaults"] = {xcd: [format, ...]} and detail["registerFaults"]
-    = {xcd: {"files": [...], "cells": n, "flipMask": "0x...", "simds": n}}; a
+    GpuHealth naming the bad physical XCDs of any of these sweeps; a
     partition device numbers its XCDs logically, so there a failed sweep fails
     the device as a whole (a plain bool). CUs a sweep could not reach are
     logged, never counted as failed.
@@ -459,30 +474,14 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
     publishes); the agent withholds such a GPU as a whole. A device on which no
     memory could be had is logged as unswept and a sweep that got less than it
     asked for as short; neither fails the device."""
+    given = locals()  # the parameters by name, for SWEEP_KINDS
     from ..ops.hip_probe import HBM_UNSWEPT, ProbeError, probe
 
     p = probe()
     last: dict[int, tuple[float, object]] = {}  # dev -> (monotonic time, sweep verdict)
-
-    def register_fault(v: dict) -> dict:
-        return {"files": list(v["failed_files"]), "cells": int(v["bad_cells"]), "flipMask": v["flip_mask"],
-                "simds": sum(len(sm) for sm in v["bad_simds"].values())} if v["failed_files"] else {}
-
-    # In the order they run: enabled, the probe's method, its keywords, the
-    # fault of one XCD from its entry of the summary (empty: none; None: the
-    # sweep publishes no fault kind), the label of the log line, and the keys
-    # of the verdict's detail for the summary and for {xcd: fault}.
-    per_cu_sweeps = [
-        (sweep, "cu_sweep", dict(sweep_args or {}), None, "cu", "sweep", None),
-        (matrix, "matrix_sweep", dict(formats=matrix_formats, **(matrix_args or {})),
-         lambda v: list(v["failed_formats"]), "matrix", "matrixSweep", "matrixFaults"),
-        (regfile, "regfile_sweep", dict(regfile_args or {}), register_fault, "register", "registerSweep",
-         "registerFaults"),
-        (lane, "lane_sweep", dict(paths=lane_paths, **(lane_args or {})),
-         lambda v: list(v["failed_paths"]), "lane", "laneSweep", "laneFaults"),
-        (valu, "valu_sweep", dict(units=valu_units, **(valu_args or {})),
-         lambda v: list(v["failed_units"]), "valu", "valuSweep", "valuFaults"),
-    ]
+    # The enabled kinds, each with the keywords of its probe method.
+    per_cu_sweeps = [(k, {**({k.selection: given[f"{k.enabled_by}_{k.selection}"]} if k.selection else {}),
+                          **(given[f"{k.enabled_by}_args"] or {})}) for k in SWEEP_KINDS if given[k.enabled_by]]
 
     def sweep_verdict(dev: int):
         now = time.monotonic()
@@ -490,22 +489,20 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
             return last[dev][1]
         bad: set[int] = set()
         detail: dict = {}
-        for on, run, keywords, fault_of, label, summary_key, faults_key in per_cu_sweeps:
-            if not on:
-                continue
-            s = getattr(p, run)(dev, **keywords)["summary"]
-            # The cu sweep names no fault kind: its log line shows the bad XCDs.
+        for k, keywords in per_cu_sweeps:
+            s = getattr(p, k.method)(dev, **keywords)["summary"]
+            fault_of = k.fault_of
             found = {int(x): fault_of(v) for x, v in s["xcds"].items() if fault_of(v)} if fault_of else s["bad_xcds"]
             log.log(logging.WARNING if s["bad_xcds"] else logging.INFO,
                     "%s sweep GPU %d: %d CUs on %d XCDs in %.2f ms (%d launch(es)), covered=%s uncovered=%s "
-                    "%s=%s", label, dev, s["cus_seen"], len(s["xcds"]), s["ms"], s["rounds"], s["covered"],
+                    "%s=%s", k.label, dev, s["cus_seen"], len(s["xcds"]), s["ms"], s["rounds"], s["covered"],
                     {x: n for x, n in s["uncovered"].items() if n}, "bad_xcds" if fault_of is None else "faults", found)
             if s.get("failed_steps"):
-                log.warning("%s sweep GPU %d: failed steps %s", label, dev, s["failed_steps"])
+                log.warning("%s sweep GPU %d: failed steps %s", k.label, dev, s["failed_steps"])
             bad |= set(s["bad_xcds"])
-            detail[summary_key] = s
-            if faults_key:
-                detail[faults_key] = found
+            detail[k.summary_key] = s
+            if k.faults_key:
+                detail[k.faults_key] = found
         hbm_faults: dict = {}
         if hbm:
             h = None
@@ -542,7 +539,7 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
         # HBM pattern/checksum and an exact-integer MFMA tile: a GPU whose matrix
         # cores mis-compute is withheld even if its memory checks out.
         ok = bool(p.health(dev)["healthy"]) and bool(p.mfma_check(dev)["healthy"])
-        if not (sweep or matrix or hbm or regfile or lane or valu) or not ok:
+        if not (per_cu_sweeps or hbm) or not ok:
             return ok
         return sweep_verdict(dev)
 

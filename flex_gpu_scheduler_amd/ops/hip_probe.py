@@ -1,25 +1,29 @@
-"""ctypes front-end for the HIP/CDNA4 device probes (csrc/hip/hbm_probe.hip,
-csrc/hip/mfma_probe.hip, csrc/hip/cu_sweep.hip, csrc/hip/matrix_sweep.hip,
-csrc/hip/hbm_sweep.hip, csrc/hip/regfile_sweep.hip, csrc/hip/lane_sweep.hip,
-csrc/hip/valu_sweep.hip).
+"""ctypes front-end for the HIP/CDNA4 device probes: what the node agent runs
+before it advertises an MI355X as schedulable.
 
-The probes are what the node agent runs before advertising an MI355X as
-schedulable: device properties, HBM streaming bandwidth (optionally with a
-partition-sized CU budget), an XCD census that verifies the compute-partition
-mode, a checksum health test, an exact-integer MFMA tile check of the matrix
-cores, the dense bf16 MFMA throughput of the whole GPU or of one
-partition's XCDs, and a sweep that checks MFMA, VALU and LDS on every CU and
-names the XCD of a CU that mis-computes, and a sweep that runs every matrix
-format (f16, f32, f64, fp8, bf8, i8 and the block-scaled MX fp8/fp6/fp4) on
-every CU and names the formats a CU gets wrong, and a sweep of all free HBM
-with an address-keyed pattern in both polarities that names the vectors and
-bits that read back wrong, and a sweep of every SIMD's whole VGPR/AGPR file
-that names the register file, the cells and the SIMDs that read back wrong,
-and a sweep of every CU's cross-lane network (DPP, permlane swaps, readlane /
-writelane, the LDS crossbar) and wide, sub-dword, transposed, atomic and DMA
-LDS paths that names the paths a CU gets wrong, and a sweep of every SIMD's
-vector ALU (float, packed, wide-integer, bit-field, dot, conversion and
-transcendental instructions) that names the units and steps a CU gets wrong.
+Probes (csrc/hip/hbm_probe.hip, csrc/hip/mfma_probe.hip): device properties;
+HBM streaming bandwidth, optionally with a partition-sized CU budget or on a
+partition's XCDs; an XCD census that verifies the compute-partition mode; a
+checksum health test; an exact-integer MFMA tile check of the matrix cores;
+the dense bf16 MFMA throughput of the whole GPU or of one partition's XCDs.
+
+Sweeps of every CU (csrc/hip/<name>.hip), each naming the XCD of a CU that fails:
+  * cu_sweep: MFMA, VALU and LDS;
+  * matrix_sweep: every matrix format (f16, f32, f64, fp8, bf8, i8 and the
+    block-scaled MX fp8/fp6/fp4); names the formats;
+  * regfile_sweep: every SIMD's whole VGPR/AGPR file; names the register
+    file, the cells and the SIMDs;
+  * lane_sweep: the cross-lane network (DPP, permlane swaps, readlane /
+    writelane, the LDS crossbar) and the wide, sub-dword, transposed, atomic
+    and DMA LDS paths; names the paths;
+  * valu_sweep: every SIMD's vector ALU (float, packed, wide-integer,
+    bit-field, dot, conversion and transcendental instructions); names the
+    units and the steps.
+The matrix, lane and VALU sweeps are sweeps over named parts: PART_SWEEPS
+describes each, and one implementation serves the three.
+
+hbm_sweep (csrc/hip/hbm_sweep.hip): all free HBM under an address-keyed
+pattern in both polarities; names the vectors and bits that read back wrong.
 """
 from __future__ import annotations
 
@@ -98,6 +102,36 @@ VALU_RECORD_WORDS = 32
 VALU_SEED = 0x1B873593
 VALU_ROUNDS = 2  # operand sets per step; measured in profiles/valu_sweep_defaults.md
 VALU_BLOCK = 256
+
+
+@dataclass(frozen=True)
+class PartSweep:
+    """A sweep over named parts: a bit mask selects parts, the selected ones run
+    on every CU, a record's fail bits are part bits and it carries one digest
+    per part. Its C ABI is xs_<prefix>_sweep(dev, blocks, mask, [seed,
+    [rounds,]] inject xcd, cu, mask, records, n, ms), xs_<prefix>_sweep_expected(
+    mask, [seed, [rounds,]] digests) and xs_<prefix>_shape(part, out)."""
+    prefix: str
+    names_symbol: str  # returns the part names, comma-separated, in bit order
+    noun: str  # a part, in error messages
+    summary_key: str  # the failed parts, in the summary
+    selection: str  # the selected parts, in the summary
+    record_words: int
+    digests: int  # word offset of the first part's digest in a record; so the next three, where it has them
+    bad: int | None = None  # a mismatch count per part
+    bad_simds: int | None = None
+    step_mask: int | None = None  # bits over the global step index
+
+
+PART_SWEEPS = {
+    "matrix": PartSweep("matrix", "xs_matrix_formats", "matrix format", "failed_formats", "formats",
+                        MATRIX_RECORD_WORDS, digests=4),
+    "lane": PartSweep("lane", "xs_lane_paths", "lane path", "failed_paths", "paths",
+                      LANE_RECORD_WORDS, digests=12, bad=4, bad_simds=20),
+    "valu": PartSweep("valu", "xs_valu_units", "VALU unit", "failed_units", "units",
+                      VALU_RECORD_WORDS, digests=12, bad=4, bad_simds=20, step_mask=22),
+}
+MATRIX_SWEEP, LANE_SWEEP, VALU_SWEEP = PART_SWEEPS.values()
 
 # k_hbm_fill / k_hbm_verify (csrc/hip/hbm_sweep.hip)
 HBM_SWEEP_SEED = 0x5EED1E55
@@ -184,6 +218,29 @@ def _inject_target(t: tuple | None) -> tuple[int, int]:
     """(xcd, cu key) of an `inject` / `poison` tuple as the C ABI takes them:
     -1 for no XCD (no tuple) and for every CU of the XCD (None)."""
     return (-1, -1) if t is None else (int(t[0]), -1 if t[1] is None else int(t[1]))
+
+
+def decode_part_record(kind: PartSweep, names: list[str], w, expected: dict, steps=()) -> dict:
+    """The record of one workgroup of a sweep over named parts from its words
+    `w`. `names`: the parts in bit order; `expected`: the host's digest per
+    selected part; `steps`: the step names in the order of the step mask's
+    bits. A digest that differs from the host's (0 for a part not selected) sets
+    the part's fail bit, even if the device's comparator, on the same CU, passed it."""
+    n = len(names)
+    digests = w[kind.digests:kind.digests + n]
+    rec = {"xcd": w[0], "cu": w[1], "simd_mask": w[2], "fail": w[3]}
+    if kind.bad is not None:
+        rec["bad"] = dict(zip(names, w[kind.bad:kind.bad + n]))
+    rec["digests"] = dict(zip(names, digests))
+    if kind.bad_simds is not None:
+        rec["bad_simds"] = w[kind.bad_simds]
+    if kind.step_mask is not None:
+        mask = w[kind.step_mask:kind.step_mask + (len(steps) + 31) // 32]  # seldom set: walk the steps only then
+        rec["bad_steps"] = [s for g, s in enumerate(steps) if mask[g // 32] >> (g % 32) & 1] if any(mask) else []
+    for b, f in enumerate(names):
+        if digests[b] != expected.get(f, 0):
+            rec["fail"] |= 1 << b
+    return rec
 
 
 class HipProbe:
@@ -640,6 +697,12 @@ class HipProbe:
 
 
     # ------------------------------------------------------ the per-CU sweeps
+    def _call(self, sweep: str, what: str, *args) -> None:
+        """xs_<what>(*args) of the file of <sweep>; a ProbeError unless it returns 0."""
+        rc = getattr(self.lib, f"xs_{what}")(*args)
+        if rc != 0:
+            raise _probe_error(getattr(self.lib, f"xs_{sweep}_last_error"), rc, what)
+
     def _sweep_until_covered(self, name: str, dev: int, blocks: int, max_rounds: int, words: int, launch, expected,
                              decode, summarize) -> dict:
         """The launch policy of every per-CU sweep. A launch whose grid could
@@ -690,9 +753,7 @@ class HipProbe:
     def cu_sweep_expected(self, k: int = 64, lds_bytes: int = SWEEP_LDS_MAX) -> dict:
         """The digests a healthy CU leaves, computed on the host."""
         out = (ctypes.c_uint32 * 3)()
-        rc = self.lib.xs_cu_sweep_expected(k, lds_bytes, out)
-        if rc != 0:
-            raise _probe_error(self.lib.xs_cu_sweep_last_error, rc, "cu_sweep_expected")
+        self._call("cu_sweep", "cu_sweep_expected", k, lds_bytes, out)
         return {"mfma": out[0], "valu": out[1], "lds": out[2]}
 
     def cu_sweep(self, dev: int = 0, blocks: int = 0, k: int = 64, lds_bytes: int | None = None,
@@ -724,23 +785,65 @@ class HipProbe:
         out["summary"].update(k=k, lds_bytes=lds_bytes)
         return out
 
+    # ---------------------------------------------- sweeps over named parts
+    def _part_names(self, kind: PartSweep) -> list[str]:
+        return getattr(self.lib, kind.names_symbol)().decode().split(",")
+
+    def _part_mask(self, kind: PartSweep, chosen) -> int:
+        return _name_mask(self._part_names(kind), chosen, kind.noun)
+
+    def _part_shape(self, kind: PartSweep, name: str, fields: int):
+        out = (ctypes.c_int * fields)()
+        self._part_mask(kind, [name])  # ValueError for a name the sweep does not have
+        self._call(f"{kind.prefix}_sweep", f"{kind.prefix}_shape", self._part_names(kind).index(name), out)
+        return out
+
+    def _part_expected(self, kind: PartSweep, chosen, *args) -> dict:
+        names = self._part_names(kind)
+        mask = self._part_mask(kind, chosen)
+        out = (ctypes.c_uint32 * len(names))()
+        self._call(f"{kind.prefix}_sweep", f"{kind.prefix}_sweep_expected", mask, *args, out)
+        return {n: out[i] for i, n in enumerate(names) if mask >> i & 1}
+
+    def _sweep_info(self, name: str, dev: int, fields: tuple) -> dict:
+        """xs_<name>_info: what the runtime reports for the sweep's kernel, under `fields`."""
+        out = (ctypes.c_int * len(fields))()
+        self._call(name, f"{name}_info", dev, out)
+        return dict(zip(fields, out))
+
+    def _part_sweep(self, kind: PartSweep, summarize, dev: int, blocks: int, chosen, inject, max_rounds: int,
+                    args: tuple = (), report: dict | None = None, steps=()) -> dict:
+        """One sweep over the `chosen` parts (None: all), its verdict being
+        summarize(records, compute_units, names). `args` stand between the mask
+        and the injection in the C call and behind the mask in that of the
+        expected digests; `report` goes into the summary before the selection."""
+        names = self._part_names(kind)
+        mask = self._part_mask(kind, chosen)
+        selected = [f for i, f in enumerate(names) if mask >> i & 1]
+        (ix, ic), im = _inject_target(inject), 0 if inject is None else self._part_mask(kind, inject[2])
+        sweep = getattr(self.lib, f"xs_{kind.prefix}_sweep")
+        out = self._sweep_until_covered(
+            f"{kind.prefix}_sweep", dev, blocks, max_rounds, kind.record_words,
+            lambda nb, *out: sweep(dev, nb, mask, *args, ix, ic, im, *out),
+            lambda: self._part_expected(kind, selected, *args),
+            lambda w, expected: decode_part_record(kind, names, w, expected, steps),
+            lambda records, cus: summarize(records, cus, names))
+        out["summary"].update(report or {}, **{kind.selection: selected})
+        return out
+
     # --------------------------------------------------------- matrix sweep
     def matrix_formats(self) -> list[str]:
         """Format names of the matrix sweep; the index is the format's bit."""
-        return self.lib.xs_matrix_formats().decode().split(",")
+        return self._part_names(MATRIX_SWEEP)
 
     def _matrix_mask(self, formats) -> int:
-        return _name_mask(self.matrix_formats(), formats, "matrix format")
+        return self._part_mask(MATRIX_SWEEP, formats)
 
     def matrix_shape(self, fmt: str) -> dict:
         """`tile` (the result is tile x tile), `k` (both K-steps), `blocks`
         (32-element scale blocks along K; 0 when not block-scaled),
         `accumulator` and `frac` (every result is a multiple of 2^-frac)."""
-        out = (ctypes.c_int * 5)()
-        self._matrix_mask([fmt])
-        rc = self.lib.xs_matrix_shape(self.matrix_formats().index(fmt), out)
-        if rc != 0:
-            raise _probe_error(self.lib.xs_matrix_sweep_last_error, rc, "matrix_shape")
+        out = self._part_shape(MATRIX_SWEEP, fmt, 5)
         return {"tile": out[0], "k": out[1], "blocks": out[2], "accumulator": ("f32", "f64", "i32")[out[3]],
                 "frac": out[4]}
 
@@ -757,10 +860,8 @@ class HipProbe:
         a, b = np.zeros((t, k), np.uint64), np.zeros((k, t), np.uint64)
         sa = np.zeros((t, nb), np.uint8) if nb else None
         sb = np.zeros((nb, t), np.uint8) if nb else None
-        rc = self.lib.xs_matrix_inputs(self.matrix_formats().index(fmt), a.ctypes.data, b.ctypes.data,
-                                       sa.ctypes.data if nb else None, sb.ctypes.data if nb else None)
-        if rc != 0:
-            raise _probe_error(self.lib.xs_matrix_sweep_last_error, rc, "matrix_inputs")
+        self._call("matrix_sweep", "matrix_inputs", self.matrix_formats().index(fmt), a.ctypes.data, b.ctypes.data,
+                   sa.ctypes.data if nb else None, sb.ctypes.data if nb else None)
         return {"a": a, "b": b, "a_scale": sa, "b_scale": sb, **sh}
 
     def matrix_tile(self, dev: int, fmt: str):
@@ -770,21 +871,13 @@ class HipProbe:
 
         sh = self.matrix_shape(fmt)
         out = np.zeros((sh["tile"], sh["tile"]), np.float64)
-        rc = self.lib.xs_matrix_tile(dev, self.matrix_formats().index(fmt), out.ctypes.data)
-        if rc != 0:
-            raise _probe_error(self.lib.xs_matrix_sweep_last_error, rc, "matrix_tile")
+        self._call("matrix_sweep", "matrix_tile", dev, self.matrix_formats().index(fmt), out.ctypes.data)
         return out.astype(np.int64) if sh["accumulator"] == "i32" else out
 
     def matrix_sweep_expected(self, formats=None) -> dict:
         """The workgroup digest a healthy CU leaves per selected format,
         computed on the host from the decoded operand encodings."""
-        names = self.matrix_formats()
-        mask = self._matrix_mask(formats)
-        out = (ctypes.c_uint32 * len(names))()
-        rc = self.lib.xs_matrix_sweep_expected(mask, out)
-        if rc != 0:
-            raise _probe_error(self.lib.xs_matrix_sweep_last_error, rc, "matrix_sweep_expected")
-        return {n: out[i] for i, n in enumerate(names) if mask >> i & 1}
+        return self._part_expected(MATRIX_SWEEP, formats)
 
     def matrix_sweep(self, dev: int = 0, formats=None, blocks: int = 0, inject: tuple | None = None,
                      max_rounds: int = 4) -> dict:
@@ -797,45 +890,20 @@ class HipProbe:
         Relaunched while some CU has not been seen, as cu_sweep does. Returns
         {"records": [...], "summary": summarize_matrix_sweep(...) plus rounds,
         ms, blocks, formats}."""
-        names = self.matrix_formats()
-        mask = self._matrix_mask(formats)
-        selected = [f for i, f in enumerate(names) if mask >> i & 1]
-        (ix, ic), im = _inject_target(inject), 0 if inject is None else self._matrix_mask(inject[2])
-
-        def decode(w, expected):
-            rec = {"xcd": w[0], "cu": w[1], "simd_mask": w[2], "fail": w[3],
-                   "digests": {f: w[4 + b] for b, f in enumerate(names)}}
-            for b, f in enumerate(names):
-                if rec["digests"][f] != expected.get(f, 0):
-                    rec["fail"] |= 1 << b
-            return rec
-
-        out = self._sweep_until_covered(
-            "matrix_sweep", dev, blocks, max_rounds, MATRIX_RECORD_WORDS,
-            lambda nb, *out: self.lib.xs_matrix_sweep(dev, nb, mask, ix, ic, im, *out),
-            lambda: self.matrix_sweep_expected(selected), decode,
-            lambda records, cus: summarize_matrix_sweep(records, cus, names))
-        out["summary"].update(formats=selected)
-        return out
+        return self._part_sweep(MATRIX_SWEEP, summarize_matrix_sweep, dev, blocks, formats, inject, max_rounds)
 
     # -------------------------------------------------- register-file sweep
     def regfile_sweep_expected(self, seed: int = REGFILE_SEED) -> int:
         """The workgroup digest a healthy CU leaves, computed on the host."""
         out = ctypes.c_uint32()
-        rc = self.lib.xs_regfile_sweep_expected(seed, ctypes.byref(out))
-        if rc != 0:
-            raise _probe_error(self.lib.xs_regfile_sweep_last_error, rc, "regfile_sweep_expected")
+        self._call("regfile_sweep", "regfile_sweep_expected", seed, ctypes.byref(out))
         return int(out.value)
 
     def regfile_sweep_info(self, dev: int = 0) -> dict:
         """What the runtime reports for k_regfile_sweep: `num_regs`,
         `scratch_bytes` per lane and `blocks_per_cu` (256-thread workgroups
         that fit on a CU at once)."""
-        out = (ctypes.c_int * 3)()
-        rc = self.lib.xs_regfile_sweep_info(dev, out)
-        if rc != 0:
-            raise _probe_error(self.lib.xs_regfile_sweep_last_error, rc, "regfile_sweep_info")
-        return {"num_regs": out[0], "scratch_bytes": out[1], "blocks_per_cu": out[2]}
+        return self._sweep_info("regfile_sweep", dev, ("num_regs", "scratch_bytes", "blocks_per_cu"))
 
     def regfile_sweep(self, dev: int = 0, blocks: int = 0, seed: int = REGFILE_SEED, inject: tuple | None = None,
                       poison: tuple | None = None, max_rounds: int = 4) -> dict:
@@ -880,18 +948,14 @@ class HipProbe:
     # ----------------------------------------------------------- lane sweep
     def lane_paths(self) -> list[str]:
         """Path names of the lane sweep; the index is the path's bit."""
-        return self.lib.xs_lane_paths().decode().split(",")
+        return self._part_names(LANE_SWEEP)
 
     def _lane_mask(self, paths) -> int:
-        return _name_mask(self.lane_paths(), paths, "lane path")
+        return self._part_mask(LANE_SWEEP, paths)
 
     def lane_shape(self, path: str) -> dict:
         """`steps` of one path and the `words` every thread receives per step."""
-        self._lane_mask([path])
-        out = (ctypes.c_int * 2)()
-        rc = self.lib.xs_lane_shape(self.lane_paths().index(path), out)
-        if rc != 0:
-            raise _probe_error(self.lib.xs_lane_sweep_last_error, rc, "lane_shape")
+        out = self._part_shape(LANE_SWEEP, path, 2)
         return {"steps": out[0], "words": out[1]}
 
     def lane_probe(self, dev: int, path: str, seed: int = LANE_SEED):
@@ -901,31 +965,19 @@ class HipProbe:
 
         sh = self.lane_shape(path)
         out = np.zeros((sh["steps"], sh["words"], LANE_BLOCK), np.uint32)
-        rc = self.lib.xs_lane_probe(dev, self.lane_paths().index(path), seed, out.ctypes.data, out.size)
-        if rc != 0:
-            raise _probe_error(self.lib.xs_lane_sweep_last_error, rc, "lane_probe")
+        self._call("lane_sweep", "lane_probe", dev, self.lane_paths().index(path), seed, out.ctypes.data, out.size)
         return out
 
     def lane_sweep_expected(self, paths=None, seed: int = LANE_SEED) -> dict:
         """The workgroup digest a healthy CU leaves per selected path,
         computed on the host from the lane maps."""
-        names = self.lane_paths()
-        mask = self._lane_mask(paths)
-        out = (ctypes.c_uint32 * len(names))()
-        rc = self.lib.xs_lane_sweep_expected(mask, seed, out)
-        if rc != 0:
-            raise _probe_error(self.lib.xs_lane_sweep_last_error, rc, "lane_sweep_expected")
-        return {n: out[i] for i, n in enumerate(names) if mask >> i & 1}
+        return self._part_expected(LANE_SWEEP, paths, seed)
 
     def lane_sweep_info(self, dev: int = 0) -> dict:
         """What the runtime reports for k_lane_sweep: `num_regs`,
         `scratch_bytes` per lane, `lds_bytes` per workgroup and `blocks_per_cu`
         (workgroups that fit on a CU at once)."""
-        out = (ctypes.c_int * 4)()
-        rc = self.lib.xs_lane_sweep_info(dev, out)
-        if rc != 0:
-            raise _probe_error(self.lib.xs_lane_sweep_last_error, rc, "lane_sweep_info")
-        return {"num_regs": out[0], "scratch_bytes": out[1], "lds_bytes": out[2], "blocks_per_cu": out[3]}
+        return self._sweep_info("lane_sweep", dev, ("num_regs", "scratch_bytes", "lds_bytes", "blocks_per_cu"))
 
     def lane_sweep(self, dev: int = 0, blocks: int = 0, paths=None, seed: int = LANE_SEED,
                    inject: tuple | None = None, max_rounds: int = 4) -> dict:
@@ -938,96 +990,58 @@ class HipProbe:
         Relaunched while some CU has not been seen, as cu_sweep does. Returns
         {"records": [...], "summary": summarize_lane_sweep(...) plus rounds,
         ms, blocks, paths, seed}."""
-        names = self.lane_paths()
-        mask = self._lane_mask(paths)
-        selected = [f for i, f in enumerate(names) if mask >> i & 1]
-        (ix, ic), im = _inject_target(inject), 0 if inject is None else self._lane_mask(inject[2])
-
-        def decode(w, expected):
-            rec = {"xcd": w[0], "cu": w[1], "simd_mask": w[2], "fail": w[3],
-                   "bad": {f: w[4 + b] for b, f in enumerate(names)},
-                   "digests": {f: w[12 + b] for b, f in enumerate(names)}, "bad_simds": w[20]}
-            for b, f in enumerate(names):
-                if rec["digests"][f] != expected.get(f, 0):
-                    rec["fail"] |= 1 << b
-            return rec
-
-        out = self._sweep_until_covered(
-            "lane_sweep", dev, blocks, max_rounds, LANE_RECORD_WORDS,
-            lambda nb, *out: self.lib.xs_lane_sweep(dev, nb, mask, seed, ix, ic, im, *out),
-            lambda: self.lane_sweep_expected(selected, seed), decode,
-            lambda records, cus: summarize_lane_sweep(records, cus, names))
-        out["summary"].update(seed=seed, paths=selected)
-        return out
+        return self._part_sweep(LANE_SWEEP, summarize_lane_sweep, dev, blocks, paths, inject, max_rounds, (seed,),
+                                {"seed": seed})
 
     # ----------------------------------------------------------- VALU sweep
     def valu_units(self) -> list[str]:
         """Unit names of the VALU sweep; the index is the unit's bit."""
-        return self.lib.xs_valu_units().decode().split(",")
+        return self._part_names(VALU_SWEEP)
 
     def _valu_mask(self, units) -> int:
-        return _name_mask(self.valu_units(), units, "VALU unit")
+        return self._part_mask(VALU_SWEEP, units)
 
     def valu_steps(self, unit: str | None = None) -> list[str]:
         """Step names of one unit in order; None: of every unit, in the order
         of the record's step bits."""
-        names = self.valu_units()
         if unit is None:
-            return [s for u in names for s in self.valu_steps(u)]
+            return [s for u in self.valu_units() for s in self.valu_steps(u)]
         self._valu_mask([unit])
-        return self.lib.xs_valu_steps(names.index(unit)).decode().split(",")
+        return self.lib.xs_valu_steps(self.valu_units().index(unit)).decode().split(",")
 
     def valu_shape(self, unit: str) -> dict:
         """`steps` of one unit and the result `words` every thread gets per round."""
-        self._valu_mask([unit])
-        out = (ctypes.c_int * 2)()
-        rc = self.lib.xs_valu_shape(self.valu_units().index(unit), out)
-        if rc != 0:
-            raise _probe_error(self.lib.xs_valu_sweep_last_error, rc, "valu_shape")
+        out = self._part_shape(VALU_SWEEP, unit, 2)
         return {"steps": out[0], "words": out[1]}
 
-    def _valu_dump(self, what: str, unit: str, rounds: int, call):
+    def _valu_dump(self, what: str, before: tuple, unit: str, seed: int, rounds: int):
         import numpy as np
 
         sh = self.valu_shape(unit)
         out = np.zeros((max(int(rounds), 0), sh["words"], VALU_BLOCK), np.uint32)
-        rc = call(self.valu_units().index(unit), out)
-        if rc != 0:
-            raise _probe_error(self.lib.xs_valu_sweep_last_error, rc, what)
+        self._call("valu_sweep", what, *before, self.valu_units().index(unit), seed, rounds, out.ctypes.data, out.size)
         return out
 
     def valu_expected(self, unit: str, seed: int = VALU_SEED, rounds: int = VALU_ROUNDS):
         """What every thread of a healthy SIMD gets from `unit`, computed on
         the host: uint32 [rounds, words, 256]. No device call."""
-        return self._valu_dump("valu_expected", unit, rounds, lambda u, out: self.lib.xs_valu_expected(
-            u, seed, rounds, out.ctypes.data, out.size))
+        return self._valu_dump("valu_expected", (), unit, seed, rounds)
 
     def valu_probe(self, dev: int, unit: str, seed: int = VALU_SEED, rounds: int = VALU_ROUNDS):
         """k_valu_probe: one workgroup runs `unit` and stores every result:
         uint32 [rounds, words, 256] (thread = 64 x wave + lane)."""
-        return self._valu_dump("valu_probe", unit, rounds, lambda u, out: self.lib.xs_valu_probe(
-            dev, u, seed, rounds, out.ctypes.data, out.size))
+        return self._valu_dump("valu_probe", (dev,), unit, seed, rounds)
 
     def valu_sweep_expected(self, units=None, seed: int = VALU_SEED, rounds: int = VALU_ROUNDS) -> dict:
         """The workgroup digest a healthy CU leaves per selected unit,
         computed on the host from the step table."""
-        names = self.valu_units()
-        mask = self._valu_mask(units)
-        out = (ctypes.c_uint32 * len(names))()
-        rc = self.lib.xs_valu_sweep_expected(mask, seed, rounds, out)
-        if rc != 0:
-            raise _probe_error(self.lib.xs_valu_sweep_last_error, rc, "valu_sweep_expected")
-        return {n: out[i] for i, n in enumerate(names) if mask >> i & 1}
+        return self._part_expected(VALU_SWEEP, units, seed, rounds)
 
     def valu_sweep_info(self, dev: int = 0) -> dict:
         """What the runtime reports for k_valu_sweep: `num_regs`,
         `scratch_bytes` per lane, `lds_bytes` per workgroup and `blocks_per_cu`
         (workgroups that fit on a CU at once)."""
-        out = (ctypes.c_int * 4)()
-        rc = self.lib.xs_valu_sweep_info(dev, out)
-        if rc != 0:
-            raise _probe_error(self.lib.xs_valu_sweep_last_error, rc, "valu_sweep_info")
-        return {"num_regs": out[0], "scratch_bytes": out[1], "lds_bytes": out[2], "blocks_per_cu": out[3]}
+        return self._sweep_info("valu_sweep", dev, ("num_regs", "scratch_bytes", "lds_bytes", "blocks_per_cu"))
 
     def valu_sweep(self, dev: int = 0, blocks: int = 0, units=None, seed: int = VALU_SEED,
                    rounds: int = VALU_ROUNDS, inject: tuple | None = None, max_rounds: int = 4) -> dict:
@@ -1041,28 +1055,9 @@ class HipProbe:
         seen, as cu_sweep does. Returns {"records": [...], "summary":
         summarize_valu_sweep(...) plus rounds (launches), ms, blocks, units,
         operand_rounds, seed}."""
-        names = self.valu_units()
-        steps = self.valu_steps()
-        mask = self._valu_mask(units)
-        selected = [f for i, f in enumerate(names) if mask >> i & 1]
-        (ix, ic), im = _inject_target(inject), 0 if inject is None else self._valu_mask(inject[2])
-
-        def decode(w, expected):
-            rec = {"xcd": w[0], "cu": w[1], "simd_mask": w[2], "fail": w[3],
-                   "bad": {f: w[4 + b] for b, f in enumerate(names)},
-                   "digests": {f: w[12 + b] for b, f in enumerate(names)}, "bad_simds": w[20],
-                   "bad_steps": [s for g, s in enumerate(steps) if w[22 + g // 32] >> (g % 32) & 1]}
-            for b, f in enumerate(names):
-                if rec["digests"][f] != expected.get(f, 0):
-                    rec["fail"] |= 1 << b
-            return rec
-
-        out = self._sweep_until_covered(
-            "valu_sweep", dev, blocks, max_rounds, VALU_RECORD_WORDS,
-            lambda nb, *out: self.lib.xs_valu_sweep(dev, nb, mask, seed, rounds, ix, ic, im, *out),
-            lambda: self.valu_sweep_expected(selected, seed, rounds), decode,
-            lambda records, cus: summarize_valu_sweep(records, cus, names))
-        out["summary"].update(seed=seed, units=selected, operand_rounds=rounds)
+        out = self._part_sweep(VALU_SWEEP, summarize_valu_sweep, dev, blocks, units, inject, max_rounds,
+                               (seed, rounds), {"seed": seed}, self.valu_steps())
+        out["summary"].update(operand_rounds=rounds)
         return out
 
     # ------------------------------------------------------------ HBM sweep
@@ -1224,7 +1219,7 @@ def summarize_matrix_sweep(records: list[dict], compute_units: int, formats: lis
     """summarize_sweep over k_matrix_sweep records, whose fail bits are format
     bits (`formats` names them in bit order): adds `failed_formats` per XCD
     and overall."""
-    return _name_fail_bits(summarize_sweep(records, compute_units), "failed_formats", formats)
+    return _name_fail_bits(summarize_sweep(records, compute_units), MATRIX_SWEEP.summary_key, formats)
 
 
 def summarize_regfile_sweep(records: list[dict], compute_units: int) -> dict:
@@ -1261,7 +1256,7 @@ def summarize_lane_sweep(records: list[dict], compute_units: int, paths: list[st
     """summarize_sweep over k_lane_sweep records, whose fail bits are path
     bits (`paths` names them in bit order): adds `failed_paths` per XCD and
     overall."""
-    return _name_fail_bits(summarize_sweep(records, compute_units), "failed_paths", paths)
+    return _name_fail_bits(summarize_sweep(records, compute_units), LANE_SWEEP.summary_key, paths)
 
 
 def summarize_valu_sweep(records: list[dict], compute_units: int, units: list[str]) -> dict:
@@ -1269,7 +1264,7 @@ def summarize_valu_sweep(records: list[dict], compute_units: int, units: list[st
     bits (`units` names them in bit order): adds `failed_units` per XCD and
     overall, and `failed_steps` (the names in the records' `bad_steps`, in
     first-seen order) per XCD and overall."""
-    s = _name_fail_bits(summarize_sweep(records, compute_units), "failed_units", units)
+    s = _name_fail_bits(summarize_sweep(records, compute_units), VALU_SWEEP.summary_key, units)
     steps: dict[int, list[str]] = {}
     for r in records:
         if int(r.get("fail", 0)):
