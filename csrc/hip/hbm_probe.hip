@@ -26,7 +26,7 @@
 //                       32 CUs) or a QPX/DPX partition can pull, measured on
 //                       an SPX device. A launch in which a selected XCD got
 //                       no workgroup fails with -1002 instead of a rate.
-//  * xs_stream_op_g, xs_pinned_op_g, xs_segment_op, xs_checksum_op  one
+//  * xs_stream_op, xs_pinned_op, xs_segment_op, xs_checksum_op  one
 //                       launch of the same kernels over caller-owned buffers,
 //                       for the GPU tests; the read paths run as checked
 //                       instantiations (k_*_fold) that report the XOR of the
@@ -43,12 +43,14 @@
 //                       to numpy and see the verdict fail on a flipped bit.
 //
 // Exposed as a C ABI (loaded with ctypes from flex_gpu_scheduler_amd/ops).
+// Every entry point checks its arguments before it touches the device: -1000
+// for bad arguments, -1001 for a null or mis-aligned buffer, nothing launched.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
-#include <algorithm>
-#include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "hip/sweep_common.h"
@@ -60,9 +62,12 @@ namespace {
 xsprobe::ErrBuf g_err;
 
 using xsprobe::DevMem;
-using xsprobe::Event;
 using xsprobe::Stream;
+using xsprobe::XcdCounters;
 using xsprobe::hw_id;
+using xsprobe::kBadArgs;
+using xsprobe::kCounterStride;
+using xsprobe::kMaxXcds;
 using xsprobe::xcc_id;
 
 constexpr int kBlock = 256;  // 4 waves of 64 lanes
@@ -188,10 +193,21 @@ __global__ __launch_bounds__(kBlock) void k_triad(f32x4* __restrict__ a, const f
 // device-wide counter serialized the 8-XCD case at ~2 TB/s, round-3 pmc
 // run). mode 0 read, 1 write, 2 copy. Where workgroups land is the
 // dispatcher's choice: a selected XCD that gets none leaves its slice
-// untouched, which the host detects from that XCD's counter (undrained_xcds)
+// untouched, which the host detects from that XCD's counter (check_drained)
 // and reports as an error, never as a rate.
-constexpr int kCounterStride = 32;  // unsigned per XCD counter (128 B)
-constexpr int kMaxXcds = 8;
+constexpr size_t kChunk = 16384;  // vec4s = 256 KiB
+
+struct Slice {
+  size_t c0, c1;
+};
+// The chunks [c0, c1) that XCD x of the selected set `sel` owns of a buffer of
+// n vec4s: the kernel's split and the host's check of it.
+__host__ __device__ __forceinline__ Slice xcd_slice(size_t n, uint32_t sel, uint32_t x) {
+  const size_t nsel = static_cast<size_t>(__builtin_popcount(sel));
+  const size_t rank = static_cast<size_t>(__builtin_popcount(sel & ((1u << x) - 1u)));
+  const size_t nchunks = (n + kChunk - 1) / kChunk;
+  return {nchunks * rank / nsel, nchunks * (rank + 1) / nsel};
+}
 
 template <bool FOLD>
 __device__ __forceinline__ void pinned_lanes(const vec4* __restrict__ src, vec4* __restrict__ dst, size_t n,
@@ -199,12 +215,7 @@ __device__ __forceinline__ void pinned_lanes(const vec4* __restrict__ src, vec4*
                                              uint32_t* __restrict__ sink, unsigned long long* __restrict__ fold) {
   const uint32_t x = xcc_id();
   if (x >= kMaxXcds || !((xcd_mask >> x) & 1u)) return;
-  constexpr size_t kChunk = 16384;  // vec4s = 256 KiB
-  const uint32_t sel = xcd_mask & 0xffu;
-  const size_t nsel = static_cast<size_t>(__popc(sel));
-  const size_t rank = static_cast<size_t>(__popc(sel & ((1u << x) - 1u)));
-  const size_t nchunks = (n + kChunk - 1) / kChunk;
-  const size_t c0 = nchunks * rank / nsel, c1 = nchunks * (rank + 1) / nsel;
+  const auto [c0, c1] = xcd_slice(n, xcd_mask & 0xffu, x);
   unsigned* ctr = counters + x * kCounterStride;
   __shared__ unsigned chunk;
   uint32_t acc = 0;
@@ -342,40 +353,24 @@ __global__ __launch_bounds__(kBlock) void k_segments_fold(vec4* __restrict__ buf
   segment_lanes<0, NT, true>(buf, touches, stride_vec, seg_lanes, nullptr, fold);
 }
 
-// Per-launch timing: `launch(i)` enqueues launch i; every launch sits
-// between its own event pair on `s`. out: [median ms, min ms, batch ms per
-// launch (first start to last end / iters)]. Events are created once.
-template <typename F>
-int time_launches(hipStream_t s, int iters, F&& launch, double out[3]) {
-  std::vector<Event> ev(2 * static_cast<size_t>(iters));
-  for (auto& e : ev) XS_CHECK(hipEventCreate(&e.e));
-  for (int i = 0; i < iters; ++i) {
-    XS_CHECK(hipEventRecord(ev[2 * i].e, s));
-    launch(i);
-    XS_CHECK(hipEventRecord(ev[2 * i + 1].e, s));
-  }
-  XS_CHECK(hipEventSynchronize(ev.back().e));
-  XS_CHECK(hipGetLastError());
-  std::vector<double> per(iters);
-  for (int i = 0; i < iters; ++i) {
-    float ms = 0;
-    XS_CHECK(hipEventElapsedTime(&ms, ev[2 * i].e, ev[2 * i + 1].e));
-    per[i] = ms;
-  }
-  float total = 0;
-  XS_CHECK(hipEventElapsedTime(&total, ev.front().e, ev.back().e));
-  std::vector<double> sorted = per;
-  std::sort(sorted.begin(), sorted.end());
-  out[0] = sorted[sorted.size() / 2];
-  out[1] = sorted.front();
-  out[2] = static_cast<double>(total) / iters;
-  return 0;
+constexpr int kBadBuffer = -1001;
+constexpr int kUndrained = -1002;
+constexpr int kBlocksPerCu = 8;  // the persistent grid of everything but a variant
+
+// A caller's buffer that is null though `needed`, or not aligned to `align` (a power of two).
+bool bad_buffer(const void* p, size_t align, bool needed = true) {
+  return (!p && needed) || (reinterpret_cast<uintptr_t>(p) & (align - 1));
 }
 
-int cu_count(int dev) {
-  hipDeviceProp_t p;
-  if (hipGetDeviceProperties(&p, dev) != hipSuccess) return 256;
-  return p.multiProcessorCount;
+// What a timed probe reports: `moved` bytes per launch over time_launches' t.
+void report_rate(double moved, const double t[3], double* gbps, double* ms_per_iter, double* detail) {
+  if (gbps) *gbps = moved / (t[0] * 1e-3) / 1e9;
+  if (ms_per_iter) *ms_per_iter = t[0];
+  if (detail) {
+    detail[0] = moved / (t[1] * 1e-3) / 1e9;
+    detail[1] = moved / (t[2] * 1e-3) / 1e9;
+    detail[2] = t[2];
+  }
 }
 
 // variant = unroll(1|4|8) | (nt ? 0x100 : 0) | (one_shot ? 0x200 : 0) |
@@ -411,45 +406,54 @@ int grid_for(const Variant& v, size_t n, int cus) {
 constexpr uint32_t kWriteSeed = 7;
 constexpr float kTriadScale = 3.0f;
 
-// mode 0 read(a), 1 write(a <- pattern(seed)), 2 copy(b <- a), 3 triad(a <- b + scale*c).
-template <int U, bool NT>
-void launch_t(int mode, int grid, hipStream_t s, void* a, void* b, void* c, size_t n, uint32_t* sink, uint32_t seed,
-              float scale) {
-  switch (mode) {
-    case 0: k_read<U, NT><<<grid, kBlock, 0, s>>>(static_cast<const vec4*>(a), n, sink); break;
-    case 1: k_write<U, NT><<<grid, kBlock, 0, s>>>(static_cast<vec4*>(a), n, seed); break;
-    case 2: k_copy<U, NT><<<grid, kBlock, 0, s>>>(static_cast<const vec4*>(a), static_cast<vec4*>(b), n); break;
-    default:
-      k_triad<U, NT><<<grid, kBlock, 0, s>>>(static_cast<f32x4*>(a), static_cast<const f32x4*>(b),
-                                            static_cast<const f32x4*>(c), scale, n);
-  }
+// f(U, NT) with variant v's unroll and cache policy as compile-time constants
+// (std::integral_constant<int, U>, std::bool_constant<NT>).
+template <typename F>
+void with_variant(const Variant& v, F&& f) {
+  auto with_unroll = [&](auto nt) {
+    if (v.unroll == 1) f(std::integral_constant<int, 1>{}, nt);
+    else if (v.unroll == 8) f(std::integral_constant<int, 8>{}, nt);
+    else f(std::integral_constant<int, 4>{}, nt);
+  };
+  if (v.nt) with_unroll(std::true_type{});
+  else with_unroll(std::false_type{});
 }
 
+// mode 0 read(a), 1 write(a <- pattern(seed)), 2 copy(b <- a), 3 triad(a <- b + scale*c).
 void launch(const Variant& v, int mode, int grid, hipStream_t s, void* a, void* b, void* c, size_t n, uint32_t* sink,
             uint32_t seed = kWriteSeed, float scale = kTriadScale) {
-  if (v.nt) {
-    if (v.unroll == 1) launch_t<1, true>(mode, grid, s, a, b, c, n, sink, seed, scale);
-    else if (v.unroll == 8) launch_t<8, true>(mode, grid, s, a, b, c, n, sink, seed, scale);
-    else launch_t<4, true>(mode, grid, s, a, b, c, n, sink, seed, scale);
-  } else {
-    if (v.unroll == 1) launch_t<1, false>(mode, grid, s, a, b, c, n, sink, seed, scale);
-    else if (v.unroll == 8) launch_t<8, false>(mode, grid, s, a, b, c, n, sink, seed, scale);
-    else launch_t<4, false>(mode, grid, s, a, b, c, n, sink, seed, scale);
-  }
+  with_variant(v, [&](auto u, auto nt) {
+    constexpr int U = decltype(u)::value;
+    constexpr bool NT = decltype(nt)::value;
+    switch (mode) {
+      case 0: k_read<U, NT><<<grid, kBlock, 0, s>>>(static_cast<const vec4*>(a), n, sink); break;
+      case 1: k_write<U, NT><<<grid, kBlock, 0, s>>>(static_cast<vec4*>(a), n, seed); break;
+      case 2: k_copy<U, NT><<<grid, kBlock, 0, s>>>(static_cast<const vec4*>(a), static_cast<vec4*>(b), n); break;
+      default:
+        k_triad<U, NT><<<grid, kBlock, 0, s>>>(static_cast<f32x4*>(a), static_cast<const f32x4*>(b),
+                                              static_cast<const f32x4*>(c), scale, n);
+    }
+  });
 }
 
-// The checked read (k_read_fold) of variant v: same unroll and cache policy.
-void launch_read_fold(const Variant& v, int grid, hipStream_t s, const void* a, size_t n, unsigned long long* fold) {
-  const vec4* p = static_cast<const vec4*>(a);
-  if (v.nt) {
-    if (v.unroll == 1) k_read_fold<1, true><<<grid, kBlock, 0, s>>>(p, n, fold);
-    else if (v.unroll == 8) k_read_fold<8, true><<<grid, kBlock, 0, s>>>(p, n, fold);
-    else k_read_fold<4, true><<<grid, kBlock, 0, s>>>(p, n, fold);
-  } else {
-    if (v.unroll == 1) k_read_fold<1, false><<<grid, kBlock, 0, s>>>(p, n, fold);
-    else if (v.unroll == 8) k_read_fold<8, false><<<grid, kBlock, 0, s>>>(p, n, fold);
-    else k_read_fold<4, false><<<grid, kBlock, 0, s>>>(p, n, fold);
-  }
+// One k_segments launch: the checked read when `fold` is given, otherwise
+// mode 0 reads into the DCE sink and mode 1 writes the fill.
+void launch_segments(int mode, bool nt, int grid, hipStream_t s, vec4* buf, size_t touches, size_t stride_vec,
+                     int seg_lanes, uint32_t* sink, unsigned long long* fold) {
+  auto with_policy = [&](auto policy) {
+    constexpr bool NT = decltype(policy)::value;
+    if (fold) k_segments_fold<NT><<<grid, kBlock, 0, s>>>(buf, touches, stride_vec, seg_lanes, fold);
+    else if (mode == 0) k_segments<0, NT><<<grid, kBlock, 0, s>>>(buf, touches, stride_vec, seg_lanes, sink);
+    else k_segments<1, NT><<<grid, kBlock, 0, s>>>(buf, touches, stride_vec, seg_lanes, sink);
+  };
+  if (nt) with_policy(std::true_type{});
+  else with_policy(std::false_type{});
+}
+
+// What xs_segment_access and xs_segment_op both require of a segment layout.
+bool segment_args_ok(int mode, int seg_bytes, size_t stride_bytes, size_t touches) {
+  return mode >= 0 && mode <= 1 && seg_bytes >= 16 && seg_bytes <= 1024 && seg_bytes % 16 == 0 &&
+         stride_bytes % 128 == 0 && stride_bytes >= static_cast<size_t>(seg_bytes) && touches != 0;
 }
 
 constexpr int kMaxGrid = 1 << 22;  // grid_for's cap; an explicit grid obeys it too
@@ -469,36 +473,32 @@ struct Fold {
   }
 };
 
-constexpr int kUndrained = -1002;
-
-// k_pinned's per-XCD counters of one completed launch (host copy). Every
-// workgroup on a selected XCD takes chunks from that XCD's counter until its
-// slice [c0, c1) is exhausted, so a selected XCD whose slice is not empty and
-// whose counter is still 0 received no workgroup: its slice was never
-// processed. Returns those XCDs as a mask (slice bounds as in the kernel).
-uint32_t undrained_xcds(const unsigned* ctr, size_t n, uint32_t xcd_mask) {
-  const uint32_t sel = xcd_mask & 0xffu;
-  const size_t nsel = static_cast<size_t>(__builtin_popcount(sel));
-  const size_t nchunks = (n + 16384 - 1) / 16384;
-  uint32_t missed = 0;
-  for (uint32_t x = 0; x < kMaxXcds; ++x) {
-    if (!((sel >> x) & 1u)) continue;
-    const size_t rank = static_cast<size_t>(__builtin_popcount(sel & ((1u << x) - 1u)));
-    const size_t c0 = nchunks * rank / nsel, c1 = nchunks * (rank + 1) / nsel;
-    if (c1 > c0 && ctr[x * kCounterStride] == 0) missed |= 1u << x;
-  }
-  return missed;
+// Both k_pinned callers: some of the 8 XCDs, chunk indices that fit its 32-bit counters.
+bool pinned_args_ok(int mode, uint32_t xcd_mask, size_t n) {
+  return mode >= 0 && mode <= 2 && xcd_mask != 0 && !(xcd_mask & ~0xffu) && n != 0 && n / kChunk < 0xffffff00ull;
 }
 
-int fail_undrained(uint32_t missed, uint32_t xcd_mask, int launch) {
-  char list[32];
-  int k = 0;
-  for (int x = 0; x < kMaxXcds; ++x)
-    if ((missed >> x) & 1u) k += std::snprintf(list + k, sizeof list - k, "%s%d", k ? "," : "", x);
-  std::snprintf(g_err, sizeof g_err,
-                "k_pinned: no workgroup ran on XCD(s) %s of xcd_mask 0x%x (launch %d); their slices were not processed",
-                list, xcd_mask, launch);
-  return kUndrained;
+// Checks k_pinned's counters of every launch, all completed. A workgroup on a
+// selected XCD takes chunks from that XCD's counter until its slice is done, so
+// a selected XCD with a slice and a counter still 0 received no workgroup and
+// its slice was never processed: the first such launch fails with kUndrained.
+int check_drained(const XcdCounters& counters, size_t n, uint32_t xcd_mask) {
+  std::vector<unsigned> ctr(static_cast<size_t>(counters.launches) * kMaxXcds);
+  XS_CHECK(counters.fetch(ctr.data()));
+  for (int launch = 0; launch < counters.launches; ++launch) {
+    uint32_t missed = 0;
+    for (uint32_t x = 0; x < kMaxXcds; ++x) {
+      if (!((xcd_mask >> x) & 1u)) continue;
+      const auto [c0, c1] = xcd_slice(n, xcd_mask & 0xffu, x);
+      if (c1 > c0 && ctr[launch * kMaxXcds + x] == 0) missed |= 1u << x;
+    }
+    if (!missed) continue;
+    std::snprintf(g_err, sizeof g_err,
+                  "k_pinned: no workgroup ran on XCD(s) %s of xcd_mask 0x%x (launch %d); their slices were not processed",
+                  xsprobe::XcdList(missed).text, xcd_mask, launch);
+    return kUndrained;
+  }
+  return 0;
 }
 
 Variant default_variant(int mode) {
@@ -551,12 +551,12 @@ int xs_device_props(int dev, char* out, int len) {
 // mode: 0 read, 1 write, 2 copy, 3 triad. bytes = working set per array.
 // cu_limit > 0 caps the grid at cu_limit * blocks_per_cu workgroups.
 // detail (optional, 3 doubles): min-launch GB/s, batch GB/s, batch ms/launch.
-int xs_hbm_bandwidth_d(int dev, size_t bytes, int iters, int cu_limit, int mode, int variant, double* gbps,
-                       double* ms_per_iter, double* detail) {
+int xs_hbm_bandwidth(int dev, size_t bytes, int iters, int cu_limit, int mode, int variant, double* gbps,
+                     double* ms_per_iter, double* detail) {
+  const size_t n = bytes / sizeof(vec4);
+  if (n == 0 || mode < 0 || mode > 3) return kBadArgs;
   XS_CHECK(hipSetDevice(dev));
   if (iters <= 0) iters = 10;
-  size_t n = bytes / sizeof(vec4);
-  if (n == 0 || mode < 0 || mode > 3) return -1000;
   bytes = n * sizeof(vec4);
   Variant v = variant == 0 ? default_variant(mode) : decode(variant);
   DevMem a, b, c, sink;
@@ -564,7 +564,8 @@ int xs_hbm_bandwidth_d(int dev, size_t bytes, int iters, int cu_limit, int mode,
   XS_CHECK(hipMalloc(&b.p, bytes));
   if (mode == 3) XS_CHECK(hipMalloc(&c.p, bytes));
   XS_CHECK(hipMalloc(&sink.p, sizeof(uint32_t)));
-  int cus = cu_count(dev);
+  int cus = 0;
+  XS_CHECK(xsprobe::cu_count(dev, &cus));
   if (cu_limit > 0 && cu_limit < cus) {
     cus = cu_limit;
     v.one_shot = false;  // a CU budget needs the persistent grid
@@ -580,22 +581,10 @@ int xs_hbm_bandwidth_d(int dev, size_t bytes, int iters, int cu_limit, int mode,
   launch(v, mode, grid, s.s, a.p, b.p, c.p, n, sink.as<uint32_t>());
   XS_CHECK(hipStreamSynchronize(s.s));
   double t[3];
-  int rc = time_launches(s.s, iters, [&](int) { launch(v, mode, grid, s.s, a.p, b.p, c.p, n, sink.as<uint32_t>()); }, t);
-  if (rc) return rc;
-  const double moved = static_cast<double>(bytes) * (mode == 2 ? 2.0 : mode == 3 ? 3.0 : 1.0);
-  if (gbps) *gbps = moved / (t[0] * 1e-3) / 1e9;
-  if (ms_per_iter) *ms_per_iter = t[0];
-  if (detail) {
-    detail[0] = moved / (t[1] * 1e-3) / 1e9;
-    detail[1] = moved / (t[2] * 1e-3) / 1e9;
-    detail[2] = t[2];
-  }
+  auto timed = [&](int) { launch(v, mode, grid, s.s, a.p, b.p, c.p, n, sink.as<uint32_t>()); };
+  if (int rc = xsprobe::time_launches(g_err, s.s, iters, timed, t)) return rc;
+  report_rate(static_cast<double>(bytes) * (mode == 2 ? 2.0 : mode == 3 ? 3.0 : 1.0), t, gbps, ms_per_iter, detail);
   return 0;
-}
-
-int xs_hbm_bandwidth_v(int dev, size_t bytes, int iters, int cu_limit, int mode, int variant, double* gbps,
-                       double* ms_per_iter) {
-  return xs_hbm_bandwidth_d(dev, bytes, iters, cu_limit, mode, variant, gbps, ms_per_iter, nullptr);
 }
 
 // One streaming kernel over caller-owned device buffers (e.g. torch tensors),
@@ -603,39 +592,39 @@ int xs_hbm_bandwidth_v(int dev, size_t bytes, int iters, int cu_limit, int mode,
 // references (a float64 bound for triad; subnormal operands and results are
 // kept, the library is built without a flush-to-zero flag). mode 1: a <- pattern(seed); 2: b <- a; 3: a <- b +
 // scale*c (float4 lanes). bytes must be a multiple of 16 and every pointer
-// 16-byte aligned. variant as in xs_hbm_bandwidth_v (0 = the tuned default).
+// 16-byte aligned. variant as in xs_hbm_bandwidth (0 = the tuned default).
 // grid > 0 launches that many workgroups instead of the variant's own grid
 // (the tests reach the unrolled bodies and the grid-stride path with small
 // buffers that way). mode 0 (read a) needs `fold`, two host words: the
 // checked read kernel's XOR of all 32-bit words and its count of 16-B loads.
-int xs_stream_op_g(int dev, int mode, void* a, void* b, void* c, size_t bytes, uint32_t seed, float scale,
-                   int variant, int grid, unsigned long long* fold) {
-  XS_CHECK(hipSetDevice(dev));
+int xs_stream_op(int dev, int mode, void* a, void* b, void* c, size_t bytes, uint32_t seed, float scale, int variant,
+                 int grid, unsigned long long* fold) {
   if (mode < 0 || mode > 3 || (mode == 0) != (fold != nullptr) || bytes == 0 || bytes % sizeof(vec4) != 0 ||
       grid < 0 || grid > kMaxGrid)
-    return -1000;
-  const uintptr_t align = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) |
-                          reinterpret_cast<uintptr_t>(c);
-  if (!a || (mode >= 2 && !b) || (mode == 3 && !c) || (align & (sizeof(vec4) - 1))) return -1001;
+    return kBadArgs;
+  if (bad_buffer(a, sizeof(vec4)) || bad_buffer(b, sizeof(vec4), mode >= 2) || bad_buffer(c, sizeof(vec4), mode == 3))
+    return kBadBuffer;
+  XS_CHECK(hipSetDevice(dev));
   Variant v = variant == 0 ? default_variant(mode) : decode(variant);
   const size_t n = bytes / sizeof(vec4);
-  if (grid == 0) grid = grid_for(v, n, cu_count(dev));
+  if (grid == 0) {
+    int cus = 0;
+    XS_CHECK(xsprobe::cu_count(dev, &cus));
+    grid = grid_for(v, n, cus);
+  }
   Fold f;
   if (mode == 0) {
     if (int rc = f.init()) return rc;
-    launch_read_fold(v, grid, nullptr, a, n, f.d.as<unsigned long long>());
+    with_variant(v, [&](auto u, auto nt) {  // the checked read of variant v: same unroll and cache policy
+      k_read_fold<decltype(u)::value, decltype(nt)::value><<<grid, kBlock>>>(static_cast<const vec4*>(a), n,
+                                                                             f.d.as<unsigned long long>());
+    });
   } else {
     launch(v, mode, grid, nullptr, a, b, c, n, nullptr, seed, scale);
   }
   XS_CHECK(hipGetLastError());
   XS_CHECK(hipDeviceSynchronize());
   return mode == 0 ? f.fetch(fold) : 0;
-}
-
-int xs_stream_op(int dev, int mode, void* a, void* b, void* c, size_t bytes, uint32_t seed, float scale,
-                 int variant) {
-  if (mode == 0) return -1000;
-  return xs_stream_op_g(dev, mode, a, b, c, bytes, seed, scale, variant, 0, nullptr);
 }
 
 // XCD-pinned streaming over caller-owned buffers (mode 1 write dst, 2 copy
@@ -645,102 +634,69 @@ int xs_stream_op(int dev, int mode, void* a, void* b, void* c, size_t bytes, uin
 // received no workgroup (xs_last_error names it); what the other XCDs wrote
 // stays. xcd_mask bits above the 8 XCDs are refused. grid > 0 launches that
 // many workgroups instead of 8 per CU. mode 0 (read src) needs `fold`, two
-// host words as in xs_stream_op_g.
-int xs_pinned_op_g(int dev, int mode, const void* src, void* dst, size_t bytes, uint32_t xcd_mask, int grid,
-                   unsigned long long* fold) {
-  XS_CHECK(hipSetDevice(dev));
-  if (mode < 0 || mode > 2 || (mode == 0) != (fold != nullptr) || xcd_mask == 0 || (xcd_mask & ~0xffu) ||
-      bytes == 0 || bytes % sizeof(vec4) != 0 || grid < 0 || grid > kMaxGrid)
-    return -1000;
+// host words as in xs_stream_op.
+int xs_pinned_op(int dev, int mode, const void* src, void* dst, size_t bytes, uint32_t xcd_mask, int grid,
+                 unsigned long long* fold) {
   const size_t n = bytes / sizeof(vec4);
-  if (n / 16384 >= 0xffffff00ull) return -1000;
-  if ((mode != 0 && !dst) || (mode != 1 && !src) ||
-      ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & (sizeof(vec4) - 1)))
-    return -1001;
-  DevMem counter, sink;
-  const size_t ctr_bytes = sizeof(unsigned) * kMaxXcds * kCounterStride;
-  XS_CHECK(hipMalloc(&counter.p, ctr_bytes));
+  if (!pinned_args_ok(mode, xcd_mask, n) || (mode == 0) != (fold != nullptr) || bytes % sizeof(vec4) != 0 ||
+      grid < 0 || grid > kMaxGrid)
+    return kBadArgs;
+  if (bad_buffer(dst, sizeof(vec4), mode != 0) || bad_buffer(src, sizeof(vec4), mode != 1)) return kBadBuffer;
+  XS_CHECK(hipSetDevice(dev));
+  XcdCounters counters;
+  XS_CHECK(counters.init());
+  DevMem sink;
   XS_CHECK(hipMalloc(&sink.p, sizeof(uint32_t)));
-  XS_CHECK(hipMemset(counter.p, 0, ctr_bytes));
-  if (grid == 0) grid = cu_count(dev) * 8;
+  if (grid == 0) XS_CHECK(xsprobe::cu_count(dev, &grid, kBlocksPerCu));
   Fold f;
   if (mode == 0) {
     if (int rc = f.init()) return rc;
-    k_pinned_fold<<<grid, kBlock>>>(static_cast<const vec4*>(src), n, xcd_mask, counter.as<unsigned>(),
+    k_pinned_fold<<<grid, kBlock>>>(static_cast<const vec4*>(src), n, xcd_mask, counters.of(0),
                                     f.d.as<unsigned long long>());
   } else {
-    k_pinned<<<grid, kBlock>>>(static_cast<const vec4*>(src), static_cast<vec4*>(dst), n, xcd_mask,
-                               counter.as<unsigned>(), mode, sink.as<uint32_t>());
+    k_pinned<<<grid, kBlock>>>(static_cast<const vec4*>(src), static_cast<vec4*>(dst), n, xcd_mask, counters.of(0),
+                               mode, sink.as<uint32_t>());
   }
   XS_CHECK(hipGetLastError());
   XS_CHECK(hipDeviceSynchronize());
-  unsigned ctr[kMaxXcds * kCounterStride];
-  XS_CHECK(hipMemcpy(ctr, counter.p, ctr_bytes, hipMemcpyDeviceToHost));
-  if (uint32_t missed = undrained_xcds(ctr, n, xcd_mask)) return fail_undrained(missed, xcd_mask, 0);
+  if (int rc = check_drained(counters, n, xcd_mask)) return rc;
   return mode == 0 ? f.fetch(fold) : 0;
 }
 
-int xs_pinned_op(int dev, int mode, const void* src, void* dst, size_t bytes, uint32_t xcd_mask) {
-  if (mode == 0) return -1000;
-  return xs_pinned_op_g(dev, mode, src, dst, bytes, xcd_mask, 0, nullptr);
-}
-
-int xs_hbm_bandwidth(int dev, size_t bytes, int iters, int cu_limit, int mode, double* gbps, double* ms_per_iter) {
-  return xs_hbm_bandwidth_v(dev, bytes, iters, cu_limit, mode, 0, gbps, ms_per_iter);
-}
-
 // Bandwidth pulled by the workgroups resident on the XCDs in xcd_mask
-// (mode 0 read, 1 write, 2 copy). detail as in xs_hbm_bandwidth_d.
-int xs_hbm_bandwidth_xcd_d(int dev, size_t bytes, int iters, uint32_t xcd_mask, int mode, double* gbps,
-                           double* ms_per_iter, double* detail) {
+// (mode 0 read, 1 write, 2 copy). detail as in xs_hbm_bandwidth.
+int xs_hbm_bandwidth_xcd(int dev, size_t bytes, int iters, uint32_t xcd_mask, int mode, double* gbps,
+                         double* ms_per_iter, double* detail) {
+  const size_t n = bytes / sizeof(vec4);
+  if (!pinned_args_ok(mode, xcd_mask, n)) return kBadArgs;
   XS_CHECK(hipSetDevice(dev));
   if (iters <= 0) iters = 10;
-  if (mode < 0 || mode > 2 || xcd_mask == 0 || (xcd_mask & ~0xffu)) return -1000;
-  size_t n = bytes / sizeof(vec4);
-  if (n == 0 || n / 16384 >= 0xffffff00ull) return -1000;
   bytes = n * sizeof(vec4);
-  DevMem a, b, counters, sink;
+  DevMem a, b, sink;
   XS_CHECK(hipMalloc(&a.p, bytes));
   XS_CHECK(hipMalloc(&b.p, bytes));
-  const size_t per_launch = static_cast<size_t>(kMaxXcds) * kCounterStride;  // fresh counters per launch
-  XS_CHECK(hipMalloc(&counters.p, sizeof(unsigned) * per_launch * (iters + 1)));
   XS_CHECK(hipMalloc(&sink.p, sizeof(uint32_t)));
-  XS_CHECK(hipMemset(counters.p, 0, sizeof(unsigned) * per_launch * (iters + 1)));
-  unsigned* ctr = counters.as<unsigned>();
-  int grid = cu_count(dev) * 8;  // every CU gets 8 workgroups; only masked XCDs work
+  XcdCounters counters;  // fresh ones per launch; the warm-up is launch `iters`
+  XS_CHECK(counters.init(iters + 1));
+  int grid = 0;  // every CU gets 8 workgroups; only masked XCDs work
+  XS_CHECK(xsprobe::cu_count(dev, &grid, kBlocksPerCu));
   Stream s;
   XS_CHECK(hipStreamCreateWithFlags(&s.s, hipStreamNonBlocking));
+  auto pinned = [&](int i) {
+    k_pinned<<<grid, kBlock, 0, s.s>>>(a.as<const vec4>(), b.as<vec4>(), n, xcd_mask, counters.of(i), mode,
+                                       sink.as<uint32_t>());
+  };
   k_write<4, true><<<grid, kBlock, 0, s.s>>>(a.as<vec4>(), n, 1);
-  k_pinned<<<grid, kBlock, 0, s.s>>>(a.as<const vec4>(), b.as<vec4>(), n, xcd_mask, &ctr[iters * per_launch], mode,
-                                     sink.as<uint32_t>());
+  pinned(iters);
   XS_CHECK(hipGetLastError());
   XS_CHECK(hipStreamSynchronize(s.s));
   double t[3];
-  int rc = time_launches(s.s, iters, [&](int i) {
-    k_pinned<<<grid, kBlock, 0, s.s>>>(a.as<const vec4>(), b.as<vec4>(), n, xcd_mask, &ctr[i * per_launch], mode,
-                                       sink.as<uint32_t>());
-  }, t);
-  if (rc) return rc;
-  // No rate for bytes that were not moved: every launch (the warm-up is
-  // launch `iters`) must have had a workgroup on each selected XCD.
-  std::vector<unsigned> hctr(per_launch * (iters + 1));
-  XS_CHECK(hipMemcpy(hctr.data(), counters.p, sizeof(unsigned) * hctr.size(), hipMemcpyDeviceToHost));
-  for (int i = 0; i <= iters; ++i)
-    if (uint32_t missed = undrained_xcds(&hctr[i * per_launch], n, xcd_mask)) return fail_undrained(missed, xcd_mask, i);
-  const double moved = static_cast<double>(bytes) * (mode == 2 ? 2.0 : 1.0);
-  if (gbps) *gbps = moved / (t[0] * 1e-3) / 1e9;
-  if (ms_per_iter) *ms_per_iter = t[0];
-  if (detail) {
-    detail[0] = moved / (t[1] * 1e-3) / 1e9;
-    detail[1] = moved / (t[2] * 1e-3) / 1e9;
-    detail[2] = t[2];
-  }
+  if (int rc = xsprobe::time_launches(g_err, s.s, iters, pinned, t)) return rc;
+  // No rate for bytes that were not moved: every launch must have had a
+  // workgroup on each selected XCD.
+  if (int rc = check_drained(counters, n, xcd_mask)) return rc;
+  report_rate(static_cast<double>(bytes) * (mode == 2 ? 2.0 : 1.0), t, gbps, ms_per_iter, detail);
   return 0;
-}
-
-int xs_hbm_bandwidth_xcd(int dev, size_t bytes, int iters, uint32_t xcd_mask, int mode, double* gbps,
-                         double* ms_per_iter) {
-  return xs_hbm_bandwidth_xcd_d(dev, bytes, iters, xcd_mask, mode, gbps, ms_per_iter, nullptr);
 }
 
 // Counter calibration: `touches` segments of `seg_bytes` (16..1024, a
@@ -750,34 +706,28 @@ int xs_hbm_bandwidth_xcd(int dev, size_t bytes, int iters, uint32_t xcd_mask, in
 // per dispatch, 128-B lines per dispatch].
 int xs_segment_access(int dev, int mode, int nt, int seg_bytes, size_t stride_bytes, size_t touches, int iters,
                       double* out) {
+  if (!segment_args_ok(mode, seg_bytes, stride_bytes, touches)) return kBadArgs;
   XS_CHECK(hipSetDevice(dev));
-  if (mode < 0 || mode > 1 || seg_bytes < 16 || seg_bytes > 1024 || seg_bytes % 16 || stride_bytes % 128 ||
-      stride_bytes < static_cast<size_t>(seg_bytes) || touches == 0)
-    return -1000;
   if (iters <= 0) iters = 10;
   const size_t bytes = stride_bytes * touches;
   const size_t n = bytes / sizeof(vec4);
   DevMem buf, sink;
   XS_CHECK(hipMalloc(&buf.p, bytes));
   XS_CHECK(hipMalloc(&sink.p, sizeof(uint32_t)));
-  const int grid = cu_count(dev) * 8;
+  int grid = 0;
+  XS_CHECK(xsprobe::cu_count(dev, &grid, kBlocksPerCu));
   Stream s;
   XS_CHECK(hipStreamCreateWithFlags(&s.s, hipStreamNonBlocking));
   k_write<4, true><<<grid, kBlock, 0, s.s>>>(buf.as<vec4>(), n, 1);  // page in
-  const size_t sv = stride_bytes / sizeof(vec4);
-  const int lanes = seg_bytes / 16;
-  auto go = [&] {
-    if (mode == 0 && nt) k_segments<0, true><<<grid, kBlock, 0, s.s>>>(buf.as<vec4>(), touches, sv, lanes, sink.as<uint32_t>());
-    else if (mode == 0) k_segments<0, false><<<grid, kBlock, 0, s.s>>>(buf.as<vec4>(), touches, sv, lanes, sink.as<uint32_t>());
-    else if (nt) k_segments<1, true><<<grid, kBlock, 0, s.s>>>(buf.as<vec4>(), touches, sv, lanes, sink.as<uint32_t>());
-    else k_segments<1, false><<<grid, kBlock, 0, s.s>>>(buf.as<vec4>(), touches, sv, lanes, sink.as<uint32_t>());
+  auto go = [&](int) {
+    launch_segments(mode, nt, grid, s.s, buf.as<vec4>(), touches, stride_bytes / sizeof(vec4), seg_bytes / 16,
+                    sink.as<uint32_t>(), nullptr);
   };
-  go();
+  go(0);
   XS_CHECK(hipGetLastError());
   XS_CHECK(hipStreamSynchronize(s.s));
   double t[3];
-  int rc = time_launches(s.s, iters, [&](int) { go(); }, t);
-  if (rc) return rc;
+  if (int rc = xsprobe::time_launches(g_err, s.s, iters, go, t)) return rc;
   out[0] = t[0];
   out[1] = static_cast<double>(touches) * seg_bytes;
   out[2] = static_cast<double>(touches) * ((seg_bytes + 127) / 128);
@@ -790,25 +740,17 @@ int xs_segment_access(int dev, int mode, int nt, int seg_bytes, size_t stride_by
 // needs `fold`, two host words: XOR of the 32-bit words read, 16-B loads issued.
 int xs_segment_op(int dev, int mode, int nt, int seg_bytes, size_t stride_bytes, size_t touches, void* buf,
                   unsigned long long* fold) {
+  if (!segment_args_ok(mode, seg_bytes, stride_bytes, touches) || (mode == 0) != (fold != nullptr)) return kBadArgs;
+  if (bad_buffer(buf, sizeof(vec4))) return kBadBuffer;
   XS_CHECK(hipSetDevice(dev));
-  if (mode < 0 || mode > 1 || (mode == 0) != (fold != nullptr) || seg_bytes < 16 || seg_bytes > 1024 ||
-      seg_bytes % 16 || stride_bytes % 128 || stride_bytes < static_cast<size_t>(seg_bytes) || touches == 0)
-    return -1000;
-  if (!buf || (reinterpret_cast<uintptr_t>(buf) & (sizeof(vec4) - 1))) return -1001;
-  const int grid = cu_count(dev) * 8;
-  const size_t sv = stride_bytes / sizeof(vec4);
-  const int lanes = seg_bytes / 16;
-  vec4* p = static_cast<vec4*>(buf);
+  int grid = 0;
+  XS_CHECK(xsprobe::cu_count(dev, &grid, kBlocksPerCu));
   Fold f;
-  if (mode == 0) {
+  if (mode == 0) {  // and only then is `fold` given: launch_segments runs the checked read
     if (int rc = f.init()) return rc;
-    if (nt) k_segments_fold<true><<<grid, kBlock>>>(p, touches, sv, lanes, f.d.as<unsigned long long>());
-    else k_segments_fold<false><<<grid, kBlock>>>(p, touches, sv, lanes, f.d.as<unsigned long long>());
-  } else if (nt) {
-    k_segments<1, true><<<grid, kBlock>>>(p, touches, sv, lanes, nullptr);
-  } else {
-    k_segments<1, false><<<grid, kBlock>>>(p, touches, sv, lanes, nullptr);
   }
+  launch_segments(mode, nt, grid, nullptr, static_cast<vec4*>(buf), touches, stride_bytes / sizeof(vec4),
+                  seg_bytes / 16, nullptr, f.d.as<unsigned long long>());
   XS_CHECK(hipGetLastError());
   XS_CHECK(hipDeviceSynchronize());
   return mode == 0 ? f.fetch(fold) : 0;
@@ -848,18 +790,37 @@ int xs_xcd_census(int dev, int blocks, int* xcd_hist8, int* distinct_cus) {
   return distinct;
 }
 
-int xs_checksum_op(int dev, const void* buf, size_t bytes, unsigned long long* out_sum);
-
 // k_pattern, launched as xs_health_check launches it, over a caller-owned
 // device buffer of `bytes` (a multiple of 4, 4-byte aligned): word i <-
 // uint32(i * 2654435761) ^ 0xa5a5a5a5.
 int xs_pattern_op(int dev, void* buf, size_t bytes) {
+  if (bytes == 0 || bytes % sizeof(uint32_t) != 0) return kBadArgs;
+  if (bad_buffer(buf, sizeof(uint32_t))) return kBadBuffer;
   XS_CHECK(hipSetDevice(dev));
-  if (bytes == 0 || bytes % sizeof(uint32_t) != 0) return -1000;
-  if (!buf || (reinterpret_cast<uintptr_t>(buf) & (sizeof(uint32_t) - 1))) return -1001;
-  k_pattern<<<cu_count(dev) * 8, kBlock>>>(static_cast<uint32_t*>(buf), bytes / sizeof(uint32_t));
+  int grid = 0;
+  XS_CHECK(xsprobe::cu_count(dev, &grid, kBlocksPerCu));
+  k_pattern<<<grid, kBlock>>>(static_cast<uint32_t*>(buf), bytes / sizeof(uint32_t));
   XS_CHECK(hipGetLastError());
   XS_CHECK(hipDeviceSynchronize());
+  return 0;
+}
+
+// k_checksum, launched as xs_health_check launches it, over a caller-owned
+// device buffer of `bytes` (a multiple of 4, 4-byte aligned): out_sum <- the
+// sum of its 32-bit words.
+int xs_checksum_op(int dev, const void* buf, size_t bytes, unsigned long long* out_sum) {
+  if (bytes == 0 || bytes % sizeof(uint32_t) != 0 || !out_sum) return kBadArgs;
+  if (bad_buffer(buf, sizeof(uint32_t))) return kBadBuffer;
+  XS_CHECK(hipSetDevice(dev));
+  int grid = 0;
+  XS_CHECK(xsprobe::cu_count(dev, &grid, kBlocksPerCu));
+  DevMem out;
+  XS_CHECK(hipMalloc(&out.p, sizeof(unsigned long long)));
+  XS_CHECK(hipMemset(out.p, 0, sizeof(unsigned long long)));
+  k_checksum<<<grid, kBlock>>>(static_cast<const uint32_t*>(buf), bytes / sizeof(uint32_t),
+                              out.as<unsigned long long>());
+  XS_CHECK(hipGetLastError());
+  XS_CHECK(hipMemcpy(out_sum, out.p, sizeof *out_sum, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -890,23 +851,6 @@ int xs_health_check(int dev, size_t bytes, unsigned long long* device_sum, unsig
   XS_CHECK(hipMalloc(&buf.p, n * sizeof(uint32_t)));
   if (int rc = xs_pattern_op(dev, buf.p, n * sizeof(uint32_t))) return rc;
   return xs_health_verify(dev, buf.p, n * sizeof(uint32_t), device_sum, host_sum);
-}
-
-// k_checksum, launched as xs_health_check launches it, over a caller-owned
-// device buffer of `bytes` (a multiple of 4, 4-byte aligned): out_sum <- the
-// sum of its 32-bit words.
-int xs_checksum_op(int dev, const void* buf, size_t bytes, unsigned long long* out_sum) {
-  XS_CHECK(hipSetDevice(dev));
-  if (bytes == 0 || bytes % sizeof(uint32_t) != 0 || !out_sum) return -1000;
-  if (!buf || (reinterpret_cast<uintptr_t>(buf) & (sizeof(uint32_t) - 1))) return -1001;
-  DevMem out;
-  XS_CHECK(hipMalloc(&out.p, sizeof(unsigned long long)));
-  XS_CHECK(hipMemset(out.p, 0, sizeof(unsigned long long)));
-  k_checksum<<<cu_count(dev) * 8, kBlock>>>(static_cast<const uint32_t*>(buf), bytes / sizeof(uint32_t),
-                                           out.as<unsigned long long>());
-  XS_CHECK(hipGetLastError());
-  XS_CHECK(hipMemcpy(out_sum, out.p, sizeof *out_sum, hipMemcpyDeviceToHost));
-  return 0;
 }
 
 }  // extern "C"

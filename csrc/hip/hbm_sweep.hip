@@ -275,11 +275,7 @@ __global__ __launch_bounds__(kBlock) void k_hbm_verify(vec4* __restrict__ buf, s
   }
 }
 
-int production_grid(int dev) {
-  hipDeviceProp_t p;
-  if (hipGetDeviceProperties(&p, dev) != hipSuccess) return 256 * kBlocksPerCu;
-  return p.multiProcessorCount * kBlocksPerCu;
-}
+hipError_t production_grid(int dev, int* grid) { return xsprobe::cu_count(dev, grid, kBlocksPerCu); }
 
 void launch_pass(int pass, int grid, hipStream_t s, void* buf, size_t n, uint64_t first_vec, uint32_t seed,
                  HbmSweepResult* res) {
@@ -322,7 +318,7 @@ int xs_hbm_sweep_op(int dev, int pass, void* buf, size_t bytes, uint64_t first_v
     return kBadArgs;
   if (!buf || (reinterpret_cast<uintptr_t>(buf) & (sizeof(vec4) - 1))) return kBadBuffer;
   XS_CHECK(hipSetDevice(dev));
-  if (grid == 0) grid = production_grid(dev);
+  if (grid == 0) XS_CHECK(production_grid(dev, &grid));
   DevMem res;
   if (pass != 0) {
     XS_CHECK(hipMalloc(&res.p, sizeof(HbmSweepResult)));
@@ -400,7 +396,8 @@ int xs_hbm_sweep(int dev, size_t bytes, size_t chunk_bytes, uint32_t seed, uint6
   const size_t res_bytes = 2 * got * sizeof(HbmSweepResult);
   XS_CHECK(hipMalloc(&res.p, res_bytes));
   XS_CHECK(hipMemset(res.p, 0, res_bytes));
-  const int grid = production_grid(dev);
+  int grid = 0;
+  XS_CHECK(production_grid(dev, &grid));
   Stream s;
   XS_CHECK(hipStreamCreateWithFlags(&s.s, hipStreamNonBlocking));
   Event ev[6];

@@ -49,6 +49,8 @@ namespace {
 xsprobe::ErrBuf g_mfma_err;
 
 using xsprobe::kBadArgs;
+using xsprobe::kCounterStride;
+using xsprobe::kMaxXcds;
 using xsprobe::xcc_id;
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -74,8 +76,6 @@ __global__ __launch_bounds__(64) void k_mfma_tile(const __bf16* __restrict__ A, 
   for (int q = 0; q < 16; ++q) C[((q & 3) + 8 * (q >> 2) + 4 * h) * 32 + r] = acc[q];
 }
 
-constexpr int kMaxXcds = 8;
-constexpr int kCounterStride = 32;          // unsigned per XCD counter: one 128-B line each
 constexpr int kMaxTileK = 4096;             // xs_mfma_tile_op: A and B of 256 KiB each
 constexpr int kMaxCheckedBlocks = 4096;     // xs_mfma_peak_op: 64 KiB of accumulators per workgroup
 constexpr uint32_t kDidNotRun = 0x80000000u;  // xcd_of_block flag of a workgroup that exited
@@ -149,14 +149,6 @@ inline double peak_flops(unsigned active, int iters) {
 }
 
 inline bool mask_ok(uint32_t xcd_mask) { return xcd_mask != 0 && !(xcd_mask & ~0xffu); }
-
-// Reads the eight per-XCD counters of one completed launch into per_xcd.
-int fetch_counters(const unsigned* d_active, unsigned per_xcd[kMaxXcds]) {
-  unsigned h[kMaxXcds * kCounterStride];
-  XS_CHECK(hipMemcpy(h, d_active, sizeof h, hipMemcpyDeviceToHost));
-  for (int x = 0; x < kMaxXcds; ++x) per_xcd[x] = h[x * kCounterStride];
-  return 0;
-}
 
 }  // namespace
 
@@ -248,27 +240,25 @@ int xs_mfma_peak_op(int dev, int iters, uint32_t xcd_mask, int blocks, float* ac
   if (!mask_ok(xcd_mask) || iters <= 0 || blocks < 0 || blocks > kMaxCheckedBlocks) return kBadArgs;
   if (!acc_out || !xcd_of_block_out || !active_per_xcd_out) return -1001;
   XS_CHECK(hipSetDevice(dev));
-  hipDeviceProp_t p;
-  XS_CHECK(hipGetDeviceProperties(&p, dev));
-  if (blocks == 0) blocks = 8 * p.multiProcessorCount;
+  if (blocks == 0) XS_CHECK(xsprobe::cu_count(dev, &blocks, 8));
   if (blocks > kMaxCheckedBlocks) return kBadArgs;
   const size_t acc_bytes = static_cast<size_t>(blocks) * kPeakBlock * kAcc * 16 * sizeof(float);
   const size_t xcd_bytes = static_cast<size_t>(blocks) * sizeof(uint32_t);
-  xsprobe::DevMem active_mem, acc_mem, xcd_mem;
-  XS_CHECK(hipMalloc(&active_mem.p, sizeof(unsigned) * kMaxXcds * kCounterStride));
+  xsprobe::XcdCounters active;
+  XS_CHECK(active.init());
+  xsprobe::DevMem acc_mem, xcd_mem;
   XS_CHECK(hipMalloc(&acc_mem.p, acc_bytes));
   XS_CHECK(hipMalloc(&xcd_mem.p, xcd_bytes));
-  XS_CHECK(hipMemset(active_mem.p, 0, sizeof(unsigned) * kMaxXcds * kCounterStride));
   XS_CHECK(hipMemset(acc_mem.p, 0xff, acc_bytes));
   XS_CHECK(hipMemset(xcd_mem.p, 0xff, xcd_bytes));
-  hipLaunchKernelGGL(k_mfma_peak<true>, dim3(blocks), dim3(kPeakBlock), 0, 0, iters, xcd_mask,
-                     active_mem.as<unsigned>(), static_cast<float*>(nullptr), acc_mem.as<float>(),
-                     xcd_mem.as<uint32_t>());
+  hipLaunchKernelGGL(k_mfma_peak<true>, dim3(blocks), dim3(kPeakBlock), 0, 0, iters, xcd_mask, active.of(0),
+                     static_cast<float*>(nullptr), acc_mem.as<float>(), xcd_mem.as<uint32_t>());
   XS_CHECK(hipGetLastError());
   XS_CHECK(hipDeviceSynchronize());
   XS_CHECK(hipMemcpy(acc_out, acc_mem.p, acc_bytes, hipMemcpyDeviceToHost));
   XS_CHECK(hipMemcpy(xcd_of_block_out, xcd_mem.p, xcd_bytes, hipMemcpyDeviceToHost));
-  return fetch_counters(active_mem.as<unsigned>(), active_per_xcd_out);
+  XS_CHECK(active.fetch(active_per_xcd_out));
+  return 0;
 }
 
 // Dense bf16 MFMA throughput on the XCDs of `xcd_mask` (0xff = whole GPU;
@@ -287,69 +277,48 @@ int xs_mfma_peak(int dev, int iters, uint32_t xcd_mask, int blocks, double* tflo
                  int* active_blocks, unsigned* active_per_xcd, double* flops_out) {
   if (!mask_ok(xcd_mask)) return kBadArgs;
   XS_CHECK(hipSetDevice(dev));
-  hipDeviceProp_t p;
-  XS_CHECK(hipGetDeviceProperties(&p, dev));
-  if (blocks <= 0) blocks = 8 * p.multiProcessorCount;
+  if (blocks <= 0) XS_CHECK(xsprobe::cu_count(dev, &blocks, 8));
   if (iters <= 0) iters = 4096;
-  xsprobe::DevMem active_mem, sink_mem;
-  const size_t ctr_bytes = sizeof(unsigned) * kMaxXcds * kCounterStride;
-  XS_CHECK(hipMalloc(&active_mem.p, ctr_bytes));
+  xsprobe::XcdCounters counters;  // [0] the warm-up launches', [1] the timed launch's
+  XS_CHECK(counters.init(2));
+  xsprobe::DevMem sink_mem;
   XS_CHECK(hipMalloc(&sink_mem.p, blocks * sizeof(float)));
-  unsigned* d_active = active_mem.as<unsigned>();
-  float* d_sink = sink_mem.as<float>();
   xsprobe::Stream stream;
   XS_CHECK(hipStreamCreate(&stream.s));
-  hipStream_t s = stream.s;
-  xsprobe::Event ev0, ev1;
-  XS_CHECK(hipEventCreate(&ev0.e));
-  XS_CHECK(hipEventCreate(&ev1.e));
-  hipEvent_t e0 = ev0.e, e1 = ev1.e;
-  auto go = [&] {
-    hipLaunchKernelGGL(k_mfma_peak<false>, dim3(blocks), dim3(kPeakBlock), 0, s, iters, xcd_mask, d_active, d_sink,
-                       static_cast<float*>(nullptr), static_cast<uint32_t*>(nullptr));
+  auto go = [&](int timed) {
+    hipLaunchKernelGGL(k_mfma_peak<false>, dim3(blocks), dim3(kPeakBlock), 0, stream.s, iters, xcd_mask,
+                       counters.of(timed), sink_mem.as<float>(), static_cast<float*>(nullptr),
+                       static_cast<uint32_t*>(nullptr));
   };
   // Warm-up: code resident, then about 20 ms of the same load so the clock has
   // ramped before the timed launch: 2.11 -> 2.40-2.41 PF/s in a fresh process
   // (profiles/r4za_probe_warm_ab.jsonl). The HBM probes are memory-bound and
   // read the same with or without it (same file), so they keep their short one.
-  float warm_ms = 0.f;
-  XS_CHECK(hipMemsetAsync(d_active, 0, ctr_bytes, s));
-  XS_CHECK(hipEventRecord(e0, s));
-  go();
-  XS_CHECK(hipGetLastError());
-  XS_CHECK(hipEventRecord(e1, s));
-  XS_CHECK(hipEventSynchronize(e1));
-  XS_CHECK(hipEventElapsedTime(&warm_ms, e0, e1));
-  const char* env = std::getenv("XS_PROBE_WARM_MS");  // as the HBM probes; 0 = one launch
+  double t[3];
+  if (int rc = xsprobe::time_launches(g_mfma_err, stream.s, 1, [&](int) { go(0); }, t)) return rc;
+  const float warm_ms = static_cast<float>(t[0]);
+  const char* env = std::getenv("XS_PROBE_WARM_MS");  // only this probe reads it; 0 = one launch
   const float target = env ? static_cast<float>(std::atof(env)) : 20.f;
   const int warm = target <= 0.f ? 0 : warm_ms > 0.f ? std::min(64, static_cast<int>(target / warm_ms) + 1) : 4;
-  for (int w = 0; w < warm; ++w) go();
-  XS_CHECK(hipGetLastError());
-  XS_CHECK(hipMemsetAsync(d_active, 0, ctr_bytes, s));
-  XS_CHECK(hipEventRecord(e0, s));
-  go();
-  XS_CHECK(hipGetLastError());
-  XS_CHECK(hipEventRecord(e1, s));
-  XS_CHECK(hipEventSynchronize(e1));
-  float ms = 0.f;
-  XS_CHECK(hipEventElapsedTime(&ms, e0, e1));
-  unsigned per_xcd[kMaxXcds];
-  if (int rc = fetch_counters(d_active, per_xcd)) return rc;
+  for (int w = 0; w < warm; ++w) go(0);
+  if (int rc = xsprobe::time_launches(g_mfma_err, stream.s, 1, [&](int) { go(1); }, t)) return rc;
+  const double ms = t[0];
+  unsigned both[2 * kMaxXcds];
+  XS_CHECK(counters.fetch(both));
+  const unsigned* per_xcd = both + kMaxXcds;
   unsigned active = 0;
-  char idle[32];
-  int k = 0;
+  uint32_t idle = 0;
   for (int x = 0; x < kMaxXcds; ++x) {
     active += per_xcd[x];
-    if (((xcd_mask >> x) & 1u) && per_xcd[x] == 0)
-      k += std::snprintf(idle + k, sizeof idle - k, "%s%d", k ? "," : "", x);
+    if (((xcd_mask >> x) & 1u) && per_xcd[x] == 0) idle |= 1u << x;
   }
   if (active_per_xcd)
     for (int x = 0; x < kMaxXcds; ++x) active_per_xcd[x] = per_xcd[x];
   *active_blocks = static_cast<int>(active);
-  if (k) {
+  if (idle) {
     std::snprintf(g_mfma_err, sizeof g_mfma_err,
-                  "k_mfma_peak: no workgroup ran on XCD(s) %s of xcd_mask 0x%x (%d workgroups launched, %u ran)", idle,
-                  xcd_mask, blocks, active);
+                  "k_mfma_peak: no workgroup ran on XCD(s) %s of xcd_mask 0x%x (%d workgroups launched, %u ran)",
+                  xsprobe::XcdList(idle).text, xcd_mask, blocks, active);
     return kIdleXcd;
   }
   const double flops = peak_flops(active, iters);

@@ -1,5 +1,6 @@
 // What the probe and sweep files share: where a wave runs, the wave
-// reductions, the error check, and the host side of a per-CU sweep launch.
+// reductions, the error check, the probes' CU count, launch timing and per-XCD
+// counters, and the host side of a per-CU sweep launch.
 //
 // A per-CU sweep (cu_sweep.hip, matrix_sweep.hip, regfile_sweep.hip,
 // lane_sweep.hip, valu_sweep.hip) is one launch of 256-thread workgroups of
@@ -22,6 +23,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstdio>
+#include <vector>
 
 #include "hip/device_raii.h"
 
@@ -101,6 +103,80 @@ constexpr size_t kLdsPerCu = 160u << 10;     // LDS of one gfx950 CU
 constexpr size_t kLdsExclusive = 96u << 10;  // > half a CU's LDS: one sweep workgroup per CU
 
 #define XS_ERR_BUF err
+
+// out = per_cu x the compute units of `dev`: a grid of per_cu workgroups per
+// CU. Like XcdCounters it returns the HIP error for the caller's XS_CHECK: one
+// body then serves files whose XS_ERR_RC differs.
+inline hipError_t cu_count(int dev, int* out, int per_cu = 1) {
+  hipDeviceProp_t p;
+  const hipError_t e = hipGetDeviceProperties(&p, dev);
+  if (e == hipSuccess) *out = per_cu * p.multiProcessorCount;
+  return e;
+}
+
+// Per-launch timing: `launch(i)` enqueues launch i; every launch sits
+// between its own event pair on `s`. out: [median ms, min ms, batch ms per
+// launch (first start to last end / iters)]. Events are created once.
+template <typename F>
+int time_launches(ErrBuf& err, hipStream_t s, int iters, F&& launch, double out[3]) {
+  std::vector<Event> ev(2 * static_cast<size_t>(iters));
+  for (auto& e : ev) XS_CHECK(hipEventCreate(&e.e));
+  for (int i = 0; i < iters; ++i) {
+    XS_CHECK(hipEventRecord(ev[2 * i].e, s));
+    launch(i);
+    XS_CHECK(hipEventRecord(ev[2 * i + 1].e, s));
+  }
+  XS_CHECK(hipEventSynchronize(ev.back().e));
+  XS_CHECK(hipGetLastError());
+  std::vector<double> per(iters);
+  for (int i = 0; i < iters; ++i) {
+    float ms = 0;
+    XS_CHECK(hipEventElapsedTime(&ms, ev[2 * i].e, ev[2 * i + 1].e));
+    per[i] = ms;
+  }
+  float total = 0;
+  XS_CHECK(hipEventElapsedTime(&total, ev.front().e, ev.back().e));
+  std::vector<double> sorted = per;
+  std::sort(sorted.begin(), sorted.end());
+  out[0] = sorted[sorted.size() / 2];
+  out[1] = sorted.front();
+  out[2] = static_cast<double>(total) / iters;
+  return 0;
+}
+
+// One counter per XCD and launch, each on its own 128-B line: k_pinned hands
+// out an XCD's chunks from it, k_mfma_peak counts the workgroups that ran
+// there, and the host reads which selected XCDs took part in a launch.
+constexpr int kMaxXcds = 8;
+constexpr int kCounterStride = 32;  // unsigned per XCD counter (128 B)
+
+struct XcdCounters {
+  DevMem d;
+  int launches = 0;
+  // Zeroed counters for `n` launches.
+  hipError_t init(int n = 1) {
+    launches = n;
+    const hipError_t e = hipMalloc(&d.p, sizeof(unsigned) * kMaxXcds * kCounterStride * n);
+    return e != hipSuccess ? e : hipMemset(d.p, 0, sizeof(unsigned) * kMaxXcds * kCounterStride * n);
+  }
+  unsigned* of(int launch) const { return d.as<unsigned>() + static_cast<size_t>(launch) * kMaxXcds * kCounterStride; }
+  // The eight counters of every launch, all completed, in one copy: per_xcd[launch * kMaxXcds + xcd].
+  hipError_t fetch(unsigned* per_xcd) const {
+    std::vector<unsigned> h(static_cast<size_t>(launches) * kMaxXcds * kCounterStride);
+    const hipError_t e = hipMemcpy(h.data(), d.p, sizeof(unsigned) * h.size(), hipMemcpyDeviceToHost);
+    for (int i = 0; i < launches * kMaxXcds; ++i) per_xcd[i] = h[static_cast<size_t>(i) * kCounterStride];
+    return e;
+  }
+};
+
+// The XCDs of `mask` as "0,3,5", for an error text.
+struct XcdList {
+  char text[32] = "";
+  explicit XcdList(uint32_t mask) {
+    for (int x = 0, k = 0; x < kMaxXcds; ++x)
+      if ((mask >> x) & 1u) k += std::snprintf(text + k, sizeof text - k, "%s%d", k ? "," : "", x);
+  }
+};
 
 // Largest dynamic LDS one workgroup may ask for on `dev`, in whole KiB.
 inline int max_workgroup_lds(ErrBuf& err, int dev, size_t* out) {

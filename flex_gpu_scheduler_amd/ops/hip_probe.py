@@ -43,7 +43,7 @@ class ProbeError(RuntimeError):
 
 BAD_ARGS = -1000
 # k_pinned: a selected XCD received no workgroup, so its slice of the buffer
-# was never processed (xs_pinned_op_g, xs_hbm_bandwidth_xcd_d).
+# was never processed (xs_pinned_op, xs_hbm_bandwidth_xcd).
 PINNED_UNDRAINED = -1002
 # k_mfma_peak: a selected XCD ran no workgroup, so the rate would be that of
 # fewer XCDs than asked for (xs_mfma_peak).
@@ -261,27 +261,20 @@ class HipProbe:
         L.xs_device_count.restype = ctypes.c_int
         L.xs_device_props.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
         L.xs_hbm_bandwidth.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                       ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
-        L.xs_hbm_bandwidth_v.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                         ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
+                                       ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                       ctypes.POINTER(ctypes.c_double)]
         L.xs_hbm_bandwidth_xcd.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
-                                           ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
-        L.xs_hbm_bandwidth_d.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                         ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
-                                         ctypes.POINTER(ctypes.c_double)]
-        L.xs_hbm_bandwidth_xcd_d.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint32,
-                                             ctypes.c_int, ctypes.POINTER(ctypes.c_double),
-                                             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
+                                           ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                           ctypes.POINTER(ctypes.c_double)]
         L.xs_xcd_census.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
                                     ctypes.POINTER(ctypes.c_int)]
         L.xs_health_check.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.POINTER(ctypes.c_ulonglong),
                                       ctypes.POINTER(ctypes.c_ulonglong)]
         L.xs_stream_op.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                   ctypes.c_size_t, ctypes.c_uint32, ctypes.c_float, ctypes.c_int]
+                                   ctypes.c_size_t, ctypes.c_uint32, ctypes.c_float, ctypes.c_int, ctypes.c_int,
+                                   ctypes.POINTER(ctypes.c_ulonglong)]
         L.xs_pinned_op.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-                                   ctypes.c_uint32]
-        L.xs_stream_op_g.argtypes = [*L.xs_stream_op.argtypes, ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong)]
-        L.xs_pinned_op_g.argtypes = [*L.xs_pinned_op.argtypes, ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong)]
+                                   ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong)]
         L.xs_checksum_op.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
                                      ctypes.POINTER(ctypes.c_ulonglong)]
         L.xs_segment_op.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_size_t,
@@ -358,25 +351,36 @@ class HipProbe:
         L.xs_hbm_sweep.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint64,
                                    ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
 
+    def _call(self, file: str, what: str, *args, wording: dict | None = None, value: bool = False) -> int:
+        """xs_<what>(*args), whose file's last error is xs_<file>_last_error
+        (xs_last_error for "", hbm_probe.hip). A ProbeError unless it returns
+        0 or, with `value`, a count of 0 or more, which is returned. `wording`
+        as in _probe_error."""
+        rc = getattr(self.lib, f"xs_{what}")(*args)
+        if rc < 0 or (rc and not value):
+            raise _probe_error(getattr(self.lib, f"xs_{file}_last_error" if file else "xs_last_error"), rc, what,
+                               wording)
+        return rc
+
     def device_count(self) -> int:
         return int(self.lib.xs_device_count())
 
     def props(self, dev: int = 0) -> dict:
         buf = ctypes.create_string_buffer(4096)
-        rc = self.lib.xs_device_props(dev, buf, len(buf))
-        if rc < 0:
-            raise _probe_error(self.lib.xs_last_error, rc, "device_props")
+        self._call("", "device_props", dev, buf, len(buf), value=True)
         return json.loads(buf.value.decode())
+
+    def _bandwidth(self, what: str, mode: str, nbytes: int, cus: int, *args) -> Bandwidth:
+        """The Bandwidth of xs_<what>(*args, gbps, ms_per_iter, detail) over `cus` CUs."""
+        g, ms = ctypes.c_double(), ctypes.c_double()
+        d = (ctypes.c_double * 3)()
+        self._call("", what, *args, ctypes.byref(g), ctypes.byref(ms), d)
+        return Bandwidth(mode, nbytes, g.value, ms.value, cus, d[0], d[1])
 
     def hbm_bandwidth(self, dev: int = 0, nbytes: int = DEFAULT_BYTES, iters: int = 20, cu_limit: int = 0,
                       mode: str = "copy", variant: int = 0) -> Bandwidth:
-        g, ms = ctypes.c_double(), ctypes.c_double()
-        d = (ctypes.c_double * 3)()
-        rc = self.lib.xs_hbm_bandwidth_d(dev, nbytes, iters, cu_limit, MODES[mode], variant, ctypes.byref(g),
-                                         ctypes.byref(ms), d)
-        if rc != 0:
-            raise _probe_error(self.lib.xs_last_error, rc, "hbm_bandwidth")
-        return Bandwidth(mode, nbytes, g.value, ms.value, cu_limit, d[0], d[1])
+        return self._bandwidth("hbm_bandwidth", mode, nbytes, cu_limit, dev, nbytes, iters, cu_limit, MODES[mode],
+                               variant)
 
     @staticmethod
     def variant(unroll: int = 4, nontemporal: bool = True, blocks_per_cu: int = 8) -> int:
@@ -409,13 +413,14 @@ class HipProbe:
     # must be imported before this library is loaded (one HIP runtime: both
     # resolve the soname libamdhip64.so.7 to the same copy).
     @staticmethod
-    def _dev_buf(t, what: str, granular: bool = True) -> tuple[int, int]:
-        """`granular` False leaves the 16-byte size and alignment check to the C ABI."""
+    def _dev_buf(t, what: str, granule: int = 16) -> tuple[int, int]:
+        """(pointer, bytes) of a device tensor whose size and address are
+        multiples of `granule`; 0 leaves that check to the C ABI."""
         if not t.is_cuda or not t.is_contiguous():
             raise ValueError(f"{what} must be a contiguous device tensor")
         nbytes = t.numel() * t.element_size()
-        if granular and (nbytes % 16 or t.data_ptr() % 16):
-            raise ValueError(f"{what}: {nbytes} bytes at {t.data_ptr():#x} is not 16-byte granular")
+        if granule and (nbytes % granule or t.data_ptr() % granule):
+            raise ValueError(f"{what}: {nbytes} bytes at {t.data_ptr():#x} is not {granule}-byte granular")
         return t.data_ptr(), nbytes
 
     # `grid` > 0 launches that many workgroups of 256 lanes instead of the
@@ -423,9 +428,7 @@ class HipProbe:
     # and the grid-stride path that production sizes reach.
     def _stream(self, dev: int, mode: int, a, b, c, nbytes: int, seed: int = 7, scale: float = 3.0,
                 variant: int = 0, grid: int = 0, fold=None) -> None:
-        rc = self.lib.xs_stream_op_g(dev, mode, a, b, c, nbytes, seed, scale, variant, grid, fold)
-        if rc != 0:
-            raise _probe_error(self.lib.xs_last_error, rc, "stream_op")
+        self._call("", "stream_op", dev, mode, a, b, c, nbytes, seed, scale, variant, grid, fold)
 
     def read_fold(self, src, variant: int = 0, grid: int = 0) -> tuple[int, int]:
         """k_read, checked instantiation: (XOR of every 32-bit word of `src`,
@@ -473,33 +476,23 @@ class HipProbe:
             ps, ns = self._dev_buf(src, "src")
             if ns != n:
                 raise ValueError("pinned: size mismatch")
-        rc = self.lib.xs_pinned_op_g(dst.device.index or 0, 2 if src is not None else 1, ps or None, pd, n, xcd_mask,
-                                     grid, None)
-        if rc != 0:
-            raise _probe_error(self.lib.xs_last_error, rc, "pinned_op")
+        self._call("", "pinned_op", dst.device.index or 0, 2 if src is not None else 1, ps or None, pd, n, xcd_mask,
+                   grid, None)
 
     def pinned_read_fold(self, src, xcd_mask: int = 0x1, grid: int = 0) -> tuple[int, int]:
         """k_pinned's read mode, checked instantiation: (XOR of every 32-bit
         word of `src`, number of 16-B loads issued)."""
         ps, n = self._dev_buf(src, "src")
         fold = (ctypes.c_ulonglong * 2)()
-        rc = self.lib.xs_pinned_op_g(src.device.index or 0, 0, ps, None, n, xcd_mask, grid, fold)
-        if rc != 0:
-            raise _probe_error(self.lib.xs_last_error, rc, "pinned_op")
+        self._call("", "pinned_op", src.device.index or 0, 0, ps, None, n, xcd_mask, grid, fold)
         return int(fold[0]), int(fold[1])
 
     def checksum(self, buf) -> int:
         """k_checksum (the health check's kernel) over a device tensor: the
         sum of its 32-bit words."""
-        if not buf.is_cuda or not buf.is_contiguous():
-            raise ValueError("buf must be a contiguous device tensor")
-        nbytes = buf.numel() * buf.element_size()
-        if nbytes % 4 or buf.data_ptr() % 4:
-            raise ValueError(f"buf: {nbytes} bytes at {buf.data_ptr():#x} is not 4-byte granular")
+        p, n = self._dev_buf(buf, "buf", granule=4)
         out = ctypes.c_ulonglong()
-        rc = self.lib.xs_checksum_op(buf.device.index or 0, buf.data_ptr(), nbytes, ctypes.byref(out))
-        if rc != 0:
-            raise _probe_error(self.lib.xs_last_error, rc, "checksum_op")
+        self._call("", "checksum_op", buf.device.index or 0, p, n, ctypes.byref(out))
         return int(out.value)
 
     def segment_op(self, buf, mode: str = "read", seg_bytes: int = 128, stride_bytes: int = 4096, touches: int = 1,
@@ -512,21 +505,14 @@ class HipProbe:
         if n != stride_bytes * touches:
             raise ValueError(f"segment_op: buf holds {n} bytes, not {stride_bytes} x {touches}")
         fold = (ctypes.c_ulonglong * 2)() if mode == "read" else None
-        rc = self.lib.xs_segment_op(buf.device.index or 0, MODES[mode], int(nontemporal), seg_bytes, stride_bytes,
-                                    touches, p, fold)
-        if rc != 0:
-            raise _probe_error(self.lib.xs_last_error, rc, "segment_op")
+        self._call("", "segment_op", buf.device.index or 0, MODES[mode], int(nontemporal), seg_bytes, stride_bytes,
+                   touches, p, fold)
         return (int(fold[0]), int(fold[1])) if fold is not None else None
 
     def hbm_bandwidth_xcd(self, dev: int = 0, xcd_mask: int = 0x1, nbytes: int = DEFAULT_BYTES, iters: int = 10,
                           mode: str = "read") -> Bandwidth:
-        g, ms = ctypes.c_double(), ctypes.c_double()
-        d = (ctypes.c_double * 3)()
-        rc = self.lib.xs_hbm_bandwidth_xcd_d(dev, nbytes, iters, xcd_mask, MODES[mode], ctypes.byref(g),
-                                             ctypes.byref(ms), d)
-        if rc != 0:
-            raise _probe_error(self.lib.xs_last_error, rc, "hbm_bandwidth_xcd")
-        return Bandwidth(mode, nbytes, g.value, ms.value, bin(xcd_mask).count("1") * 32, d[0], d[1])
+        return self._bandwidth("hbm_bandwidth_xcd", mode, nbytes, bin(xcd_mask).count("1") * 32, dev, nbytes, iters,
+                               xcd_mask, MODES[mode])
 
     def partition_table(self, dev: int = 0, nbytes: int = DEFAULT_BYTES, iters: int = 10) -> dict:
         """HBM read/copy GB/s that the CUs of one compute partition pull, for
@@ -568,10 +554,8 @@ class HipProbe:
         `stride_bytes` slot -- a dispatch of known bytes and 128-B lines, for
         calibrating rocprofv3's L2 request counters (scripts/pmc_calibrate.sh)."""
         out = (ctypes.c_double * 3)()
-        rc = self.lib.xs_segment_access(dev, MODES[mode], int(nontemporal), seg_bytes, stride_bytes, touches, iters,
-                                        out)
-        if rc != 0:
-            raise _probe_error(self.lib.xs_last_error, rc, "segment_access")
+        self._call("", "segment_access", dev, MODES[mode], int(nontemporal), seg_bytes, stride_bytes, touches, iters,
+                   out)
         return {"kernel": "k_segments", "mode": mode, "nontemporal": nontemporal, "seg_bytes": seg_bytes,
                 "stride_bytes": stride_bytes, "touches": touches, "ms": round(out[0], 4),
                 "bytes_per_dispatch": int(out[1]), "lines128_per_dispatch": int(out[2])}
@@ -579,44 +563,33 @@ class HipProbe:
     def xcd_census(self, dev: int = 0, blocks: int = 4096) -> dict:
         hist = (ctypes.c_int * 8)()
         cus = ctypes.c_int()
-        rc = self.lib.xs_xcd_census(dev, blocks, hist, ctypes.byref(cus))
-        if rc < 0:
-            raise _probe_error(self.lib.xs_last_error, rc, "xcd_census")
+        rc = self._call("", "xcd_census", dev, blocks, hist, ctypes.byref(cus), value=True)
         return {"distinct_xcds": rc, "blocks_per_xcd": list(hist), "distinct_cu_slots": cus.value}
 
     def health(self, dev: int = 0, nbytes: int = 64 << 20) -> dict:
         d, h = ctypes.c_ulonglong(), ctypes.c_ulonglong()
-        rc = self.lib.xs_health_check(dev, nbytes, ctypes.byref(d), ctypes.byref(h))
-        if rc < 0:
-            raise _probe_error(self.lib.xs_last_error, rc, "health_check")
+        rc = self._call("", "health_check", dev, nbytes, ctypes.byref(d), ctypes.byref(h), value=True)
         return {"healthy": rc == 0, "device_sum": d.value, "host_sum": h.value}
-
 
     def pattern(self, buf) -> None:
         """k_pattern (the health check's fill) over a device tensor: 32-bit
         word i <- uint32(i * 2654435761) ^ 0xa5a5a5a5."""
-        p, n = self._dev_buf(buf, "buf", granular=False)
-        rc = self.lib.xs_pattern_op(buf.device.index or 0, p, n)
-        if rc != 0:
-            raise _probe_error(self.lib.xs_last_error, rc, "pattern_op")
+        p, n = self._dev_buf(buf, "buf", granule=0)
+        self._call("", "pattern_op", buf.device.index or 0, p, n)
 
     def health_verify(self, buf) -> dict:
         """The health check's verdict over a device tensor: k_checksum's sum
         of its words against the host's sum of the pattern for that size."""
-        p, n = self._dev_buf(buf, "buf", granular=False)
+        p, n = self._dev_buf(buf, "buf", granule=0)
         d, h = ctypes.c_ulonglong(), ctypes.c_ulonglong()
-        rc = self.lib.xs_health_verify(buf.device.index or 0, p, n, ctypes.byref(d), ctypes.byref(h))
-        if rc < 0:
-            raise _probe_error(self.lib.xs_last_error, rc, "health_verify")
+        rc = self._call("", "health_verify", buf.device.index or 0, p, n, ctypes.byref(d), ctypes.byref(h), value=True)
         return {"healthy": rc == 0, "device_sum": d.value, "host_sum": h.value}
 
     def mfma_check(self, dev: int = 0, k: int = 64) -> dict:
         """C[32x32] = A·B through v_mfma_f32_32x32x16_bf16 on exact integers.
         `k`: a positive multiple of 16, at most mfma_max_k() (ProbeError with
         rc BAD_ARGS otherwise)."""
-        rc = self.lib.xs_mfma_check(dev, k)
-        if rc < 0:
-            raise _probe_error(self.lib.xs_mfma_last_error, rc, "mfma_check", MFMA_WORDING)
+        rc = self._call("mfma", "mfma_check", dev, k, wording=MFMA_WORDING, value=True)
         return {"healthy": rc == 0, "mismatches": int(rc), "k": k}
 
     def mfma_max_k(self) -> int:
@@ -627,9 +600,7 @@ class HipProbe:
         import numpy as np
 
         a, b = np.zeros((32, max(k, 0)), np.int32), np.zeros((max(k, 0), 32), np.int32)
-        rc = self.lib.xs_mfma_inputs(k, a.ctypes.data, b.ctypes.data)
-        if rc != 0:
-            raise _probe_error(self.lib.xs_mfma_last_error, rc, "mfma_inputs", MFMA_WORDING)
+        self._call("mfma", "mfma_inputs", k, a.ctypes.data, b.ctypes.data, wording=MFMA_WORDING)
         return a, b
 
     def mfma_compare(self, k: int, c, cap: int = 32) -> tuple[int, list[int]]:
@@ -642,9 +613,7 @@ class HipProbe:
         if c.shape != (32, 32):
             raise ValueError(f"mfma_compare: C is {c.shape}, not (32, 32)")
         idx = np.full(max(cap, 1), -1, np.int32)
-        rc = self.lib.xs_mfma_compare(k, c.ctypes.data, idx.ctypes.data, cap)
-        if rc < 0:
-            raise _probe_error(self.lib.xs_mfma_last_error, rc, "mfma_compare", MFMA_WORDING)
+        rc = self._call("mfma", "mfma_compare", k, c.ctypes.data, idx.ctypes.data, cap, wording=MFMA_WORDING, value=True)
         return int(rc), [int(i) for i in idx[:min(rc, cap)]]
 
     def mfma_tile(self, a_bits, b_bits, dev: int = 0):
@@ -659,9 +628,8 @@ class HipProbe:
         if a.ndim != 2 or a.shape[0] != 32 or b.shape != (a.shape[1], 32):
             raise ValueError(f"mfma_tile: A {a.shape} and B {b.shape} are not [32, K] and [K, 32]")
         c = np.zeros((32, 32), np.float32)
-        rc = self.lib.xs_mfma_tile_op(dev, a.ctypes.data, b.ctypes.data, a.shape[1], c.ctypes.data)
-        if rc != 0:
-            raise _probe_error(self.lib.xs_mfma_last_error, rc, "mfma_tile_op", MFMA_WORDING)
+        self._call("mfma", "mfma_tile_op", dev, a.ctypes.data, b.ctypes.data, a.shape[1], c.ctypes.data,
+                   wording=MFMA_WORDING)
         return c
 
     def mfma_peak_op(self, dev: int = 0, xcd_mask: int = 0xFF, iters: int = 1, blocks: int = 0) -> dict:
@@ -675,9 +643,8 @@ class HipProbe:
         acc = np.zeros((n, MFMA_PEAK_BLOCK, MFMA_PEAK_ACC, 16), np.float32)
         xcd = np.zeros(n, np.uint32)
         per = (ctypes.c_uint * 8)()
-        rc = self.lib.xs_mfma_peak_op(dev, iters, xcd_mask, n, acc.ctypes.data, xcd.ctypes.data, per)
-        if rc != 0:
-            raise _probe_error(self.lib.xs_mfma_last_error, rc, "mfma_peak_op", MFMA_WORDING)
+        self._call("mfma", "mfma_peak_op", dev, iters, xcd_mask, n, acc.ctypes.data, xcd.ctypes.data, per,
+                   wording=MFMA_WORDING)
         return {"acc": acc, "xcd": (xcd & 0xF).astype(np.int64), "ran": (xcd & MFMA_DID_NOT_RUN) == 0,
                 "raw_xcd": xcd, "active_per_xcd": [int(v) for v in per], "iters": iters, "xcd_mask": xcd_mask}
 
@@ -688,21 +655,12 @@ class HipProbe:
         MFMA_IDLE_XCD when a selected XCD ran no workgroup."""
         tf, ms, act, fl = ctypes.c_double(), ctypes.c_double(), ctypes.c_int(), ctypes.c_double()
         per = (ctypes.c_uint * 8)()
-        rc = self.lib.xs_mfma_peak(dev, iters, xcd_mask, blocks, ctypes.byref(tf), ctypes.byref(ms), ctypes.byref(act),
-                                   per, ctypes.byref(fl))
-        if rc != 0:
-            raise _probe_error(self.lib.xs_mfma_last_error, rc, "mfma_peak", MFMA_WORDING)
+        self._call("mfma", "mfma_peak", dev, iters, xcd_mask, blocks, ctypes.byref(tf), ctypes.byref(ms),
+                   ctypes.byref(act), per, ctypes.byref(fl), wording=MFMA_WORDING)
         return {"tflops": tf.value, "ms": ms.value, "active_blocks": act.value, "xcd_mask": xcd_mask,
                 "active_per_xcd": [int(v) for v in per], "flops": fl.value, "iters": iters if iters > 0 else 4096}
 
-
     # ------------------------------------------------------ the per-CU sweeps
-    def _call(self, sweep: str, what: str, *args) -> None:
-        """xs_<what>(*args) of the file of <sweep>; a ProbeError unless it returns 0."""
-        rc = getattr(self.lib, f"xs_{what}")(*args)
-        if rc != 0:
-            raise _probe_error(getattr(self.lib, f"xs_{sweep}_last_error"), rc, what)
-
     def _sweep_until_covered(self, name: str, dev: int, blocks: int, max_rounds: int, words: int, launch, expected,
                              decode, summarize) -> dict:
         """The launch policy of every per-CU sweep. A launch whose grid could
@@ -1067,9 +1025,8 @@ class HipProbe:
         import numpy as np
 
         out = np.zeros((nvec, 4), np.uint32)
-        rc = self.lib.xs_hbm_sweep_pattern(first_vec, nvec, seed, int(inverted), out.ctypes.data)
-        if rc != 0:
-            raise _probe_error(self.lib.xs_hbm_sweep_last_error, rc, "hbm_sweep_pattern", HBM_WORDING)
+        self._call("hbm_sweep", "hbm_sweep_pattern", first_vec, nvec, seed, int(inverted), out.ctypes.data,
+                   wording=HBM_WORDING)
         return out
 
     def hbm_sweep_op(self, buf, pass_: int, first_vec: int = 0, seed: int = HBM_SWEEP_SEED,
@@ -1082,12 +1039,10 @@ class HipProbe:
         bad_vectors, bad_bits, one_to_zero, zero_to_one, flip_or [4],
         reader_xcd_mask, log_claims and log (at most 32 entries). Size and
         alignment are the C ABI's to refuse (ProbeError, rc -1000 / -1001)."""
-        p, n = self._dev_buf(buf, "buf", granular=False)
+        p, n = self._dev_buf(buf, "buf", granule=0)
         res = _HbmSweepResult()
-        rc = self.lib.xs_hbm_sweep_op(buf.device.index or 0, pass_, p, n, first_vec, seed, grid,
-                                      ctypes.addressof(res) if pass_ != 0 else None)
-        if rc != 0:
-            raise _probe_error(self.lib.xs_hbm_sweep_last_error, rc, "hbm_sweep_op", HBM_WORDING)
+        self._call("hbm_sweep", "hbm_sweep_op", buf.device.index or 0, pass_, p, n, first_vec, seed, grid,
+                   ctypes.addressof(res) if pass_ != 0 else None, wording=HBM_WORDING)
         if pass_ == 0:
             return None
         fold = 0
@@ -1115,10 +1070,8 @@ class HipProbe:
             iv, iw, im, ip = (int(x) for x in inject)
         s = _HbmSweepSummary()
         log = (_HbmLogEntry * HBM_SWEEP_LOG_CAP)()
-        rc = self.lib.xs_hbm_sweep(dev, nbytes, chunk_bytes, seed, iv, iw, im, ip, ctypes.addressof(s),
-                                   ctypes.addressof(log))
-        if rc != 0:
-            raise _probe_error(self.lib.xs_hbm_sweep_last_error, rc, "hbm_sweep", HBM_WORDING)
+        self._call("hbm_sweep", "hbm_sweep", dev, nbytes, chunk_bytes, seed, iv, iw, im, ip, ctypes.addressof(s),
+                   ctypes.addressof(log), wording=HBM_WORDING)
         raw = {"bytes_requested": int(s.bytes_requested), "bytes_tested": int(s.bytes_tested),
                "chunk_bytes": int(s.chunk_bytes), "chunks": int(s.chunks), "short": bool(s.short),
                "vectors_read": int(s.vectors_read), "fold": [int(f) for f in s.fold],
