@@ -1,5 +1,6 @@
 #include "api/resource.h"
 
+#include <charconv>
 #include <stdexcept>
 
 namespace xsched {
@@ -92,7 +93,11 @@ Res Res::from_json(const Json& rl) {
     } else if (kv.second.is_int()) {
       q = Quantity::from_int(kv.second.as_int());
     } else if (kv.second.is_number()) {
-      q = Quantity::parse(std::to_string(kv.second.as_double()));
+      // The shortest text that reads back as this double: what the document
+      // said, up to spelling (5e-7 stays 5e-7; "%f" made it 0.000000).
+      char buf[32];
+      auto r = std::to_chars(buf, buf + sizeof buf, kv.second.as_double());
+      q = Quantity::parse(std::string_view(buf, static_cast<size_t>(r.ptr - buf)));
     } else {
       continue;
     }

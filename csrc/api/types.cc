@@ -1,9 +1,11 @@
 #include "api/types.h"
 
 #include <algorithm>
+#include <charconv>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <limits>
 #include <mutex>
 #include <unordered_set>
 
@@ -102,6 +104,35 @@ MicroTime wall_now_us() {
       .count();
 }
 
+// ------------------------------------------------------------- numbers ----
+namespace {
+// A JSON number as an int32 field: toward zero, saturating (never wrapped).
+int32_t as_i32(const Json& j, int32_t dflt = 0) {
+  if (!j.is_number()) return dflt;
+  return static_cast<int32_t>(std::clamp<int64_t>(j.as_int(), std::numeric_limits<int32_t>::min(),
+                                                  std::numeric_limits<int32_t>::max()));
+}
+
+// The whole of `s` as a decimal integer (optional '-', then digits only).
+// A value outside T is not a T: false, like text that is no number at all.
+template <typename T>
+bool parse_whole(std::string_view s, T* out) {
+  auto r = std::from_chars(s.data(), s.data() + s.size(), *out, 10);
+  return r.ec == std::errc() && r.ptr == s.data() + s.size() && !s.empty();
+}
+
+// metadata.resourceVersion as text: a decimal integer, saturating; other
+// text reads as 0, like a missing one.
+int64_t parse_resource_version(const std::string& s) {
+  int64_t v = 0;
+  auto r = std::from_chars(s.data(), s.data() + s.size(), v, 10);
+  if (s.empty() || r.ptr != s.data() + s.size()) return 0;
+  if (r.ec == std::errc::result_out_of_range)
+    return s[0] == '-' ? std::numeric_limits<int64_t>::min() : std::numeric_limits<int64_t>::max();
+  return r.ec == std::errc() ? v : 0;
+}
+}  // namespace
+
 // ---------------------------------------------------------------- maps ----
 const std::string* strmap_get(const StrMap& m, std::string_view k) {
   for (const auto& kv : m)
@@ -123,7 +154,7 @@ ObjectMeta ObjectMeta::from_json(const Json& obj) {
   m.name = md["name"].as_string();
   m.uid = md["uid"].as_string();
   const Json& rv = md["resourceVersion"];
-  m.resource_version = rv.is_string() ? std::atoll(rv.as_string().c_str()) : rv.as_int();
+  m.resource_version = rv.is_string() ? parse_resource_version(rv.as_string()) : rv.as_int();
   m.labels = strmap_from_json(md["labels"]);
   m.annotations = strmap_from_json(md["annotations"]);
   if (md["creationTimestamp"].is_string()) m.creation = parse_rfc3339(md["creationTimestamp"].as_string());
@@ -224,7 +255,7 @@ Container parse_container(const Json& c) {
   }
   for (const auto& p : c["ports"].items()) {
     ContainerPort cp;
-    cp.host_port = static_cast<int32_t>(p["hostPort"].as_int(0));
+    cp.host_port = as_i32(p["hostPort"]);
     cp.protocol = p["protocol"].str_or("TCP");
     cp.host_ip = p["hostIP"].str_or("0.0.0.0");
     out.ports.push_back(cp);
@@ -253,10 +284,23 @@ void parse_pod_affinity(const Json& a, std::vector<PodAffinityTerm>* req, std::v
     req->push_back(parse_pod_affinity_term(t));
   for (const auto& t : a["preferredDuringSchedulingIgnoredDuringExecution"].items()) {
     WeightedPodAffinityTerm w;
-    w.weight = static_cast<int32_t>(t["weight"].as_int());
+    w.weight = as_i32(t["weight"]);
     w.term = parse_pod_affinity_term(t["podAffinityTerm"]);
     pref->push_back(std::move(w));
   }
+}
+
+// a += b, each sum held at the int64 bounds: a pod that asks for 2^63-1 of
+// something plus overhead asks for a lot, never for a negative amount.
+void add_saturating(Res& a, const Res& b) {
+  for (uint64_t m = b.mask; m; m &= m - 1) {
+    int i = __builtin_ctzll(m);
+    int64_t sum;
+    if (__builtin_add_overflow(a.v[i], b.v[i], &sum))
+      sum = b.v[i] > 0 ? std::numeric_limits<int64_t>::max() : std::numeric_limits<int64_t>::min();
+    a.v[i] = sum;
+  }
+  a.mask |= b.mask;
 }
 
 // Defaults from pkg/scheduler/util/non_zero.go (DefaultMilliCPURequest=100m,
@@ -283,19 +327,45 @@ QoS compute_qos(const Pod& p) {
   return guaranteed ? QoS::Guaranteed : QoS::Burstable;
 }
 
-std::vector<int> parse_int_list(const std::string& s) {
-  std::vector<int> out;
-  size_t i = 0;
-  while (i < s.size()) {
+// Calls fn(token) for each comma-separated token of `s` (strings.Split: an
+// empty string is one empty token); stops and returns false when fn does.
+template <typename F>
+bool each_token(std::string_view s, F&& fn) {
+  for (size_t i = 0;;) {
     size_t j = s.find(',', i);
-    if (j == std::string::npos) j = s.size();
-    std::string tok = s.substr(i, j - i);
-    char* e = nullptr;
-    long v = std::strtol(tok.c_str(), &e, 10);
-    if (!tok.empty() && e && *e == '\0' && v >= 0) out.push_back(static_cast<int>(v));
-    else return {};
+    if (!fn(s.substr(i, j == std::string_view::npos ? j : j - i))) return false;
+    if (j == std::string_view::npos) return true;
     i = j + 1;
   }
+}
+
+// "0,3": non-negative ints that fit. Anything else makes the annotation
+// unparsable: the empty list.
+std::vector<int> parse_int_list(const std::string& s) {
+  std::vector<int> out;
+  bool ok = each_token(s, [&](std::string_view tok) {
+    int v = 0;
+    if (!parse_whole(tok, &v) || v < 0) return false;
+    out.push_back(v);
+    return true;
+  });
+  if (!ok) out.clear();
+  return out;
+}
+
+// "gpu:partition,gpu:partition", read the same way.
+std::vector<std::pair<int, int>> parse_partition_list(const std::string& s) {
+  std::vector<std::pair<int, int>> out;
+  bool ok = each_token(s, [&](std::string_view tok) {
+    size_t c = tok.find(':');
+    int g = 0, part = 0;
+    if (c == std::string_view::npos || !parse_whole(tok.substr(0, c), &g) || !parse_whole(tok.substr(c + 1), &part) ||
+        g < 0 || part < 0)
+      return false;
+    out.emplace_back(g, part);
+    return true;
+  });
+  if (!ok) out.clear();
   return out;
 }
 }  // namespace
@@ -307,20 +377,7 @@ void Pod::recompute_gpu_assignment(const GpuNames& gn) {
   std::vector<int> gpus = parse_int_list(*idx);
   if (gpus.empty()) return;  // unparsable annotation: skipped (gpu_node.go:91-96)
   std::vector<std::pair<int, int>> parts;
-  if (const std::string* ps = meta.annotation(gn.partition_annotation)) {
-    size_t i = 0;
-    const std::string& s = *ps;
-    while (i < s.size()) {
-      size_t j = s.find(',', i);
-      if (j == std::string::npos) j = s.size();
-      std::string tok = s.substr(i, j - i);
-      size_t c = tok.find(':');
-      if (c != std::string::npos) {
-        parts.emplace_back(std::atoi(tok.substr(0, c).c_str()), std::atoi(tok.substr(c + 1).c_str()));
-      }
-      i = j + 1;
-    }
-  }
+  if (const std::string* ps = meta.annotation(gn.partition_annotation)) parts = parse_partition_list(*ps);
   set_gpu_assignment(std::move(gpus), std::move(parts), gn);
 }
 
@@ -378,7 +435,7 @@ std::shared_ptr<Pod> Pod::from_json(const Json& obj, const GpuNames& gn) {
   if (spec["schedulerName"].is_string()) p->scheduler_name = spec["schedulerName"].as_string();
   p->node_name = spec["nodeName"].as_string();
   p->priority_class_name = spec["priorityClassName"].as_string();
-  p->priority = static_cast<int32_t>(spec["priority"].as_int(0));
+  p->priority = as_i32(spec["priority"]);
   if (spec["preemptionPolicy"].is_string()) p->preemption_policy = spec["preemptionPolicy"].as_string();
   {
     std::vector<Container> cs, ics;
@@ -398,7 +455,7 @@ std::shared_ptr<Pod> Pod::from_json(const Json& obj, const GpuNames& gn) {
     }
     for (const auto& t : (*na)["preferredDuringSchedulingIgnoredDuringExecution"].items()) {
       PreferredSchedulingTerm pt;
-      pt.weight = static_cast<int32_t>(t["weight"].as_int());
+      pt.weight = as_i32(t["weight"]);
       pt.pref = parse_term(t["preference"]);
       p->preferred_node_terms.push_back(std::move(pt));
     }
@@ -409,7 +466,7 @@ std::shared_ptr<Pod> Pod::from_json(const Json& obj, const GpuNames& gn) {
     parse_pod_affinity(*paa, &p->pod_anti_affinity_required, &p->pod_anti_affinity_preferred);
   for (const auto& c : spec["topologySpreadConstraints"].items()) {
     TopologySpreadConstraint tc;
-    tc.max_skew = static_cast<int32_t>(c["maxSkew"].as_int(1));
+    tc.max_skew = as_i32(c["maxSkew"], 1);
     tc.topology_key = c["topologyKey"].as_string();
     tc.hard = c["whenUnsatisfiable"].str_or("DoNotSchedule") != "ScheduleAnyway";
     tc.selector = LabelSelector::from_json(c.get("labelSelector"));
@@ -434,12 +491,12 @@ std::shared_ptr<Pod> Pod::from_json(const Json& obj, const GpuNames& gn) {
   // Derived request/limit vectors.
   Res sum;
   for (const auto& c : p->containers) {
-    sum += c.requests;
-    res->limit_sum += c.limits;
+    add_saturating(sum, c.requests);
+    add_saturating(res->limit_sum, c.limits);
     Res nz;
     nz.set(kCPU, c.requests.has(kCPU) && c.requests.get(kCPU) != 0 ? c.requests.get(kCPU) : kDefaultMilliCPU);
     nz.set(kMemory, c.requests.has(kMemory) && c.requests.get(kMemory) != 0 ? c.requests.get(kMemory) : kDefaultMemory);
-    res->nonzero_request += nz;
+    add_saturating(res->nonzero_request, nz);
     for (const auto& port : c.ports)
       if (port.host_port > 0) p->host_ports.push_back(port);
   }
@@ -454,8 +511,8 @@ std::shared_ptr<Pod> Pod::from_json(const Json& obj, const GpuNames& gn) {
     nz.set(kMemory, c.requests.has(kMemory) && c.requests.get(kMemory) != 0 ? c.requests.get(kMemory) : kDefaultMemory);
     res->nonzero_request.set_max(nz);
   }
-  sum += res->overhead;
-  res->nonzero_request += res->overhead;
+  add_saturating(sum, res->overhead);
+  add_saturating(res->nonzero_request, res->overhead);
   res->request = sum;
   p->res = std::move(res);
   p->qos = compute_qos(*p);

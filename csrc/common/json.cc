@@ -1,9 +1,13 @@
 #include "common/json.h"
 
+#include <array>
 #include <cerrno>
+#include <charconv>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
+#include <limits>
 
 namespace xsched {
 
@@ -155,72 +159,157 @@ class Parser {
     return v;
   }
 
+  // 1 for the bytes that end a run of plain string bytes: the quote, the
+  // backslash, the control bytes (refused) and every byte of a multi-byte
+  // UTF-8 sequence (validated).
+  static constexpr auto kStop = [] {
+    std::array<uint8_t, 256> t{};
+    for (int c = 0; c < 0x20; ++c) t[c] = 1;
+    for (int c = 0x80; c < 0x100; ++c) t[c] = 1;
+    t['"'] = 1;
+    t['\\'] = 1;
+    return t;
+  }();
+
+  // One well-formed multi-byte sequence (Unicode 15, table 3-7): no overlong
+  // form, no surrogate, nothing above U+10FFFF.
+  void utf8_sequence() {
+    auto cont = [&](int k, unsigned lo, unsigned hi) {
+      if (end_ - p_ <= k) fail("truncated UTF-8 sequence");
+      unsigned char c = static_cast<unsigned char>(p_[k]);
+      if (c < lo || c > hi) fail("invalid UTF-8 sequence");
+    };
+    unsigned char c = static_cast<unsigned char>(*p_);
+    if (c >= 0xC2 && c <= 0xDF) {
+      cont(1, 0x80, 0xBF);
+      p_ += 2;
+    } else if (c >= 0xE0 && c <= 0xEF) {
+      cont(1, c == 0xE0 ? 0xA0 : 0x80, c == 0xED ? 0x9F : 0xBF);
+      cont(2, 0x80, 0xBF);
+      p_ += 3;
+    } else if (c >= 0xF0 && c <= 0xF4) {
+      cont(1, c == 0xF0 ? 0x90 : 0x80, c == 0xF4 ? 0x8F : 0xBF);
+      cont(2, 0x80, 0xBF);
+      cont(3, 0x80, 0xBF);
+      p_ += 4;
+    } else {
+      fail("invalid UTF-8 byte");
+    }
+  }
+
   std::string string() {
     ++p_;  // opening quote
     std::string out;
     const char* run = p_;
     while (p_ < end_) {
-      char c = *p_;
+      unsigned char c = static_cast<unsigned char>(*p_);
+      if (!kStop[c]) {
+        ++p_;
+        continue;
+      }
       if (c == '"') {
         out.append(run, p_);
         ++p_;
         return out;
       }
-      if (c == '\\') {
-        out.append(run, p_);
-        ++p_;
-        if (p_ >= end_) fail("bad escape");
-        char e = *p_++;
-        switch (e) {
-          case '"': out.push_back('"'); break;
-          case '\\': out.push_back('\\'); break;
-          case '/': out.push_back('/'); break;
-          case 'b': out.push_back('\b'); break;
-          case 'f': out.push_back('\f'); break;
-          case 'n': out.push_back('\n'); break;
-          case 'r': out.push_back('\r'); break;
-          case 't': out.push_back('\t'); break;
-          case 'u': {
-            uint32_t cp = hex4();
-            if (cp >= 0xD800 && cp <= 0xDBFF && end_ - p_ >= 6 && p_[0] == '\\' && p_[1] == 'u') {
-              p_ += 2;
-              uint32_t lo = hex4();
-              cp = 0x10000 + ((cp - 0xD800) << 10) + (lo - 0xDC00);
-            }
-            put_utf8(out, cp);
-            break;
-          }
-          default: fail("bad escape");
-        }
-        run = p_;
+      if (c >= 0x80) {
+        utf8_sequence();
         continue;
       }
+      if (c < 0x20) fail("control character in string");
+      // c == '\\'
+      out.append(run, p_);
       ++p_;
+      if (p_ >= end_) fail("bad escape");
+      char e = *p_++;
+      switch (e) {
+        case '"': out.push_back('"'); break;
+        case '\\': out.push_back('\\'); break;
+        case '/': out.push_back('/'); break;
+        case 'b': out.push_back('\b'); break;
+        case 'f': out.push_back('\f'); break;
+        case 'n': out.push_back('\n'); break;
+        case 'r': out.push_back('\r'); break;
+        case 't': out.push_back('\t'); break;
+        case 'u': {
+          // A high surrogate directly followed by a low one is one code
+          // point; any other surrogate escape stands alone and becomes
+          // U+FFFD (encoding/json), and what followed it is read afresh.
+          uint32_t cp = hex4();
+          if (cp >= 0xD800 && cp <= 0xDBFF) {
+            const char* after = p_;
+            uint32_t lo = 0;
+            if (end_ - p_ >= 6 && p_[0] == '\\' && p_[1] == 'u') {
+              p_ += 2;
+              lo = hex4();
+            }
+            if (lo >= 0xDC00 && lo <= 0xDFFF) {
+              cp = 0x10000 + ((cp - 0xD800) << 10) + (lo - 0xDC00);
+            } else {
+              p_ = after;
+              cp = 0xFFFD;
+            }
+          } else if (cp >= 0xDC00 && cp <= 0xDFFF) {
+            cp = 0xFFFD;
+          }
+          put_utf8(out, cp);
+          break;
+        }
+        default: fail("bad escape");
+      }
+      run = p_;
     }
     fail("unterminated string");
   }
 
+  // RFC 8259 section 6: -? (0 | [1-9][0-9]*) (. [0-9]+)? ([eE] [+-]? [0-9]+)?
+  // Without fraction and exponent, and within int64, the value is an Int; any
+  // other number is the nearest double, and one that overflows is refused.
   Json number() {
     const char* start = p_;
+    auto digit = [&] { return p_ < end_ && *p_ >= '0' && *p_ <= '9'; };
+    bool neg = false;
+    if (p_ < end_ && *p_ == '-') { neg = true; ++p_; }
+    if (!digit()) fail(p_ == start ? "unexpected character" : "bad number");
+    uint64_t mag = 0;
+    bool fits = true;  // mag holds the digits so far
+    if (*p_ == '0') {
+      ++p_;
+    } else {
+      while (digit()) {
+        unsigned d = static_cast<unsigned>(*p_++ - '0');
+        if (mag > (UINT64_MAX - d) / 10) fits = false;
+        else mag = mag * 10 + d;
+      }
+    }
     bool is_float = false;
-    if (p_ < end_ && (*p_ == '-' || *p_ == '+')) ++p_;
-    while (p_ < end_) {
-      char c = *p_;
-      if (c >= '0' && c <= '9') { ++p_; continue; }
-      if (c == '.' || c == 'e' || c == 'E' || c == '-' || c == '+') { is_float = true; ++p_; continue; }
-      break;
+    if (p_ < end_ && *p_ == '.') {
+      is_float = true;
+      ++p_;
+      if (!digit()) fail("bad number");
+      while (digit()) ++p_;
     }
-    if (p_ == start) fail("unexpected character");
-    std::string tok(start, p_);
-    if (!is_float) {
-      errno = 0;
-      char* e = nullptr;
-      long long v = std::strtoll(tok.c_str(), &e, 10);
-      if (errno == 0 && e && *e == '\0') return Json(static_cast<int64_t>(v));
+    if (p_ < end_ && (*p_ == 'e' || *p_ == 'E')) {
+      is_float = true;
+      ++p_;
+      if (p_ < end_ && (*p_ == '+' || *p_ == '-')) ++p_;
+      if (!digit()) fail("bad number");
+      while (digit()) ++p_;
     }
-    char* e = nullptr;
-    double d = std::strtod(tok.c_str(), &e);
-    if (!e || *e != '\0') fail("bad number");
+    if (!is_float && fits) {
+      constexpr uint64_t kMax = static_cast<uint64_t>(std::numeric_limits<int64_t>::max());
+      if (!neg && mag <= kMax) return Json(static_cast<int64_t>(mag));
+      if (neg && mag <= kMax + 1) return Json(static_cast<int64_t>(0 - mag));
+    }
+    double d = 0.0;
+    auto r = std::from_chars(start, p_, d);
+    if (r.ec == std::errc::result_out_of_range) {
+      // Too large, or too small to tell from zero: strtod tells which.
+      d = std::strtod(std::string(start, p_).c_str(), nullptr);
+    } else if (r.ec != std::errc() || r.ptr != p_) {
+      fail("bad number");
+    }
+    if (!std::isfinite(d)) fail("number out of range");
     return Json(d);
   }
 };
@@ -326,10 +415,21 @@ bool Json::erase(std::string_view key) {
 
 void Json::push_back(Json v) { items_mut().push_back(std::move(v)); }
 
+namespace {
+// True, with the value, for a double that is integral and within int64.
+inline bool double_is_int64(double d, int64_t* out) {
+  if (!(d >= -9223372036854775808.0 && d < 9223372036854775808.0) || d != std::trunc(d)) return false;
+  *out = static_cast<int64_t>(d);
+  return true;
+}
+}  // namespace
+
 bool Json::operator==(const Json& o) const {
   if (is_number() && o.is_number()) {
-    if (t_ == Type::Int && o.t_ == Type::Int) return i_ == o.i_;
-    return as_double() == o.as_double();
+    if (t_ == o.t_) return t_ == Type::Int ? i_ == o.i_ : d_ == o.d_;
+    // Int against Double, exactly: through double, 2^53 + 1 equals 2^53.
+    int64_t as_i;
+    return t_ == Type::Int ? double_is_int64(o.d_, &as_i) && as_i == i_ : double_is_int64(d_, &as_i) && as_i == o.i_;
   }
   if (t_ != o.t_) return false;
   switch (t_) {
@@ -474,6 +574,10 @@ inline uint64_t fnv(uint64_t h, const void* data, size_t n) {
 }  // namespace
 
 uint64_t json_hash(const Json& j, uint64_t h, std::string_view skip_key) {
+  // Equal values hash equal: a Double that `==` an Int (1.0, which dump()
+  // writes as "1" and parse() reads back as an Int) hashes as that Int.
+  int64_t as_i;
+  if (j.type() == Json::Type::Double && double_is_int64(j.as_double(), &as_i)) return json_hash(Json(as_i), h);
   uint8_t tag = static_cast<uint8_t>(j.type());
   h = fnv(h, &tag, 1);
   switch (j.type()) {

@@ -5,6 +5,36 @@
 // document form in the store (so unknown fields, merge patches and the REST
 // adapter round-trip losslessly) and parse typed views (api/types.h) out of it
 // only where the scheduler needs them.
+//
+// What parse() accepts is RFC 8259 text in UTF-8, and nothing else
+// (tests/json_ref.py is the same contract in Python; tests/
+// test_json_conformance.py holds the parser to it):
+//   - one value, with only space, TAB, LF and CR around and between tokens;
+//     no byte-order mark, no comments, no trailing comma, no empty input;
+//   - literals `true`, `false`, `null` only (no NaN, Infinity);
+//   - numbers `-? (0 | [1-9][0-9]*) (. [0-9]+)? ([eE] [+-]? [0-9]+)?`: no
+//     leading `+`, no leading zeros, a digit on both sides of the point, no
+//     hex. Without fraction and exponent and within int64 the value is an
+//     Int; every other number is the nearest Double (so 2^63 is a Double),
+//     tiny numbers round to zero or a subnormal, and a number that overflows
+//     a double is refused rather than stored as infinity;
+//   - strings hold well-formed UTF-8 only (no overlong form, no encoded
+//     surrogate, nothing above U+10FFFF, no truncated sequence) and no raw
+//     byte below 0x20; the escapes are \" \\ \/ \b \f \n \r \t \uXXXX;
+//     \u0000 is kept; a \uD800-\uDBFF escape directly followed by a
+//     \uDC00-\uDFFF escape is one code point, any other surrogate escape
+//     becomes U+FFFD (encoding/json), so a stored string is always valid
+//     UTF-8;
+//   - a duplicate key keeps its first position and takes its last value
+//     (encoding/json);
+//   - a value may stand inside at most 256 arrays and objects: `[`x256 `1`
+//     `]`x256 parses, one more level is refused. parse_array_stream() counts
+//     the top-level array like parse() does.
+// Anything else throws JsonError. dump() writes compact text that parse()
+// accepts: Doubles with 17 significant digits (an integral one without a
+// point, so it reads back as an Int of the same value, and `==` and
+// json_hash() treat the two alike); a non-finite Double, which parse() never
+// produces, as null.
 #pragma once
 
 #include <cstdint>
@@ -91,7 +121,11 @@ class Json {
   bool as_bool(bool dflt = false) const { return t_ == Type::Bool ? i_ != 0 : dflt; }
   int64_t as_int(int64_t dflt = 0) const {
     if (t_ == Type::Int) return i_;
-    if (t_ == Type::Double) return static_cast<int64_t>(d_);
+    if (t_ == Type::Double) {  // toward zero, saturating; NaN is 0
+      if (d_ >= 9223372036854775808.0) return INT64_MAX;
+      if (d_ <= -9223372036854775808.0) return INT64_MIN;
+      return d_ == d_ ? static_cast<int64_t>(d_) : 0;
+    }
     return dflt;
   }
   double as_double(double dflt = 0.0) const {

@@ -79,6 +79,13 @@ Json json_arg(py::handle h) {
   return from_py(h);
 }
 
+// JSON text from Python: bytes as they are, str as UTF-8.
+std::string text_arg(py::handle h) {
+  if (py::isinstance<py::bytes>(h)) return h.cast<std::string>();
+  if (py::isinstance<py::str>(h)) return h.cast<std::string>();
+  throw py::type_error("JSON text must be bytes or str");
+}
+
 // ApiClient implemented in Python (remote kube-apiserver / HTTP store).
 class PyApiClient : public ApiClient {
  public:
@@ -269,6 +276,19 @@ PYBIND11_MODULE(_xsched, m) {
     return Registry::global().names();
   });
   m.def("json_roundtrip", [](const std::string& s) { return Json::parse(s).dump(); });
+  // The DOM itself, for the conformance tests: values, not only text. Text
+  // is bytes or str; an Int comes back as int, a Double as float.
+  m.def("json_parse", [](py::handle text) { return to_py(Json::parse(text_arg(text))); });
+  m.def("json_dump", [](py::handle obj) { return py::bytes(from_py(obj).dump()); });
+  m.def("json_hash", [](py::handle v) {
+    bool text = py::isinstance<py::str>(v) || py::isinstance<py::bytes>(v);
+    return json_hash(text ? Json::parse(text_arg(v)) : from_py(v));
+  });
+  m.def("json_parse_array_stream", [](py::handle text) {
+    py::list out;
+    Json::parse_array_stream(text_arg(text), [&](Json&& j) { out.append(to_py(j)); });
+    return out;
+  });
   // ---- live MI355X telemetry (libamd_smi) ----
   m.def("amdsmi_status", [] {
     auto& smi = telemetry::AmdSmi::get();

@@ -12,6 +12,7 @@ Usage:
     python -m flex_gpu_scheduler_amd.build_ext --tsan     # ThreadSanitizer stress driver
     python -m flex_gpu_scheduler_amd.build_ext --stress-count  # allocation-counting stress driver
     python -m flex_gpu_scheduler_amd.build_ext --gang-tests    # native gang-entry tests (--gang-tests-tsan)
+    python -m flex_gpu_scheduler_amd.build_ext --json-fuzz     # JSON/pod-decode driver under ASan+UBSan
 """
 from __future__ import annotations
 
@@ -199,6 +200,29 @@ def build_asan(verbose: bool = True) -> Path:
     return out
 
 
+def build_json_fuzz(verbose: bool = True) -> Path:
+    """Sanitizer driver for the JSON DOM and the pod decoder
+    (csrc/tests/json_fuzz_main.cc): common/ and api/ only, with
+    AddressSanitizer and UndefinedBehaviorSanitizer, every finding fatal (host only)."""
+    includes = [str(CSRC)]
+    flags = ["-fsanitize=address,undefined", "-fsanitize=float-cast-overflow", "-fno-sanitize-recover=all",
+             "-fno-omit-frame-pointer"]
+    srcs = sorted((CSRC / "common").glob("*.cc")) + sorted((CSRC / "api").glob("*.cc")) + \
+        [CSRC / "tests" / "json_fuzz_main.cc"]
+    objs = build_objects(srcs, BUILD / "json_fuzz", [*flags, "-g", "-O1"], includes)
+    out = BUILD / "xsched_json_fuzz"
+    newest = max(o.stat().st_mtime for o in objs)
+    if out.exists() and out.stat().st_mtime >= newest:
+        return out
+    cmd = ["g++", *flags, "-pthread", *[str(o) for o in objs], *LINK_LIBS, "-o", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"json fuzz link failed:\n{r.stderr[-8000:]}")
+    if verbose:
+        print(f"[build_ext] built {out.relative_to(ROOT)}")
+    return out
+
+
 def build_prof(verbose: bool = True, gprof: bool = True, debuginfo: bool = False) -> Path:
     """Native stress driver (no Python in the loop). With `gprof` it is built
     with -pg for a per-function CPU profile of the scheduling hot path;
@@ -291,6 +315,7 @@ def main(argv: list[str] | None = None) -> int:
     ap.add_argument("--hip", action="store_true")
     ap.add_argument("--tsan", action="store_true")
     ap.add_argument("--asan", action="store_true")
+    ap.add_argument("--json-fuzz", action="store_true", help="JSON/pod-decode driver under ASan+UBSan (host only)")
     ap.add_argument("--prof", action="store_true")
     ap.add_argument("--stress", action="store_true")
     ap.add_argument("--stress-g", action="store_true", help="stress driver with -g (sample_report --lines)")
@@ -307,6 +332,9 @@ def main(argv: list[str] | None = None) -> int:
         return 0
     if a.core_g:
         build_core_debuginfo()
+        return 0
+    if a.json_fuzz:
+        build_json_fuzz()
         return 0
     if a.tests:
         build_tests()
