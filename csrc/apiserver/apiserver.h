@@ -40,6 +40,12 @@
 #include "common/json.h"
 #include "store/store.h"
 
+typedef struct ssl_ctx_st SSL_CTX;
+
+namespace xsched::rest {
+class Wire;  // one HTTP/1.1 connection (rest/wire.h)
+}
+
 namespace xsched::apiserver {
 
 struct Options {
@@ -64,7 +70,7 @@ struct Requirement {
 std::vector<Requirement> parse_selector(std::string_view s);
 bool labels_match(const std::vector<Requirement>& reqs, const Json& obj);
 bool fields_match(const std::vector<Requirement>& reqs, const Json& obj);  // = / != on dotted paths
-// RFC 6902 JSON patch; throws std::invalid_argument (HTTP 422) on a bad op.
+// RFC 6902 JSON patch; a bad op throws the 422 "Invalid" ApiError (apiserver/api_error.h).
 Json apply_json_patch(const Json& doc, const Json& ops);
 
 class Server {
@@ -82,18 +88,20 @@ class Server {
   size_t connections() const;
 
   struct Request;
-  struct Conn;
+  struct Reply;
 
  private:
   void accept_loop();
   void serve(int fd);
   // Handles one request; false when the connection must close.
-  bool handle(Conn& c, Request& r);
-  void watch(Conn& c, const std::string& kind, const std::string& ns, Request& r);
+  bool handle(rest::Wire& c, Request& r);
+  // Fills in the reply to `r`; false when a watch has streamed its own.
+  bool answer(rest::Wire& c, Request& r, Reply& out);
+  void watch(rest::Wire& c, const std::string& kind, const std::string& ns, Request& r);
 
   std::shared_ptr<ObjectStore> store_;
   Options opts_;
-  void* tls_ctx_ = nullptr;  // SSL_CTX* when serving HTTPS
+  SSL_CTX* tls_ctx_ = nullptr;  // when serving HTTPS
   int listen_fd_ = -1;
   int port_ = 0;
   std::thread acceptor_;

@@ -8,13 +8,13 @@
 // no interpreter lock on the path (rest/kube.h).
 #pragma once
 
-#include <sys/types.h>
-
 #include <cstdint>
 #include <memory>
 #include <string>
 #include <string_view>
 #include <vector>
+
+#include "rest/wire.h"
 
 namespace xsched::rest {
 
@@ -50,9 +50,6 @@ class HttpConn {
  public:
   // Connects (and handshakes); throws std::runtime_error on failure.
   HttpConn(const Endpoint& ep, std::shared_ptr<TlsContext> tls, bool streaming = false);
-  ~HttpConn();
-  HttpConn(const HttpConn&) = delete;
-  HttpConn& operator=(const HttpConn&) = delete;
 
   // One request and its full response. Throws std::runtime_error on I/O
   // errors (the connection is then unusable).
@@ -69,31 +66,21 @@ class HttpConn {
   // The last roundtrip failed the way a keep-alive connection the server
   // closed while idle fails: EOF or a reset before any response byte, never
   // a receive timeout. Only then may a pooled request be sent again.
-  bool failed_stale() const { return (fail_ == Fail::kEof || fail_ == Fail::kReset) && rx_bytes_ == 0; }
+  bool failed_stale() const { return wire_.failed_stale(); }
   // Unblocks a reader blocked in next_line() (from another thread).
-  void shutdown();
+  void shutdown() { wire_.shutdown(); }
 
  private:
   void send_request(std::string_view method, std::string_view path, std::string_view body,
                     std::string_view content_type);
-  int read_head(bool* chunked, int64_t* content_length);
-  bool fill();  // reads more bytes into buf_; false on EOF/error
-  bool read_line_raw(std::string& out);  // one CRLF/LF-terminated line of the raw stream
-  bool read_exact(size_t n, std::string& out);
-  bool read_chunked_body(std::string& out);
+  int read_head(Framing* f);
   bool next_chunk();  // streaming: loads the next chunk's bytes into pending_
+  [[noreturn]] void fail(const std::string& what);  // not reusable; throws std::runtime_error
 
   Endpoint ep_;
   std::shared_ptr<TlsContext> tls_;
-  int fd_ = -1;
-  void* ssl_ = nullptr;  // SSL*
-  std::string buf_;      // received, not yet consumed
-  size_t pos_ = 0;
+  Wire wire_{Wire::Scratch::k16K};  // the socket, its TLS session, the read buffer, the failure record (rest/wire.h)
   bool reusable_ = true;
-  enum class Fail { kNone, kEof, kReset, kTimeout, kOther };
-  Fail fail_ = Fail::kNone;
-  size_t rx_bytes_ = 0;  // bytes received since the current request was sent
-  void note_io_failure(ssize_t n);
   // streaming state
   bool stream_chunked_ = false;
   int64_t stream_left_ = -1;  // Content-Length stream: bytes left (-1: until close)

@@ -13,6 +13,7 @@ Usage:
     python -m flex_gpu_scheduler_amd.build_ext --stress-count  # allocation-counting stress driver
     python -m flex_gpu_scheduler_amd.build_ext --gang-tests    # native gang-entry tests (--gang-tests-tsan)
     python -m flex_gpu_scheduler_amd.build_ext --json-fuzz     # JSON/pod-decode driver under ASan+UBSan
+    python -m flex_gpu_scheduler_amd.build_ext --wire-tests    # native HTTP wire tests (--wire-asan: under ASan+UBSan)
 """
 from __future__ import annotations
 
@@ -309,6 +310,27 @@ def build_gang_tests(verbose: bool = True, tsan: bool = False) -> Path:
     return out
 
 
+def build_wire_tests(verbose: bool = True, sanitize: bool = False) -> Path:
+    """Native tests of the HTTP/1.1 wire layer (csrc/tests/wire_tests.cc):
+    rest/wire.cc and OpenSSL only. `sanitize` builds with AddressSanitizer
+    and UndefinedBehaviorSanitizer, every finding fatal (host only)."""
+    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"] if sanitize else []
+    srcs = [CSRC / "rest" / "wire.cc", CSRC / "tests" / "wire_tests.cc"]
+    objs = build_objects(srcs, BUILD / ("wire_asan" if sanitize else "core"), [*flags, "-g", "-O1"] if sanitize else [],
+                         [str(CSRC)])
+    out = BUILD / ("xsched_wire_tests_asan" if sanitize else "xsched_wire_tests")
+    newest = max(o.stat().st_mtime for o in objs)
+    if out.exists() and out.stat().st_mtime >= newest:
+        return out
+    cmd = ["g++", *flags, "-pthread", *[str(o) for o in objs], *LINK_LIBS, "-o", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"wire tests link failed:\n{r.stderr[-8000:]}")
+    if verbose:
+        print(f"[build_ext] built {out.relative_to(ROOT)}")
+    return out
+
+
 def main(argv: list[str] | None = None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--core", action="store_true")
@@ -326,7 +348,12 @@ def main(argv: list[str] | None = None) -> int:
     ap.add_argument("--core-g", action="store_true", help="the extension with -g into dbg/ (sampling runs)")
     ap.add_argument("--gang-tests", action="store_true", help="native tests of the lister's gang entries")
     ap.add_argument("--gang-tests-tsan", action="store_true", help="the same under ThreadSanitizer (host only)")
+    ap.add_argument("--wire-tests", action="store_true", help="native tests of the HTTP/1.1 wire layer")
+    ap.add_argument("--wire-asan", action="store_true", help="the same under ASan+UBSan (host only)")
     a = ap.parse_args(argv)
+    if a.wire_tests or a.wire_asan:
+        build_wire_tests(sanitize=a.wire_asan)
+        return 0
     if a.gang_tests or a.gang_tests_tsan:
         build_gang_tests(tsan=a.gang_tests_tsan)
         return 0

@@ -300,6 +300,88 @@ def test_retried_binding_conflict_on_same_node_is_success():
         srv.close()
 
 
+class _ChunkServer:
+    """A raw-socket API server that answers every request of its first
+    connection with a chunked 201 whose first chunk-size line is `size_line`,
+    then keeps that connection open and silent; later connections get a plain
+    201. `connections` counts the accepts."""
+
+    def __init__(self, size_line):
+        import socket
+        import threading
+
+        self.size_line = size_line
+        self.connections = 0
+        self.lsock = socket.create_server(("127.0.0.1", 0))
+        self.port = self.lsock.getsockname()[1]
+        self.socks = []
+        threading.Thread(target=self._accept, daemon=True).start()
+
+    def _accept(self):
+        import threading
+
+        while True:
+            try:
+                s, _ = self.lsock.accept()
+            except OSError:
+                return
+            self.connections += 1
+            self.socks.append(s)
+            threading.Thread(target=self._serve, args=(s, self.connections == 1), daemon=True).start()
+
+    def _serve(self, s, bad):
+        buf = b""
+        try:
+            while True:
+                while b"\r\n\r\n" not in buf:
+                    data = s.recv(65536)
+                    if not data:
+                        return
+                    buf += data
+                head, _, buf = buf.partition(b"\r\n\r\n")
+                need = next((int(ln.split(b":")[1]) for ln in head.split(b"\r\n")
+                             if ln.lower().startswith(b"content-length:")), 0)
+                while len(buf) < need:
+                    buf += s.recv(65536)
+                buf = buf[need:]
+                if bad:
+                    s.sendall(b"HTTP/1.1 201 Created\r\nContent-Type: application/json\r\n"
+                              b"Transfer-Encoding: chunked\r\n\r\n" + self.size_line + b"\r\n\r\n")
+                else:
+                    body = b'{"kind":"Status","status":"Success"}'
+                    s.sendall(b"HTTP/1.1 201 Created\r\nContent-Type: application/json\r\nContent-Length: " +
+                              str(len(body)).encode() + b"\r\n\r\n" + body)
+        except OSError:
+            pass
+
+    def client(self):
+        return native().RestApiClient(native().RestEndpoint("127.0.0.1", self.port))
+
+    def close(self):
+        self.lsock.close()
+        for s in self.socks:
+            s.close()
+
+
+@pytest.mark.parametrize("size_line", [b"zz", b"f" * 16], ids=["not-hex", "sixteen-digits"])
+def test_malformed_chunk_size_is_an_error_and_ends_the_connection(size_line):
+    """A response whose chunk-size line is no size of 1-15 hex digits fails
+    the request at once (the client used to read `zz` as 0, an empty
+    successful body, and a 16-digit size as bytes to wait for until the
+    receive timeout, 30 s here), and its connection is not used again."""
+    srv = _ChunkServer(size_line)
+    try:
+        c = srv.client()
+        t0 = time.time()
+        with pytest.raises(Exception, match="chunk"):
+            c.bind_json(_pod("a"), "n0")
+        assert time.time() - t0 < 5.0
+        c.bind_json(_pod("b"), "n0")  # a fresh connection, answered well
+        assert srv.connections == 2
+    finally:
+        srv.close()
+
+
 @pytest.mark.skipif(shutil.which("openssl") is None, reason="openssl CLI not available")
 @pytest.mark.parametrize("native_http", [True, False], ids=["native-http", "python-http"])
 def test_mtls_server_requires_a_client_certificate(store, pki, native_http):
