@@ -241,16 +241,9 @@ struct Selectors {
   }
 };
 
-// Throws std::invalid_argument for a malformed selector and, with
-// `check_field_ops`, for a field requirement other than = and != (a watch
-// meets that one at its first object instead).
-Selectors parse_selectors(const Request& r, bool check_field_ops) {
-  Selectors s{parse_selector(r.q("labelSelector")), parse_selector(r.q("fieldSelector"))};
-  if (check_field_ops)
-    for (const auto& q : s.fields)
-      if (q.op != Requirement::Eq && q.op != Requirement::Ne)
-        throw std::invalid_argument("field selector supports only = and !=");
-  return s;
+// Throws std::invalid_argument for a malformed selector.
+Selectors parse_selectors(const Request& r) {
+  return {parse_selector(r.q("labelSelector")), parse_field_selector(r.q("fieldSelector"))};
 }
 
 // ---------------------------------------------------------------- routes --
@@ -343,7 +336,7 @@ Reply get_one(ObjectStore& store, const Route& rt) {
 Reply list_many(ObjectStore& store, const Route& rt, const Request& r) {
   Selectors sel;
   try {
-    sel = parse_selectors(r, /*check_field_ops=*/true);
+    sel = parse_selectors(r);
   } catch (const std::invalid_argument& e) {
     throw ApiError(400, "BadRequest", e.what());
   }
@@ -413,7 +406,13 @@ Reply patch(ObjectStore& store, const Route& rt, const Request& r) {
   if (ct == "application/json-patch+json") {
     JsonPtr cur = store.get(*rt.kind, rt.ns, rt.name);
     if (!cur) throw ApiError(404, "NotFound", *rt.kind + " \"" + rt.name + "\" not found");
-    return json_reply(200, *store.update(*rt.kind, apply_json_patch(*cur, body), true));
+    Json next = apply_json_patch(*cur, body);
+    // What is stored under this name stays an object of this name: the store would look the new one up.
+    if (!next.is_object()) throw ApiError(422, "Invalid", "the patched " + rt.rp->kind + " is not a JSON object");
+    const Json& md = next["metadata"];
+    if (md["name"] != (*cur)["metadata"]["name"] || md["namespace"] != (*cur)["metadata"]["namespace"])
+      throw ApiError(422, "Invalid", "metadata.name and metadata.namespace: field is immutable");
+    return json_reply(200, *store.update(*rt.kind, std::move(next), true));
   }
   if (ct != "application/merge-patch+json" && ct != "application/strategic-merge-patch+json" &&
       ct != "application/apply-patch+yaml" && ct != "application/json")
@@ -639,7 +638,7 @@ void Server::watch(Wire& c, const std::string& kind, const std::string& ns, Requ
   const rest::ResourcePath& rp = rest::resource_path(kind);
   Selectors sel;
   try {
-    sel = parse_selectors(r, /*check_field_ops=*/false);
+    sel = parse_selectors(r);
   } catch (const std::invalid_argument& e) {
     respond(c, status_reply(400, "BadRequest", e.what()), false);
     return;

@@ -59,18 +59,22 @@ struct Options {
   std::string tls_cert_file, tls_key_file, client_ca_file;
 };
 
-// Label / field selector requirement (k8s.io/apimachinery labels + fields
-// string syntax: a=b, a==b, a!=b, a in (x,y), a notin (x), a, !a).
+// Label / field selector requirement (the string syntax of k8s.io/apimachinery
+// labels and fields; tests/selector_ref.py writes the grammar out).
 struct Requirement {
-  enum Op { Eq, Ne, In, NotIn, Exists, NotExists } op = Eq;
+  enum Op { Eq, Ne, In, NotIn, Exists, NotExists, Gt, Lt } op = Eq;
   std::string key;
-  std::vector<std::string> values;
+  std::vector<std::string> values;  // sorted, each once
 };
-// Throws std::invalid_argument on a malformed selector.
+// Both throw std::invalid_argument on a malformed selector.
+// a=b, a==b, a!=b, a>1, a<1, a in (x,y), a notin (x), a, !a; keys and values validated.
 std::vector<Requirement> parse_selector(std::string_view s);
+// path=value, path==value, path!=value; nothing trimmed; \\ \, \= in a value.
+std::vector<Requirement> parse_field_selector(std::string_view s);
 bool labels_match(const std::vector<Requirement>& reqs, const Json& obj);
 bool fields_match(const std::vector<Requirement>& reqs, const Json& obj);  // = / != on dotted paths
-// RFC 6902 JSON patch; a bad op throws the 422 "Invalid" ApiError (apiserver/api_error.h).
+// RFC 6902 JSON patch, all or nothing (tests/json_patch_ref.py); a bad op
+// throws the 422 "Invalid" ApiError (apiserver/api_error.h).
 Json apply_json_patch(const Json& doc, const Json& ops);
 
 class Server {

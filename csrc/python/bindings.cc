@@ -366,6 +366,19 @@ PYBIND11_MODULE(_xsched, m) {
   m.def("apply_json_patch", [](py::handle doc, py::handle ops) {
     return to_py(apiserver::apply_json_patch(json_arg(doc), json_arg(ops)));
   });
+  // The API server's selectors without HTTP; a malformed one is a ValueError.
+  m.def("parse_selector", [](const std::string& s) {
+    static const char* const kOps[] = {"=", "!=", "in", "notin", "exists", "!exists", ">", "<"};
+    py::list out;
+    for (const auto& r : apiserver::parse_selector(s)) out.append(py::make_tuple(r.key, kOps[r.op], r.values));
+    return out;
+  });
+  m.def("labels_match", [](const std::string& selector, py::handle obj) {
+    return apiserver::labels_match(apiserver::parse_selector(selector), json_arg(obj));
+  });
+  m.def("fields_match", [](const std::string& selector, py::handle obj) {
+    return apiserver::fields_match(apiserver::parse_field_selector(selector), json_arg(obj));
+  });
 
   // ---- native logging (common/log.h) ----
   m.def("set_log_verbosity", &xsched::log::set_verbosity, py::arg("v"));

@@ -13,6 +13,7 @@ Usage:
     python -m flex_gpu_scheduler_amd.build_ext --stress-count  # allocation-counting stress driver
     python -m flex_gpu_scheduler_amd.build_ext --gang-tests    # native gang-entry tests (--gang-tests-tsan)
     python -m flex_gpu_scheduler_amd.build_ext --json-fuzz     # JSON/pod-decode driver under ASan+UBSan
+    python -m flex_gpu_scheduler_amd.build_ext --patch-fuzz    # JSON patch / selector driver under ASan+UBSan
     python -m flex_gpu_scheduler_amd.build_ext --wire-tests    # native HTTP wire tests (--wire-asan: under ASan+UBSan)
 """
 from __future__ import annotations
@@ -224,6 +225,29 @@ def build_json_fuzz(verbose: bool = True) -> Path:
     return out
 
 
+def build_patch_fuzz(verbose: bool = True) -> Path:
+    """Sanitizer driver for the JSON patch and the selectors
+    (csrc/tests/patch_selector_main.cc): common/ and the two apiserver/ files
+    only, with the flags of build_json_fuzz (host only)."""
+    includes = [str(CSRC)]
+    flags = ["-fsanitize=address,undefined", "-fsanitize=float-cast-overflow", "-fno-sanitize-recover=all",
+             "-fno-omit-frame-pointer"]
+    srcs = sorted((CSRC / "common").glob("*.cc")) + \
+        [CSRC / "apiserver" / "json_patch.cc", CSRC / "apiserver" / "selectors.cc", CSRC / "tests" / "patch_selector_main.cc"]
+    objs = build_objects(srcs, BUILD / "json_fuzz", [*flags, "-g", "-O1"], includes)  # common/ shared with build_json_fuzz
+    out = BUILD / "xsched_patch_selector_fuzz"
+    newest = max(o.stat().st_mtime for o in objs)
+    if out.exists() and out.stat().st_mtime >= newest:
+        return out
+    cmd = ["g++", *flags, "-pthread", *[str(o) for o in objs], "-o", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"patch fuzz link failed:\n{r.stderr[-8000:]}")
+    if verbose:
+        print(f"[build_ext] built {out.relative_to(ROOT)}")
+    return out
+
+
 def build_prof(verbose: bool = True, gprof: bool = True, debuginfo: bool = False) -> Path:
     """Native stress driver (no Python in the loop). With `gprof` it is built
     with -pg for a per-function CPU profile of the scheduling hot path;
@@ -338,6 +362,7 @@ def main(argv: list[str] | None = None) -> int:
     ap.add_argument("--tsan", action="store_true")
     ap.add_argument("--asan", action="store_true")
     ap.add_argument("--json-fuzz", action="store_true", help="JSON/pod-decode driver under ASan+UBSan (host only)")
+    ap.add_argument("--patch-fuzz", action="store_true", help="JSON patch / selector driver under ASan+UBSan (host only)")
     ap.add_argument("--prof", action="store_true")
     ap.add_argument("--stress", action="store_true")
     ap.add_argument("--stress-g", action="store_true", help="stress driver with -g (sample_report --lines)")
@@ -362,6 +387,9 @@ def main(argv: list[str] | None = None) -> int:
         return 0
     if a.json_fuzz:
         build_json_fuzz()
+        return 0
+    if a.patch_fuzz:
+        build_patch_fuzz()
         return 0
     if a.tests:
         build_tests()

@@ -32,6 +32,7 @@ every writer in this framework sends merge patches.
 from __future__ import annotations
 
 import json
+import re
 import threading
 import time
 from http.server import BaseHTTPRequestHandler, ThreadingHTTPServer
@@ -57,68 +58,125 @@ class ApiError(Exception):
         self.code, self.reason, self.message = code, reason, message
 
 
-def apply_json_patch(doc: Any, ops: list) -> Any:
-    """RFC 6902 JSON patch (add/remove/replace/move/copy/test)."""
+_PATCH_INDEX = re.compile(r"0|[1-9][0-9]*", re.ASCII)
+_PATCH_BAD_TILDE = re.compile(r"~(?![01])")
+
+
+def _json_equal(a: Any, b: Any) -> bool:
+    """RFC 6902 section 4.6: numbers by value, a bool is no number."""
+    if isinstance(a, bool) or isinstance(b, bool):
+        return isinstance(a, bool) and isinstance(b, bool) and a == b
+    if isinstance(a, (int, float)) and isinstance(b, (int, float)):
+        return a == b
+    if type(a) is not type(b):
+        return False
+    if isinstance(a, list):
+        return len(a) == len(b) and all(map(_json_equal, a, b))
+    if isinstance(a, dict):
+        return a.keys() == b.keys() and all(_json_equal(v, b[k]) for k, v in a.items())
+    return a == b
+
+
+def apply_json_patch(doc: Any, ops: Any) -> Any:
+    """RFC 6902 JSON patch (add/remove/replace/move/copy/test), all or
+    nothing: the patched copy, or the 422 ApiError. tests/json_patch_ref.py
+    writes the rules out (strict array indexes and `~` escapes, every
+    operation's shape checked before the document is touched, no remove of
+    the whole document); tests/test_json_patch_conformance.py holds this
+    function and its native twin (csrc/apiserver/json_patch.cc) to them."""
     import copy
 
-    def split(ptr: str) -> list[str]:
+    class Refused(Exception):
+        pass
+
+    def split(ptr: Any, what: str) -> list[str]:
+        if not isinstance(ptr, str):
+            raise Refused(f"{what} must be a string")
         if ptr == "":
             return []
-        if not ptr.startswith("/"):
-            raise ApiError(422, "Invalid", f"bad JSON pointer {ptr!r}")
+        if not ptr.startswith("/") or _PATCH_BAD_TILDE.search(ptr):
+            raise Refused(f"bad JSON pointer {ptr!r}")
         return [p.replace("~1", "/").replace("~0", "~") for p in ptr[1:].split("/")]
 
-    def parent(d, parts):
-        for p in parts[:-1]:
-            d = d[int(p)] if isinstance(d, list) else d[p]
+    def index(token: str, size: int, putting: bool = False) -> int:
+        if putting and token == "-":
+            return size
+        if not _PATCH_INDEX.fullmatch(token) or len(token) > 9:
+            raise Refused(f"bad array index {token!r}")
+        if int(token) > size or (int(token) == size and not putting):
+            raise Refused(f"array index {token} out of range")
+        return int(token)
+
+    def walk(d, parts):
+        for p in parts:
+            if isinstance(d, list):
+                d = d[index(p, len(d))]
+            elif isinstance(d, dict) and p in d:
+                d = d[p]
+            else:
+                raise Refused(f"nothing at {p!r}")
         return d
 
-    doc = copy.deepcopy(doc)
-    for op in ops:
-        kind, parts = op.get("op"), split(op.get("path", ""))
-        try:
-            if kind == "test":
-                cur = doc
-                for p in parts:
-                    cur = cur[int(p)] if isinstance(cur, list) else cur[p]
-                if cur != op.get("value"):
-                    raise ApiError(422, "Invalid", f"test failed at {op.get('path')}")
-                continue
-            if kind in ("move", "copy"):
-                src = split(op["from"])
-                sp = parent(doc, src)
-                val = sp[int(src[-1])] if isinstance(sp, list) else sp[src[-1]]
-                if kind == "move":
-                    if isinstance(sp, list):
-                        sp.pop(int(src[-1]))
-                    else:
-                        del sp[src[-1]]
-                kind, op = "add", {"value": copy.deepcopy(val)}
-            if not parts:
-                doc = op.get("value")
-                continue
-            par, last = parent(doc, parts), parts[-1]
+    def add(d, parts, value):
+        if not parts:
+            return value
+        par = walk(d, parts[:-1])
+        if isinstance(par, list):
+            par.insert(index(parts[-1], len(par), putting=True), value)
+        elif isinstance(par, dict):
+            par[parts[-1]] = value
+        else:
+            raise Refused("the parent of the target is a scalar")
+        return d
+
+    def remove(d, parts):
+        par = walk(d, parts[:-1])
+        walk(par, parts[-1:])  # must exist
+        return par.pop(index(parts[-1], len(par)) if isinstance(par, list) else parts[-1])
+
+    if not isinstance(ops, list):
+        raise ApiError(422, "Invalid", "json patch body must be an array")
+    op = None
+    try:
+        steps = []
+        for op in ops:  # every operation's shape, before the document is touched
+            if not isinstance(op, dict):
+                raise Refused("an operation is an object")
+            kind = op.get("op")
+            if not isinstance(kind, str) or kind not in ("add", "remove", "replace", "move", "copy", "test"):
+                raise Refused(f"unknown json-patch op {kind!r}")
+            if kind in ("add", "replace", "test") and "value" not in op:
+                raise Refused(f"{kind} needs a value")
+            src = split(op.get("from"), "from") if kind in ("move", "copy") else None
+            steps.append((op, kind, split(op.get("path"), "path"), src))
+        doc = copy.deepcopy(doc)
+        for op, kind, parts, src in steps:
             if kind == "add":
-                if isinstance(par, list):
-                    par.insert(len(par) if last == "-" else int(last), op["value"])
-                else:
-                    par[last] = op["value"]
+                doc = add(doc, parts, copy.deepcopy(op["value"]))
             elif kind == "remove":
-                if isinstance(par, list):
-                    par.pop(int(last))
-                else:
-                    del par[last]
+                if not parts:
+                    raise Refused("cannot remove the whole document")
+                remove(doc, parts)
             elif kind == "replace":
-                if isinstance(par, list):
-                    par[int(last)] = op["value"]
+                walk(doc, parts)  # must exist
+                if parts:
+                    par = walk(doc, parts[:-1])
+                    par[index(parts[-1], len(par)) if isinstance(par, list) else parts[-1]] = copy.deepcopy(op["value"])
                 else:
-                    if last not in par:
-                        raise KeyError(last)
-                    par[last] = op["value"]
-            else:
-                raise ApiError(422, "Invalid", f"unknown json-patch op {kind!r}")
-        except (KeyError, IndexError, ValueError, TypeError) as e:
-            raise ApiError(422, "Invalid", f"json patch {op}: {e}") from None
+                    doc = copy.deepcopy(op["value"])
+            elif kind == "move":
+                if len(src) < len(parts) and parts[:len(src)] == src:
+                    raise Refused("cannot move a value into one of its own children")
+                if src == parts:
+                    walk(doc, src)  # must exist
+                else:
+                    doc = add(doc, parts, remove(doc, src))
+            elif kind == "copy":
+                doc = add(doc, parts, copy.deepcopy(walk(doc, src)))
+            elif not _json_equal(walk(doc, parts), op["value"]):
+                raise Refused("test failed")
+    except Refused as e:
+        raise ApiError(422, "Invalid", f"json patch {op}: {e}") from None
     return doc
 
 
@@ -341,7 +399,10 @@ class _Handler(BaseHTTPRequestHandler):
             if obj is None:
                 raise ApiError(404, "NotFound", f'{res.kind_plural} "{name}" not found')
             return self._send(200, obj)
-        match = combine(label_matcher(q.get("labelSelector")), field_matcher(q.get("fieldSelector")))
+        try:
+            match = combine(label_matcher(q.get("labelSelector")), field_matcher(q.get("fieldSelector")))
+        except ValueError as e:
+            raise ApiError(400, "BadRequest", str(e)) from None
         if q.get("watch") in ("true", "1"):
             return self._watch(res, ns, q, match)
         items_json, rv = store.list_json(res.kind_plural, ns)
@@ -395,7 +456,13 @@ class _Handler(BaseHTTPRequestHandler):
             cur = store.get(res.kind_plural, ns, name)
             if cur is None:
                 raise ApiError(404, "NotFound", f'{res.kind_plural} "{name}" not found')
-            new = apply_json_patch(cur, body or [])
+            new = apply_json_patch(cur, body)
+            # What is stored under this name stays an object of this name: the store would look the new one up.
+            if not isinstance(new, dict):
+                raise ApiError(422, "Invalid", f"the patched {res.kind} is not a JSON object")
+            md, was = new.get("metadata"), cur.get("metadata") or {}
+            if not isinstance(md, dict) or any(md.get(k) != was.get(k) for k in ("name", "namespace")):
+                raise ApiError(422, "Invalid", "metadata.name and metadata.namespace: field is immutable")
             return self._send(200, store.update(res.kind_plural, new, True))
         if ctype not in ("application/merge-patch+json", "application/strategic-merge-patch+json",
                          "application/apply-patch+yaml", "application/json"):
