@@ -669,6 +669,14 @@ Status Framework::run_score(CycleState& s, const Pod& p, const NodeList& nodes,
   return {};
 }
 
+bool Framework::run_prepare_assumed(CycleState& s, Pod& copy, const NodeInfo& ni) {
+  auto it = chain_.find(kReserve);
+  if (it == chain_.end()) return false;
+  bool prepared = false;
+  for (const auto& pl : it->second) prepared |= pl->prepare_assumed(s, copy, ni);
+  return prepared;
+}
+
 Status Framework::run_reserve(CycleState& s, const PodPtr& p, const std::string& node) {
   auto it = chain_.find(kReserve);
   if (it == chain_.end()) return {};

@@ -132,6 +132,9 @@ class Framework {
   // Per scorer (scorer order): raw Score node-local for `p`? Empty if none is.
   std::vector<char> local_scorers(const Pod& p, const Snapshot& s) const;
   void local_scorers(const Pod& p, const Snapshot& s, std::vector<char>& out) const;  // into a reused buffer
+  // Plugin::prepare_assumed of the Reserve plugins, in Reserve order, on the
+  // cycle's private copy of the pod; true when one of them prepared it.
+  bool run_prepare_assumed(CycleState& s, Pod& copy, const NodeInfo& ni);
   Status run_reserve(CycleState& s, const PodPtr& p, const std::string& node);
   void run_unreserve(CycleState& s, const PodPtr& p, const std::string& node);
   // Returns Success, an unschedulable/error status, or Wait (then `on_done`

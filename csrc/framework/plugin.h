@@ -167,6 +167,13 @@ class Plugin {
   virtual bool has_normalize_score() const { return false; }
   virtual Status normalize_score(CycleState& s, const Pod& p, std::vector<NodeScore>& scores) { return {}; }
   // Reserve
+  // Optional, before the pod is assumed: `copy` is the cycle's private, not
+  // yet published copy of the pod (node_name set), `ni` the snapshot's version
+  // of that node. A plugin whose Reserve only derives annotations and a GPU
+  // assignment from the snapshot may set them here, with no lock, and answer
+  // its later reserve() from the cycle state; the cache then accounts the pod
+  // once, as placed. False: nothing was changed, reserve() does the work.
+  virtual bool prepare_assumed(CycleState& s, Pod& copy, const NodeInfo& ni) { return false; }
   virtual Status reserve(CycleState& s, const PodPtr& p, const std::string& node) { return {}; }
   virtual void unreserve(CycleState& s, const PodPtr& p, const std::string& node) {}
   // Permit: (status, timeout_us) — Wait requests a timeout.

@@ -27,10 +27,10 @@
 //     fail after Filter passed) and k > 1 GPUs are supported.
 #include <algorithm>
 #include <cstdint>
-#include <cstdio>
 #include <string>
 
 #include "common/log.h"
+#include "common/strings.h"
 #include "framework/plugin.h"
 #include "scheduler/cache.h"
 
@@ -172,38 +172,13 @@ void place(const GpuLedger& L, const Demand& d, Placement& pl) {
   }
 }
 
-// Both write into `s` (cleared first, its buffer kept).
-void append_int(std::string& s, int v) {
-  char buf[16];
-  int n = std::snprintf(buf, sizeof buf, "%d", v);
-  s.append(buf, static_cast<size_t>(n));
-}
-
-void join_ints(const std::vector<int>& v, std::string& s) {
-  s.clear();
-  for (size_t i = 0; i < v.size(); ++i) {
-    if (i) s += ',';
-    append_int(s, v[i]);
-  }
-}
-
-void join_parts(const std::vector<std::pair<int, int>>& v, std::string& s) {
-  s.clear();
-  for (size_t i = 0; i < v.size(); ++i) {
-    if (i) s += ',';
-    append_int(s, v[i].first);
-    s += ':';
-    append_int(s, v[i].second);
-  }
-}
-
-std::string join_ints(const std::vector<int>& v) {
+std::string joined_ints(const std::vector<int>& v) {
   std::string s;
   join_ints(v, s);
   return s;
 }
 
-std::string join_parts(const std::vector<std::pair<int, int>>& v) {
+std::string joined_parts(const std::vector<std::pair<int, int>>& v) {
   std::string s;
   join_parts(v, s);
   return s;
@@ -214,6 +189,9 @@ std::string join_parts(const std::vector<std::pair<int, int>>& v) {
 // cycle.
 struct AssignmentState : StateData {
   std::string index, partitions;  // partitions: empty for whole-GPU / HBM pods
+  // The cycle's private copy that prepare_assumed placed (its node_name is
+  // the node it was placed on); null when Reserve has to place.
+  const Pod* prepared = nullptr;
   Json annotations(const GpuNames& gn) const {
     Json a = Json::object();
     a.set(gn.index_annotation, Json(index));
@@ -330,38 +308,71 @@ class FlexGPU : public Plugin {
     return {};
   }
 
+  // Computes the placement on the snapshot's node into the thread's scratch
+  // Placement and fills the cycle's AssignmentState; null when nothing fits.
+  // Scheduling thread (per thread, so a debug cycle on another thread does
+  // not share the scratch).
+  std::shared_ptr<AssignmentState> assign(CycleState& s, const Pod& p, const NodeInfo& ni, Placement*& out) {
+    thread_local Placement pl;
+    place(ni.gpu, p.gpu_demand, pl);
+    if (!pl.ok()) return nullptr;
+    XS_LOGV(6, "assigned gpu indexes").kv("pod", p.key()).kv("node", ni.name()).kv("indexes", joined_ints(pl.gpus))
+        .kv("partitions", joined_parts(pl.parts));
+    auto st = s.reuse<AssignmentState>(kFlexGPUStateKey);
+    join_ints(pl.gpus, st->index);
+    join_parts(pl.parts, st->partitions);  // empty for whole-GPU / HBM pods
+    st->prepared = nullptr;
+    out = &pl;
+    return st;
+  }
+
+  // Writes the placement onto `cp`: the annotations Bind will send and the
+  // GPU assignment they parse to.
+  void annotate(Pod& cp, const AssignmentState& st, const Placement& pl) const {
+    const GpuNames& gn = gn_;
+    StrMap& am = cp.meta.annotations.mut();
+    am.reserve(am.size() + 2);  // one growth for the (at most) two entries
+    auto put = [&](const std::string& k, const std::string& v) {
+      for (auto& a : am)
+        if (a.first == k) {
+          a.second = v;
+          return;
+        }
+      am.emplace_back(k, v);
+    };
+    put(gn.index_annotation, st.index);
+    if (!st.partitions.empty()) put(gn.partition_annotation, st.partitions);
+    cp.set_gpu_assignment(pl.gpus, pl.parts, gn);  // what the annotations just written parse to
+  }
+
+  // The usual case of Reserve, done before the pod enters the cache: the
+  // placement depends on the snapshot's node alone, so it goes onto the
+  // cycle's private copy with no lock, and assume_pod accounts the pod once
+  // with its GPUs. Every failure is left to reserve(), which reports it.
+  bool prepare_assumed(CycleState& s, Pod& cp, const NodeInfo& ni) override {
+    const Demand& d = cp.gpu_demand;
+    if (d.kind == Demand::None || d.kind == Demand::Conflict) return false;
+    Placement* pl = nullptr;
+    auto st = assign(s, cp, ni, pl);
+    if (!st) return false;
+    annotate(cp, *st, *pl);
+    st->prepared = &cp;
+    s.write(kFlexGPUStateKey, st);
+    return true;
+  }
+
   Status reserve(CycleState& s, const PodPtr& p, const std::string& node) override {
     const Demand& d = p->gpu_demand;
     if (d.kind == Demand::None) return {};
     if (d.kind == Demand::Conflict) return Status::unresolvable("pod conflict resources");
+    if (auto* done = s.read_as<AssignmentState>(kFlexGPUStateKey))
+      if (done->prepared == p.get() && p->node_name == node) return {};  // prepare_assumed placed it
     NodeInfoPtr ni = h_.snapshot ? h_.snapshot->get(node) : nullptr;
     if (!ni) return Status::error("getting node \"" + node + "\" from Snapshot");
-    // Reserve runs on a scheduling thread; per thread, so a debug cycle on
-    // another thread does not share the scratch.
-    thread_local Placement pl;
-    place(ni->gpu, d, pl);
-    if (!pl.ok()) return Status::unschedulable("allocate index fail");
-    XS_LOGV(6, "assigned gpu indexes").kv("pod", p->key()).kv("node", node).kv("indexes", join_ints(pl.gpus))
-        .kv("partitions", join_parts(pl.parts));
-    const GpuNames& gn = gn_;
-    auto st = s.reuse<AssignmentState>(kFlexGPUStateKey);
-    join_ints(pl.gpus, st->index);
-    join_parts(pl.parts, st->partitions);  // empty for whole-GPU / HBM pods
-    h_.cache->annotate_assumed_pod(p->uid(), [&](Pod& cp) {
-      StrMap& am = cp.meta.annotations.mut();
-      am.reserve(am.size() + 2);  // one growth for the (at most) two entries
-      auto put = [&](const std::string& k, const std::string& v) {
-        for (auto& a : am)
-          if (a.first == k) {
-            a.second = v;
-            return;
-          }
-        am.emplace_back(k, v);
-      };
-      put(gn.index_annotation, st->index);
-      if (!st->partitions.empty()) put(gn.partition_annotation, st->partitions);
-      cp.set_gpu_assignment(pl.gpus, pl.parts, gn);  // what the annotations just written parse to
-    }, /*recompute=*/false);
+    Placement* pl = nullptr;
+    auto st = assign(s, *p, *ni, pl);
+    if (!st) return Status::unschedulable("allocate index fail");
+    h_.cache->annotate_assumed_pod(p->uid(), [&](Pod& cp) { annotate(cp, *st, *pl); }, /*recompute=*/false);
     s.write(kFlexGPUStateKey, st);
     return {};
   }

@@ -335,7 +335,7 @@ int64_t SchedulingQueue::scheduling_cycle() const {
   return scheduling_cycle_;
 }
 
-QueuedPodInfoPtr SchedulingQueue::pop(int timeout_ms) {
+QueuedPodInfoPtr SchedulingQueue::pop(int timeout_ms, int64_t* cycle) {
   std::unique_lock<AdaptiveMutex> lk(mu_);
   auto ready = [&] { return closed_ || !active_.empty(); };
   if (timeout_ms < 0)
@@ -347,6 +347,7 @@ QueuedPodInfoPtr SchedulingQueue::pop(int timeout_ms) {
   in_flight_.acquire(q->pod->uid()).first->second = kNoMark;
   q->attempts++;
   scheduling_cycle_++;
+  if (cycle) *cycle = scheduling_cycle_;
   return q;
 }
 

@@ -134,7 +134,9 @@ class SchedulingQueue {
   size_t in_flight() const;
   int64_t scheduling_cycle() const;
   // Blocks until a pod is available or the queue is closed (nullptr).
-  QueuedPodInfoPtr pop(int timeout_ms = -1);
+  // `cycle` (optional) receives the scheduling cycle number this pop started:
+  // what scheduling_cycle() returns until the next pop, without a second lock.
+  QueuedPodInfoPtr pop(int timeout_ms = -1, int64_t* cycle = nullptr);
   void update(const PodPtr& old_p, const PodPtr& new_p);
   void remove(const Pod& p);
   void assigned_pod_added(const Pod& p);

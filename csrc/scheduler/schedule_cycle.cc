@@ -147,7 +147,7 @@ Status Scheduler::score_feasible(Framework& fw, CycleState& s, const Pod& p, con
   return fw.run_score(s, p, feasible, scores, nullptr, &esc);
 }
 
-void Scheduler::schedule_cycle(const QueuedPodInfoPtr& qpi) {
+void Scheduler::schedule_cycle(const QueuedPodInfoPtr& qpi, int64_t cycle) {
   PodPtr pod = qpi->pod;
   Framework* fw = framework_for(pod->scheduler_name);
   if (!fw) return;
@@ -179,7 +179,6 @@ void Scheduler::schedule_cycle(const QueuedPodInfoPtr& qpi) {
   // activates after the binding cycle may have handed the frame back.
   std::shared_ptr<PodsToActivate> to_activate = frame->to_activate;
   state->write(kPodsToActivateKey, to_activate);
-  int64_t cycle = queue_->scheduling_cycle();
   if (tracer_.enabled())
     tracer_.record(TraceEvent{"queue_wait", pod->key(), "", qpi->timestamp_us, cycle_start - qpi->timestamp_us, 0});
 
@@ -191,7 +190,7 @@ void Scheduler::schedule_cycle(const QueuedPodInfoPtr& qpi) {
   release_retired();
   refresh_nom_mark(state->nominated.get());
   cnt_.attempts.fetch_add(1, std::memory_order_relaxed);
-  int64_t snap_end = clock_->now_us();
+  int64_t snap_end = tracer_.enabled() ? clock_->now_us() : 0;
   if (tracer_.enabled()) {
     tracer_.record(TraceEvent{"cycle_setup", pod->key(), "", cycle_start, snap_start - cycle_start, 0});
     tracer_.record(TraceEvent{"snapshot", pod->key(),
@@ -208,9 +207,10 @@ void Scheduler::schedule_cycle(const QueuedPodInfoPtr& qpi) {
     tracer_.record(TraceEvent{"filter", pod->key(), std::to_string(feasible.size()), snap_end,
                               clock_->now_us() - snap_end, 0});
   std::string host;
+  const NodeInfo* host_ni = nullptr;  // the snapshot's version of `host`
   if (st.is_success()) {
     if (feasible.size() == 1) {
-      host = feasible[0]->name();
+      host_ni = feasible[0];
     } else {
       std::vector<NodeScore>& scores = scores_buf_;
       if (!fw->has(kScore)) {
@@ -225,8 +225,9 @@ void Scheduler::schedule_cycle(const QueuedPodInfoPtr& qpi) {
         if (st.is_success()) st = score_feasible(*fw, *state, *pod, feasible, feasible_pos_buf_.data(), eq, scores);
       }
       if (st.is_success() && !extenders_.empty()) add_extender_scores(*pod, feasible, scores);
-      if (st.is_success()) host = feasible[select_host(scores)]->name();
+      if (st.is_success()) host_ni = feasible[select_host(scores)];
     }
+    if (host_ni) host = host_ni->name();
   }
   int64_t algo_end = clock_->now_us();
   CycleMetrics& cm = cycle_metrics(*fw);
@@ -264,6 +265,10 @@ void Scheduler::schedule_cycle(const QueuedPodInfoPtr& qpi) {
   // Assume.
   auto assumed = std::make_shared<Pod>(*pod);
   assumed->node_name = host;
+  // Still the cycle's private copy: Reserve plugins that place from the
+  // snapshot alone (FlexGPU) put their placement on it now, so the cache takes
+  // the pod in once, with its final accounting.
+  fw->run_prepare_assumed(*state, *assumed, *host_ni);
   Status ast = cache_->assume_pod(assumed);
   if (!ast.is_success()) {
     handle_failure(*fw, qpi, ast, "SchedulerError", "", cycle, {});

@@ -265,21 +265,23 @@ void Scheduler::scheduling_loop() {
   RealClock rc;
   while (running_.load()) {
     loop_tick_us_.store(rc.now_us(), std::memory_order_relaxed);
-    auto qpi = queue_->pop(100);
+    int64_t cycle = 0;
+    auto qpi = queue_->pop(100, &cycle);
     if (!qpi) continue;
     std::lock_guard<std::mutex> g(sched_mu_);
     in_cycle_.fetch_add(1);
-    schedule_cycle(qpi);
+    schedule_cycle(qpi, cycle);
     in_cycle_.fetch_sub(1);
   }
 }
 
 bool Scheduler::schedule_one(int timeout_ms) {
-  auto qpi = queue_->pop(timeout_ms);
+  int64_t cycle = 0;
+  auto qpi = queue_->pop(timeout_ms, &cycle);
   if (!qpi) return false;
   std::lock_guard<std::mutex> g(sched_mu_);
   in_cycle_.fetch_add(1);
-  schedule_cycle(qpi);
+  schedule_cycle(qpi, cycle);
   in_cycle_.fetch_sub(1);
   return true;
 }

@@ -356,7 +356,8 @@ class Scheduler {
                            Json* breakdown = nullptr);
 
   // ---- schedule_cycle.cc: scheduling cycle, binding cycle, failures ----
-  void schedule_cycle(const QueuedPodInfoPtr& qpi);
+  // `cycle`: the queue's scheduling cycle number of this pop (SchedulingQueue::pop).
+  void schedule_cycle(const QueuedPodInfoPtr& qpi, int64_t cycle);
   void activate_stashed(PodsToActivate& stash);
   // Score of the feasible nodes (after PreScore) as the scheduling cycle runs
   // it: node-local raw scores come from the template's equivalence slots

@@ -12,6 +12,7 @@ Usage:
     python -m flex_gpu_scheduler_amd.build_ext --tsan     # ThreadSanitizer stress driver
     python -m flex_gpu_scheduler_amd.build_ext --stress-count  # allocation-counting stress driver
     python -m flex_gpu_scheduler_amd.build_ext --gang-tests    # native gang-entry tests (--gang-tests-tsan)
+    python -m flex_gpu_scheduler_amd.build_ext --assume-tests  # native assume/queue/format tests (--assume-tests-tsan)
     python -m flex_gpu_scheduler_amd.build_ext --json-fuzz     # JSON/pod-decode driver under ASan+UBSan
     python -m flex_gpu_scheduler_amd.build_ext --patch-fuzz    # JSON patch / selector driver under ASan+UBSan
     python -m flex_gpu_scheduler_amd.build_ext --wire-tests    # native HTTP wire tests (--wire-asan: under ASan+UBSan)
@@ -334,6 +335,28 @@ def build_gang_tests(verbose: bool = True, tsan: bool = False) -> Path:
     return out
 
 
+def build_assume_tests(verbose: bool = True, tsan: bool = False) -> Path:
+    """Native tests of assuming a pod with its GPU placement, the cycle number
+    from the queue's pop and append_int (csrc/tests/assume_tests.cc). Shares its objects as build_gang_tests does;
+    `tsan` builds with -fsanitize=thread (host only)."""
+    includes = [str(CSRC)]
+    extra = ["-fsanitize=thread", "-g", "-O1", "-include", str(CSRC / "tools" / "tsan_compat.h")] if tsan else []
+    objs = build_objects(core_sources() + [CSRC / "tests" / "assume_tests.cc"], BUILD / ("tsan" if tsan else "core"),
+                         extra, includes)
+    out = BUILD / ("xsched_assume_tests_tsan" if tsan else "xsched_assume_tests")
+    newest = max(o.stat().st_mtime for o in objs)
+    if out.exists() and out.stat().st_mtime >= newest:
+        return out
+    cmd = ["g++", *(["-fsanitize=thread"] if tsan else []), "-pthread", *[str(o) for o in objs], *LINK_LIBS,
+           "-o", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"assume tests link failed:\n{r.stderr[-8000:]}")
+    if verbose:
+        print(f"[build_ext] built {out.relative_to(ROOT)}")
+    return out
+
+
 def build_wire_tests(verbose: bool = True, sanitize: bool = False) -> Path:
     """Native tests of the HTTP/1.1 wire layer (csrc/tests/wire_tests.cc):
     rest/wire.cc and OpenSSL only. `sanitize` builds with AddressSanitizer
@@ -373,6 +396,9 @@ def main(argv: list[str] | None = None) -> int:
     ap.add_argument("--core-g", action="store_true", help="the extension with -g into dbg/ (sampling runs)")
     ap.add_argument("--gang-tests", action="store_true", help="native tests of the lister's gang entries")
     ap.add_argument("--gang-tests-tsan", action="store_true", help="the same under ThreadSanitizer (host only)")
+    ap.add_argument("--assume-tests", action="store_true",
+                    help="native tests of assume-with-placement, pop's cycle number and append_int")
+    ap.add_argument("--assume-tests-tsan", action="store_true", help="the same under ThreadSanitizer (host only)")
     ap.add_argument("--wire-tests", action="store_true", help="native tests of the HTTP/1.1 wire layer")
     ap.add_argument("--wire-asan", action="store_true", help="the same under ASan+UBSan (host only)")
     a = ap.parse_args(argv)
@@ -381,6 +407,9 @@ def main(argv: list[str] | None = None) -> int:
         return 0
     if a.gang_tests or a.gang_tests_tsan:
         build_gang_tests(tsan=a.gang_tests_tsan)
+        return 0
+    if a.assume_tests or a.assume_tests_tsan:
+        build_assume_tests(tsan=a.assume_tests_tsan)
         return 0
     if a.core_g:
         build_core_debuginfo()

@@ -28,6 +28,12 @@ run() {  # name dir waves
 python -m flex_gpu_scheduler_amd.build_ext --gang-tests-tsan > /dev/null || exit 1
 timeout -k 10 600 build/xsched_gang_tests_tsan > /tmp/san_tsan_gang_tests.log 2>&1
 echo "tsan  gang_tests  rc=$?  reports=$(grep -c "WARNING: ThreadSanitizer" /tmp/san_tsan_gang_tests.log)  $(tail -1 /tmp/san_tsan_gang_tests.log)" | tee -a "$out"
+# Assume with placement against assume-then-Reserve, forget, confirmation,
+# Unreserve, pop's cycle number and append_int (csrc/tests/assume_tests.cc),
+# as a stand-alone ThreadSanitizer program.
+python -m flex_gpu_scheduler_amd.build_ext --assume-tests-tsan > /dev/null || exit 1
+timeout -k 10 600 build/xsched_assume_tests_tsan > /tmp/san_tsan_assume_tests.log 2>&1
+echo "tsan  assume_tests  rc=$?  reports=$(grep -c "WARNING: ThreadSanitizer" /tmp/san_tsan_assume_tests.log)  $(tail -1 /tmp/san_tsan_assume_tests.log)" | tee -a "$out"
 run bench64 /tmp/san_bench 3
 # The 1,024-node headline waves: gang window, Filter scan memo, column
 # equivalence table, snapshot arrays (one wave of 12k pods).
