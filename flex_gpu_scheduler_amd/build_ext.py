@@ -1,5 +1,5 @@
 """In-tree native build: the C++ scheduler core (`_xsched`) and the HIP/CDNA4
-probe kernels (`ops/_hipprobe`).
+probe kernels (`ops/_hipprobe`, and the memory sweep's `ops/_hipmem`).
 
 Both land next to the Python sources (not site-packages) so the built `.so`
 files travel with the repo snapshot to the MI355X box and show up as loaded
@@ -141,17 +141,21 @@ def build_hip(verbose: bool = True) -> Path | None:
     srcs = sorted((CSRC / "hip").glob("*.hip"))
     if not srcs:
         return None
+    # The memory sweep is a library of its own (ops/_hipmem.so): the C ABI of
+    # _hipprobe.so is pinned symbol by symbol and does not grow with it.
+    mem = [s for s in srcs if s.name == "mem_sweep.hip"]
     out = PKG / "ops" / "_hipprobe.so"
-    newest = max([s.stat().st_mtime for s in srcs] + [_headers_mtime()])
-    if out.exists() and out.stat().st_mtime >= newest:
-        return out
-    cmd = [hipcc, f"--offload-arch={HIP_ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared",
-           f"-I{CSRC}", *[str(s) for s in srcs], "-o", str(out)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(f"hipcc failed:\n{' '.join(cmd)}\n{r.stderr[-8000:]}")
-    if verbose:
-        print(f"[build_ext] built {out.relative_to(ROOT)} for {HIP_ARCH}")
+    for lib, lib_srcs in ((out, [s for s in srcs if s not in mem]), (PKG / "ops" / "_hipmem.so", mem)):
+        newest = max([s.stat().st_mtime for s in lib_srcs] + [_headers_mtime()])
+        if lib.exists() and lib.stat().st_mtime >= newest:
+            continue
+        cmd = [hipcc, f"--offload-arch={HIP_ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared",
+               f"-I{CSRC}", *[str(s) for s in lib_srcs], "-o", str(lib)]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError(f"hipcc failed:\n{' '.join(cmd)}\n{r.stderr[-8000:]}")
+        if verbose:
+            print(f"[build_ext] built {lib.relative_to(ROOT)} for {HIP_ARCH}")
     return out
 
 

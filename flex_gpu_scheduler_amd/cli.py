@@ -351,8 +351,8 @@ def _part_list_flag(args, kind: str, parts: str) -> dict:
 
 def health_fn_args(args) -> dict:
     """hip_health_fn's keywords from the node-agent flags.
-    --health-matrix-sweep, --health-lane-sweep, --health-valu-sweep: as
-    _part_list_flag says, but the matrix keys are always there (False, None).
+    --health-matrix-sweep, --health-lane-sweep, --health-valu-sweep,
+    --health-mem-sweep: as _part_list_flag says, but the matrix keys are always there (False, None).
     --health-hbm-sweep: absent -> no hbm keys, bare -> all free HBM less the
     reserve (hbm_gib None), else that many GiB.
     --health-register-sweep: absent -> no regfile key."""
@@ -363,7 +363,8 @@ def health_fn_args(args) -> dict:
         kw.update(hbm=True, hbm_gib=None if h == "all" else float(h))
     if getattr(args, "health_register_sweep", False):
         kw.update(regfile=True)
-    kw.update(**_part_list_flag(args, "lane", "paths"), **_part_list_flag(args, "valu", "units"))
+    kw.update(**_part_list_flag(args, "lane", "paths"), **_part_list_flag(args, "valu", "units"),
+              **_part_list_flag(args, "mem", "routes"))
     return kw
 
 
@@ -572,6 +573,13 @@ def build_parser() -> argparse.ArgumentParser:
                         "table) run on every SIMD of every CU (a comma list selects some; default all); a bad XCD is "
                         "fenced like --health-sweep's and its units are published as valuFaults. Implies "
                         "--health-probe; independent of the other sweeps")
+    p.add_argument("--health-mem-sweep", nargs="?", const="all", default=None, metavar="ROUTES",
+                   help="health probe plus the memory-path sweep: gwidth, buffer, flat, atomic, l1, l2 and scalar (global, "
+                        "buffer and flat loads and stores of every width, the memory-side atomics, the vector L1, the "
+                        "XCD's L2 and the scalar data cache) run on every CU (a comma list selects some; default all); "
+                        "it holds about 144 MiB of HBM while it runs and reports the GPU unswept, not failed, when "
+                        "that cannot be had; a bad XCD is fenced like --health-sweep's and its routes are published as "
+                        "memFaults. Implies --health-probe; independent of the other sweeps")
     p.add_argument("--health-sweep-period", type=float, default=600.0, metavar="SECONDS",
                    help="reuse a sweep's verdict this long before sweeping the GPU again")
     p.add_argument("--bandwidth-probe", action="store_true",

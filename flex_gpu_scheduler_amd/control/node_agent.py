@@ -18,7 +18,8 @@ exporter + metrics-server:
     matrix formats such an XCD gets wrong are published as `matrixFaults`
     and the register files it reads back wrong as `registerFaults` and the
     cross-lane and LDS paths it moves data wrongly through as `laneFaults`
-    and the vector-ALU units it mis-computes as `valuFaults`;
+    and the vector-ALU units it mis-computes as `valuFaults` and the routes
+    between registers and HBM it corrupts data on as `memFaults`;
     a verdict that carries an HBM fault (the HBM sweep) withholds the whole
     GPU, partitioned or not, and is published as `hbmFaults`;
   * samples load (gpu/telemetry.py) and publishes its WatcherMetrics document
@@ -92,6 +93,11 @@ SWEEP_KINDS = (
     SweepKind("lane", "lane_sweep", "lane", "laneSweep", "paths", "laneFaults", lambda v: list(v["failed_paths"])),
     SweepKind("valu", "valu_sweep", "valu", "valuSweep", "units", "valuFaults", lambda v: list(v["failed_units"])),
 )
+# The memory-path sweep runs after them, through the same code. It stands
+# apart because, like the HBM sweep, it holds HBM while it runs and can find
+# none to hold: its GPU is then unswept, which is no verdict at all.
+MEM_SWEEP_KIND = SweepKind("mem", "mem_sweep", "mem", "memSweep", "routes", "memFaults",
+                           lambda v: list(v["failed_routes"]))
 
 FAULT_KINDS = {
     # What the per-CU sweeps found on a faulty XCD. Informational: the XCD is
@@ -101,6 +107,10 @@ FAULT_KINDS = {
     # virtual address, which cannot be tied to the HBM slice of one compute
     # partition, so there is no partial fence for memory.
     "hbmFaults": FaultKind(per_xcd=False, withholds_gpu=True),
+    # What the memory-path sweep found on the GPU: one dict, {XCD id: [route,
+    # ...]}, of the XCDs with a fault. Informational like the first group; the
+    # XCD is fenced through xcdFaults.
+    MEM_SWEEP_KIND.faults_key: FaultKind(per_xcd=False),
 }
 
 
@@ -445,18 +455,21 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
                   hbm_args: dict | None = None, regfile: bool = False,
                   regfile_args: dict | None = None, lane: bool = False, lane_paths: list | None = None,
                   lane_args: dict | None = None, valu: bool = False, valu_units: list | None = None,
-                  valu_args: dict | None = None) -> Callable[[int], "bool | GpuHealth"]:
+                  valu_args: dict | None = None, mem: bool = False, mem_routes: list | None = None,
+                  mem_args: dict | None = None) -> Callable[[int], "bool | GpuHealth"]:
     """Health callback backed by the HIP probes (HBM pattern + checksum and an
     MFMA tile check per GPU).
 
-    Each kind of SWEEP_KINDS has a switch `<kind>` that also runs that per-CU
-    sweep of HipProbe (`sweep`: the CU sweep), `<kind>_args` for its keywords
+    Each kind of SWEEP_KINDS, and MEM_SWEEP_KIND, has a switch `<kind>` that
+    also runs that per-CU sweep of HipProbe (`sweep`: the CU sweep), `<kind>_args` for its keywords
     and, where it sweeps named parts, `<kind>_<parts>` to select some (None for
     all). Its summary and, the CU sweep apart, its {xcd: fault} go into the
     verdict's detail under the kind's keys. A fault is the list of the failed
-    formats, paths or units; of `regfile`, {"files": [...], "cells": n,
+    formats, paths, units or routes; of `regfile`, {"files": [...], "cells": n,
     "flipMask": "0x...", "simds": n}. The VALU sweep's failed steps are in
-    detail["valuSweep"].
+    detail["valuSweep"]. The memory sweep holds an arena in HBM while it runs;
+    where that cannot be had the device is logged as unswept, which neither
+    fails it nor touches the other sweeps' verdicts.
     The callback runs on every heartbeat, so the sweeps' verdict is reused for
     `sweep_period_s`. On a device that shows all 8 XCDs the verdict is a
     GpuHealth naming the bad physical XCDs of any of these sweeps; a
@@ -475,13 +488,14 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
     memory could be had is logged as unswept and a sweep that got less than it
     asked for as short; neither fails the device."""
     given = locals()  # the parameters by name, for SWEEP_KINDS
-    from ..ops.hip_probe import HBM_UNSWEPT, ProbeError, probe
+    from ..ops.hip_probe import HBM_UNSWEPT, MEM_UNSWEPT, ProbeError, probe
 
     p = probe()
     last: dict[int, tuple[float, object]] = {}  # dev -> (monotonic time, sweep verdict)
     # The enabled kinds, each with the keywords of its probe method.
     per_cu_sweeps = [(k, {**({k.selection: given[f"{k.enabled_by}_{k.selection}"]} if k.selection else {}),
-                          **(given[f"{k.enabled_by}_args"] or {})}) for k in SWEEP_KINDS if given[k.enabled_by]]
+                          **(given[f"{k.enabled_by}_args"] or {})})
+                     for k in SWEEP_KINDS + (MEM_SWEEP_KIND,) if given[k.enabled_by]]
 
     def sweep_verdict(dev: int):
         now = time.monotonic()
@@ -490,7 +504,13 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
         bad: set[int] = set()
         detail: dict = {}
         for k, keywords in per_cu_sweeps:
-            s = getattr(p, k.method)(dev, **keywords)["summary"]
+            try:
+                s = getattr(p, k.method)(dev, **keywords)["summary"]
+            except ProbeError as e:
+                if k is not MEM_SWEEP_KIND or e.rc != MEM_UNSWEPT:
+                    raise
+                log.warning("mem sweep GPU %d: unswept, no memory could be had (%s)", dev, e)
+                continue
             fault_of = k.fault_of
             found = {int(x): fault_of(v) for x, v in s["xcds"].items() if fault_of(v)} if fault_of else s["bad_xcds"]
             log.log(logging.WARNING if s["bad_xcds"] else logging.INFO,

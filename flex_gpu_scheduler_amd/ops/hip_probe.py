@@ -18,9 +18,13 @@ Sweeps of every CU (csrc/hip/<name>.hip), each naming the XCD of a CU that fails
     and DMA LDS paths; names the paths;
   * valu_sweep: every SIMD's vector ALU (float, packed, wide-integer,
     bit-field, dot, conversion and transcendental instructions); names the
-    units and the steps.
-The matrix, lane and VALU sweeps are sweeps over named parts: PART_SWEEPS
-describes each, and one implementation serves the three.
+    units and the steps;
+  * mem_sweep: the path between a wave's registers and HBM (global, buffer
+    and flat loads and stores of every width, the memory-side atomics, the
+    vector L1, the XCD's L2 and the scalar data cache); names the routes.
+    It is a library of its own, _hipmem.so.
+The matrix, lane, VALU and memory sweeps are sweeps over named parts:
+PART_SWEEPS describes each, and one implementation serves the four.
 
 hbm_sweep (csrc/hip/hbm_sweep.hip): all free HBM under an address-keyed
 pattern in both polarities; names the vectors and bits that read back wrong.
@@ -34,6 +38,8 @@ from dataclasses import dataclass
 from pathlib import Path
 
 _LIB = Path(__file__).resolve().parent / "_hipprobe.so"
+# The memory sweep is a library of its own: _hipprobe.so's C ABI stays as it is.
+_MEM_LIB = Path(__file__).resolve().parent / "_hipmem.so"
 MODES = {"read": 0, "write": 1, "copy": 2, "triad": 3}
 
 
@@ -103,6 +109,22 @@ VALU_SEED = 0x1B873593
 VALU_ROUNDS = 2  # operand sets per step; measured in profiles/valu_sweep_defaults.md
 VALU_BLOCK = 256
 
+# k_mem_sweep (csrc/hip/mem_sweep.hip): one 128-byte record per workgroup,
+# {xcd, cu, simd_mask, fail, 7 bad counts, 7 digests, bad_simds, 0 x 13}.
+MEM_RECORD_WORDS = 32
+MEM_SEED = 0x1B873593
+MEM_BLOCK = 256
+# xs_mem_sweep could not allocate its arena: nothing was launched. The GPU is
+# unswept, never failed (the meaning HBM_UNSWEPT has).
+MEM_UNSWEPT = -1003
+# A guard band of the arena did not hold the host's sentinel after the launch:
+# a store went astray. The library's last error names the first bad address.
+MEM_STRAY_STORE = -1004
+MEM_WORDING = {MEM_UNSWEPT: "no memory could be had for the arena: nothing was swept"}
+# The C ABI of _hipmem.so.
+MEM_SYMBOLS = ("xs_mem_sweep_last_error", "xs_mem_routes", "xs_mem_shape", "xs_mem_probe", "xs_mem_sweep_expected",
+               "xs_mem_sweep_info", "xs_mem_sweep")
+
 
 @dataclass(frozen=True)
 class PartSweep:
@@ -130,8 +152,10 @@ PART_SWEEPS = {
                       LANE_RECORD_WORDS, digests=12, bad=4, bad_simds=20),
     "valu": PartSweep("valu", "xs_valu_units", "VALU unit", "failed_units", "units",
                       VALU_RECORD_WORDS, digests=12, bad=4, bad_simds=20, step_mask=22),
+    "mem": PartSweep("mem", "xs_mem_routes", "memory route", "failed_routes", "routes",
+                     MEM_RECORD_WORDS, digests=11, bad=4, bad_simds=18),
 }
-MATRIX_SWEEP, LANE_SWEEP, VALU_SWEEP = PART_SWEEPS.values()
+MATRIX_SWEEP, LANE_SWEEP, VALU_SWEEP, MEM_SWEEP = PART_SWEEPS.values()
 
 # k_hbm_fill / k_hbm_verify (csrc/hip/hbm_sweep.hip)
 HBM_SWEEP_SEED = 0x5EED1E55
@@ -244,9 +268,10 @@ def decode_part_record(kind: PartSweep, names: list[str], w, expected: dict, ste
 
 
 class HipProbe:
-    def __init__(self, path: str | Path = _LIB):
-        if not Path(path).exists():
-            raise ProbeError(f"{path} not built; run `python -m flex_gpu_scheduler_amd.build_ext --hip`")
+    def __init__(self, path: str | Path = _LIB, mem_path: str | Path = _MEM_LIB):
+        for built in (path, mem_path):
+            if not Path(built).exists():
+                raise ProbeError(f"{built} not built; run `python -m flex_gpu_scheduler_amd.build_ext --hip`")
         try:
             # torch's bundled libamdhip64.so.7 first, whatever the import order
             # of the caller: the probe library then resolves the same soname to
@@ -343,6 +368,21 @@ class HipProbe:
         L.xs_valu_sweep.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                     ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p,
                                     ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]
+        # mem_sweep.hip's library. Its functions are made attributes of
+        # self.lib, where _call and _part_sweep look every xs_* up.
+        self.mem_lib = ctypes.CDLL(str(mem_path))
+        M = self.mem_lib
+        M.xs_mem_sweep_last_error.restype = ctypes.c_char_p
+        M.xs_mem_routes.restype = ctypes.c_char_p
+        M.xs_mem_shape.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        M.xs_mem_probe.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]
+        M.xs_mem_sweep_expected.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
+        M.xs_mem_sweep_info.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        M.xs_mem_sweep.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int,
+                                   ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int),
+                                   ctypes.POINTER(ctypes.c_double)]
+        for name in MEM_SYMBOLS:
+            setattr(L, name, getattr(M, name))
         L.xs_hbm_sweep_last_error.restype = ctypes.c_char_p
         L.xs_hbm_sweep_pattern.argtypes = [ctypes.c_uint64, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int,
                                            ctypes.c_void_p]
@@ -662,7 +702,7 @@ class HipProbe:
 
     # ------------------------------------------------------ the per-CU sweeps
     def _sweep_until_covered(self, name: str, dev: int, blocks: int, max_rounds: int, words: int, launch, expected,
-                             decode, summarize) -> dict:
+                             decode, summarize, wording: dict | None = None) -> dict:
         """The launch policy of every per-CU sweep. A launch whose grid could
         cover the device (`blocks` 0 = 4 per CU) is repeated while some CU has
         not been seen, at most `max_rounds` launches in all; records accumulate.
@@ -672,7 +712,8 @@ class HipProbe:
         asked for once, after the first launch; `decode(w, expected)` makes the
         record of one workgroup's words, failing it where a digest differs
         from the host's even if the device-side comparator (on the same CU)
-        passed it; `summarize(records, compute_units)` is the verdict.
+        passed it; `summarize(records, compute_units)` is the verdict; `wording`
+        as in _probe_error.
         Returns {"records", "summary": the verdict plus rounds, ms, blocks}."""
         cus = int(self.props(dev)["computeUnits"])
         n_blocks = blocks if blocks != 0 else 4 * cus
@@ -685,7 +726,7 @@ class HipProbe:
             n, ms = ctypes.c_int(), ctypes.c_double()
             rc = launch(n_blocks, buf, ctypes.byref(n), ctypes.byref(ms))
             if rc != 0:
-                raise _probe_error(getattr(self.lib, f"xs_{name}_last_error"), rc, name)
+                raise _probe_error(getattr(self.lib, f"xs_{name}_last_error"), rc, name, wording)
             if want is None:
                 want = expected()
             rounds += 1
@@ -770,11 +811,12 @@ class HipProbe:
         return dict(zip(fields, out))
 
     def _part_sweep(self, kind: PartSweep, summarize, dev: int, blocks: int, chosen, inject, max_rounds: int,
-                    args: tuple = (), report: dict | None = None, steps=()) -> dict:
+                    args: tuple = (), report: dict | None = None, steps=(), wording: dict | None = None) -> dict:
         """One sweep over the `chosen` parts (None: all), its verdict being
         summarize(records, compute_units, names). `args` stand between the mask
         and the injection in the C call and behind the mask in that of the
-        expected digests; `report` goes into the summary before the selection."""
+        expected digests; `report` goes into the summary before the selection;
+        `wording` as in _probe_error."""
         names = self._part_names(kind)
         mask = self._part_mask(kind, chosen)
         selected = [f for i, f in enumerate(names) if mask >> i & 1]
@@ -785,7 +827,7 @@ class HipProbe:
             lambda nb, *out: sweep(dev, nb, mask, *args, ix, ic, im, *out),
             lambda: self._part_expected(kind, selected, *args),
             lambda w, expected: decode_part_record(kind, names, w, expected, steps),
-            lambda records, cus: summarize(records, cus, names))
+            lambda records, cus: summarize(records, cus, names), wording)
         out["summary"].update(report or {}, **{kind.selection: selected})
         return out
 
@@ -950,6 +992,58 @@ class HipProbe:
         ms, blocks, paths, seed}."""
         return self._part_sweep(LANE_SWEEP, summarize_lane_sweep, dev, blocks, paths, inject, max_rounds, (seed,),
                                 {"seed": seed})
+
+    # --------------------------------------------------------- memory sweep
+    def mem_routes(self) -> list[str]:
+        """Route names of the memory-path sweep; the index is the route's bit."""
+        return self._part_names(MEM_SWEEP)
+
+    def mem_shape(self, route: str) -> dict:
+        """`steps` of one route and the `words` every thread receives per step."""
+        out = self._part_shape(MEM_SWEEP, route, 2)
+        return {"steps": out[0], "words": out[1]}
+
+    def mem_probe(self, dev: int, route: str, seed: int = MEM_SEED):
+        """k_mem_probe: one workgroup runs `route` and stores every value it
+        received: uint32 [steps, words, 256] (thread = 64 x wave + lane)."""
+        import numpy as np
+
+        sh = self.mem_shape(route)
+        out = np.zeros((sh["steps"], sh["words"], MEM_BLOCK), np.uint32)
+        self._call("mem_sweep", "mem_probe", dev, self.mem_routes().index(route), seed, out.ctypes.data, out.size,
+                   wording=MEM_WORDING)
+        return out
+
+    def mem_sweep_expected(self, routes=None, seed: int = MEM_SEED) -> dict:
+        """The workgroup digest a healthy CU leaves per selected route,
+        computed on the host from the ISA's rules and the address maps."""
+        return self._part_expected(MEM_SWEEP, routes, seed)
+
+    def mem_sweep_info(self, dev: int = 0) -> dict:
+        """What the runtime reports for k_mem_sweep: `num_regs`, `scratch_bytes`
+        per lane, `lds_bytes` per workgroup, `blocks_per_cu` (workgroups that
+        fit on a CU at once), and the `arena_bytes` of HBM a workgroup's slab
+        and its guard bands take."""
+        return self._sweep_info("mem_sweep", dev,
+                                ("num_regs", "scratch_bytes", "lds_bytes", "blocks_per_cu", "arena_bytes"))
+
+    def mem_sweep(self, dev: int = 0, blocks: int = 0, routes=None, seed: int = MEM_SEED,
+                  inject: tuple | None = None, max_rounds: int = 4) -> dict:
+        """k_mem_sweep: every selected route (None: all) between a wave's
+        registers and HBM run on every CU a workgroup lands on, each workgroup
+        in a slab of its own (`mem_sweep_info()["arena_bytes"]` per workgroup,
+        held while the launch runs). `inject` = (xcd, cu key or None for every
+        CU of that XCD, [route names]): those workgroups flip one bit of one
+        received value of those routes (tests the comparator on a healthy
+        GPU). `blocks` 0: 4 per CU.
+
+        Raises ProbeError with rc MEM_UNSWEPT when the arena could not be had
+        (nothing ran) and MEM_STRAY_STORE when a guard band was written.
+        Relaunched while some CU has not been seen, as cu_sweep does. Returns
+        {"records": [...], "summary": summarize_mem_sweep(...) plus rounds,
+        ms, blocks, routes, seed}."""
+        return self._part_sweep(MEM_SWEEP, summarize_mem_sweep, dev, blocks, routes, inject, max_rounds, (seed,),
+                                {"seed": seed}, wording=MEM_WORDING)
 
     # ----------------------------------------------------------- VALU sweep
     def valu_units(self) -> list[str]:
@@ -1210,6 +1304,13 @@ def summarize_lane_sweep(records: list[dict], compute_units: int, paths: list[st
     bits (`paths` names them in bit order): adds `failed_paths` per XCD and
     overall."""
     return _name_fail_bits(summarize_sweep(records, compute_units), LANE_SWEEP.summary_key, paths)
+
+
+def summarize_mem_sweep(records: list[dict], compute_units: int, routes: list[str]) -> dict:
+    """summarize_sweep over k_mem_sweep records, whose fail bits are route
+    bits (`routes` names them in bit order): adds `failed_routes` per XCD and
+    overall."""
+    return _name_fail_bits(summarize_sweep(records, compute_units), MEM_SWEEP.summary_key, routes)
 
 
 def summarize_valu_sweep(records: list[dict], compute_units: int, units: list[str]) -> dict:
