@@ -59,15 +59,21 @@ __device__ __forceinline__ uint32_t take_word(Tally& y, uint32_t* dump, uint32_t
 }
 
 // LDS words the reduction below uses, from the start of the allocation.
-constexpr uint32_t part_reduction_words(int n, int extra) { return (2 * n + 2 + extra) * kPartBlock; }
+template <int B = kPartBlock>
+constexpr uint32_t part_reduction_words(int n, int extra) {
+  return (2 * n + 2 + extra) * B;
+}
 
-// The 256 threads' tallies and `extra` (X words a thread ORs in, written
+// The B threads' tallies (256 unless the sweep says otherwise) and `extra` (X words a thread ORs in, written
 // behind the reserved word) become the workgroup's record: every thread stores
 // its words to `lds` as [quantity][thread]; after a barrier thread 0 sums the
 // counts and digests, ORs the rest, fails a selected part that counted a
 // mismatch or whose digest is not the host's, and writes the record with
 // vector stores. No shuffle, DPP or permute: lane_sweep.hip tests those.
-template <int N, int X, typename Record>
+// A block above 256 threads sums in two stages: lane 0 of every wave folds its
+// wave's 64 words of each quantity into its own, and after another barrier
+// thread 0 sums one word per wave.
+template <int N, int X, int B = kPartBlock, typename Record>
 __device__ __forceinline__ void reduce_parts(uint32_t* lds, uint32_t t, uint32_t simd, const Tally (&y)[N],
                                              const uint32_t* extra, uint32_t part_mask, const PartExpect<N>& expect,
                                              uint32_t xcd, uint32_t cu, Record* record) {
@@ -78,22 +84,37 @@ __device__ __forceinline__ void reduce_parts(uint32_t* lds, uint32_t t, uint32_t
   uint32_t any = 0;
 #pragma unroll
   for (int p = 0; p < N; ++p) {
-    lds[p * kPartBlock + t] = y[p].bad;
-    lds[(N + p) * kPartBlock + t] = y[p].digest;
+    lds[p * B + t] = y[p].bad;
+    lds[(N + p) * B + t] = y[p].digest;
     any |= y[p].bad;
   }
-  lds[kBadSimds * kPartBlock + t] = any ? 1u << simd : 0u;
-  lds[kSimds * kPartBlock + t] = 1u << simd;
+  lds[kBadSimds * B + t] = any ? 1u << simd : 0u;
+  lds[kSimds * B + t] = 1u << simd;
 #pragma unroll
-  for (int q = 0; q < X; ++q) lds[(kSimds + 1 + q) * kPartBlock + t] = extra[q];
+  for (int q = 0; q < X; ++q) lds[(kSimds + 1 + q) * B + t] = extra[q];
   __syncthreads();
+  constexpr int kStride = B > kPartBlock ? 64 : 1;  // thread 0 reads every kStride-th word
+  if constexpr (kStride > 1) {
+    if ((t & 63u) == 0) {
+      uint32_t part[kWords] = {};
+      for (int j = 0; j < 64; ++j) {
+#pragma unroll
+        for (uint32_t q = 0; q < 2 * N; ++q) part[q] += lds[q * B + t + j];
+#pragma unroll
+        for (uint32_t q = 2 * N; q < kWords; ++q) part[q] |= lds[q * B + t + j];
+      }
+#pragma unroll
+      for (uint32_t q = 0; q < kWords; ++q) lds[q * B + t] = part[q];
+    }
+    __syncthreads();
+  }
   if (t == 0) {
     uint32_t sum[kWords] = {};
-    for (int u = 0; u < kPartBlock; ++u) {
+    for (int u = 0; u < B; u += kStride) {
 #pragma unroll
-      for (uint32_t q = 0; q < 2 * N; ++q) sum[q] += lds[q * kPartBlock + u];
+      for (uint32_t q = 0; q < 2 * N; ++q) sum[q] += lds[q * B + u];
 #pragma unroll
-      for (uint32_t q = 2 * N; q < kWords; ++q) sum[q] |= lds[q * kPartBlock + u];
+      for (uint32_t q = 2 * N; q < kWords; ++q) sum[q] |= lds[q * B + u];
     }
     uint32_t fail = 0;
 #pragma unroll

@@ -1,5 +1,6 @@
 """In-tree native build: the C++ scheduler core (`_xsched`) and the HIP/CDNA4
-probe kernels (`ops/_hipprobe`, and the memory sweep's `ops/_hipmem`).
+probe kernels (`ops/_hipprobe`, the memory sweep's `ops/_hipmem` and the scalar
+sweep's `ops/_hipscalar`).
 
 Both land next to the Python sources (not site-packages) so the built `.so`
 files travel with the repo snapshot to the MI355X box and show up as loaded
@@ -144,8 +145,10 @@ def build_hip(verbose: bool = True) -> Path | None:
     # The memory sweep is a library of its own (ops/_hipmem.so): the C ABI of
     # _hipprobe.so is pinned symbol by symbol and does not grow with it.
     mem = [s for s in srcs if s.name == "mem_sweep.hip"]
+    scalar = [s for s in srcs if s.name == "scalar_sweep.hip"]  # ops/_hipscalar.so, by the same rule
     out = PKG / "ops" / "_hipprobe.so"
-    for lib, lib_srcs in ((out, [s for s in srcs if s not in mem]), (PKG / "ops" / "_hipmem.so", mem)):
+    for lib, lib_srcs in ((out, [s for s in srcs if s not in mem + scalar]), (PKG / "ops" / "_hipmem.so", mem),
+                          (PKG / "ops" / "_hipscalar.so", scalar)):
         newest = max([s.stat().st_mtime for s in lib_srcs] + [_headers_mtime()])
         if lib.exists() and lib.stat().st_mtime >= newest:
             continue

@@ -352,7 +352,7 @@ def _part_list_flag(args, kind: str, parts: str) -> dict:
 def health_fn_args(args) -> dict:
     """hip_health_fn's keywords from the node-agent flags.
     --health-matrix-sweep, --health-lane-sweep, --health-valu-sweep,
-    --health-mem-sweep: as _part_list_flag says, but the matrix keys are always there (False, None).
+    --health-scalar-sweep, --health-mem-sweep: as _part_list_flag says, but the matrix keys are always there (False, None).
     --health-hbm-sweep: absent -> no hbm keys, bare -> all free HBM less the
     reserve (hbm_gib None), else that many GiB.
     --health-register-sweep: absent -> no regfile key."""
@@ -364,7 +364,7 @@ def health_fn_args(args) -> dict:
     if getattr(args, "health_register_sweep", False):
         kw.update(regfile=True)
     kw.update(**_part_list_flag(args, "lane", "paths"), **_part_list_flag(args, "valu", "units"),
-              **_part_list_flag(args, "mem", "routes"))
+              **_part_list_flag(args, "scalar", "parts"), **_part_list_flag(args, "mem", "routes"))
     return kw
 
 
@@ -572,6 +572,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "vector ALU (each instruction under its own mnemonic, on hashed operands, against a host-computed "
                         "table) run on every SIMD of every CU (a comma list selects some; default all); a bad XCD is "
                         "fenced like --health-sweep's and its units are published as valuFaults. Implies "
+                        "--health-probe; independent of the other sweeps")
+    p.add_argument("--health-scalar-sweep", nargs="?", const="all", default=None, metavar="PARTS",
+                   help="health probe plus the scalar sweep: arith, logic, bits, cmp, branch, mask, movrel and sgpr (the "
+                        "scalar ALU's arithmetic, logic, bit, compare, branch, EXEC-mask and relative-move instructions "
+                        "and every SGPR a wave can name) run on every CU (a comma list selects some; default all); a bad "
+                        "XCD is fenced like --health-sweep's and its parts are published as scalarFaults. Implies "
                         "--health-probe; independent of the other sweeps")
     p.add_argument("--health-mem-sweep", nargs="?", const="all", default=None, metavar="ROUTES",
                    help="health probe plus the memory-path sweep: gwidth, buffer, flat, atomic, l1, l2 and scalar (global, "

@@ -18,7 +18,8 @@ exporter + metrics-server:
     matrix formats such an XCD gets wrong are published as `matrixFaults`
     and the register files it reads back wrong as `registerFaults` and the
     cross-lane and LDS paths it moves data wrongly through as `laneFaults`
-    and the vector-ALU units it mis-computes as `valuFaults` and the routes
+    and the vector-ALU units it mis-computes as `valuFaults` and the parts
+    of the scalar unit it gets wrong as `scalarFaults` and the routes
     between registers and HBM it corrupts data on as `memFaults`;
     a verdict that carries an HBM fault (the HBM sweep) withholds the whole
     GPU, partitioned or not, and is published as `hbmFaults`;
@@ -98,6 +99,12 @@ SWEEP_KINDS = (
 # none to hold: its GPU is then unswept, which is no verdict at all.
 MEM_SWEEP_KIND = SweepKind("mem", "mem_sweep", "mem", "memSweep", "routes", "memFaults",
                            lambda v: list(v["failed_routes"]))
+# The scalar sweep runs after the VALU sweep and before the memory sweep,
+# through the same code. It stands beside SWEEP_KINDS because its fault is one
+# dict for the GPU, as the memory sweep's is. It allocates nothing but its
+# records, so it has no "unswept" outcome.
+SCALAR_SWEEP_KIND = SweepKind("scalar", "scalar_sweep", "scalar", "scalarSweep", "parts", "scalarFaults",
+                              lambda v: list(v["failed_parts"]))
 
 FAULT_KINDS = {
     # What the per-CU sweeps found on a faulty XCD. Informational: the XCD is
@@ -111,6 +118,8 @@ FAULT_KINDS = {
     # ...]}, of the XCDs with a fault. Informational like the first group; the
     # XCD is fenced through xcdFaults.
     MEM_SWEEP_KIND.faults_key: FaultKind(per_xcd=False),
+    # What the scalar sweep found on the GPU: {XCD id: [part, ...]}, likewise.
+    SCALAR_SWEEP_KIND.faults_key: FaultKind(per_xcd=False),
 }
 
 
@@ -456,16 +465,17 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
                   regfile_args: dict | None = None, lane: bool = False, lane_paths: list | None = None,
                   lane_args: dict | None = None, valu: bool = False, valu_units: list | None = None,
                   valu_args: dict | None = None, mem: bool = False, mem_routes: list | None = None,
-                  mem_args: dict | None = None) -> Callable[[int], "bool | GpuHealth"]:
+                  mem_args: dict | None = None, scalar: bool = False, scalar_parts: list | None = None,
+                  scalar_args: dict | None = None) -> Callable[[int], "bool | GpuHealth"]:
     """Health callback backed by the HIP probes (HBM pattern + checksum and an
     MFMA tile check per GPU).
 
-    Each kind of SWEEP_KINDS, and MEM_SWEEP_KIND, has a switch `<kind>` that
+    Each kind of SWEEP_KINDS, SCALAR_SWEEP_KIND and MEM_SWEEP_KIND, in the order they run, has a switch `<kind>` that
     also runs that per-CU sweep of HipProbe (`sweep`: the CU sweep), `<kind>_args` for its keywords
     and, where it sweeps named parts, `<kind>_<parts>` to select some (None for
     all). Its summary and, the CU sweep apart, its {xcd: fault} go into the
     verdict's detail under the kind's keys. A fault is the list of the failed
-    formats, paths, units or routes; of `regfile`, {"files": [...], "cells": n,
+    formats, paths, units, scalar parts or routes; of `regfile`, {"files": [...], "cells": n,
     "flipMask": "0x...", "simds": n}. The VALU sweep's failed steps are in
     detail["valuSweep"]. The memory sweep holds an arena in HBM while it runs;
     where that cannot be had the device is logged as unswept, which neither
@@ -495,7 +505,7 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
     # The enabled kinds, each with the keywords of its probe method.
     per_cu_sweeps = [(k, {**({k.selection: given[f"{k.enabled_by}_{k.selection}"]} if k.selection else {}),
                           **(given[f"{k.enabled_by}_args"] or {})})
-                     for k in SWEEP_KINDS + (MEM_SWEEP_KIND,) if given[k.enabled_by]]
+                     for k in SWEEP_KINDS + (SCALAR_SWEEP_KIND, MEM_SWEEP_KIND) if given[k.enabled_by]]
 
     def sweep_verdict(dev: int):
         now = time.monotonic()

@@ -22,9 +22,13 @@ Sweeps of every CU (csrc/hip/<name>.hip), each naming the XCD of a CU that fails
   * mem_sweep: the path between a wave's registers and HBM (global, buffer
     and flat loads and stores of every width, the memory-side atomics, the
     vector L1, the XCD's L2 and the scalar data cache); names the routes.
-    It is a library of its own, _hipmem.so.
+    It is a library of its own, _hipmem.so;
+  * scalar_sweep: every CU's scalar ALU (arithmetic, logic, bit, compare,
+    branch, EXEC-mask and relative-move instructions) and the SGPRs a wave
+    can name; names the parts. It is a library of its own, _hipscalar.so.
 The matrix, lane, VALU and memory sweeps are sweeps over named parts:
-PART_SWEEPS describes each, and one implementation serves the four.
+PART_SWEEPS describes each, and one implementation serves the four and the
+scalar sweep, whose row SCALAR_SWEEP stands beside the table.
 
 hbm_sweep (csrc/hip/hbm_sweep.hip): all free HBM under an address-keyed
 pattern in both polarities; names the vectors and bits that read back wrong.
@@ -40,6 +44,8 @@ from pathlib import Path
 _LIB = Path(__file__).resolve().parent / "_hipprobe.so"
 # The memory sweep is a library of its own: _hipprobe.so's C ABI stays as it is.
 _MEM_LIB = Path(__file__).resolve().parent / "_hipmem.so"
+# So is the scalar sweep.
+_SCALAR_LIB = Path(__file__).resolve().parent / "_hipscalar.so"
 MODES = {"read": 0, "write": 1, "copy": 2, "triad": 3}
 
 
@@ -125,6 +131,17 @@ MEM_WORDING = {MEM_UNSWEPT: "no memory could be had for the arena: nothing was s
 MEM_SYMBOLS = ("xs_mem_sweep_last_error", "xs_mem_routes", "xs_mem_shape", "xs_mem_probe", "xs_mem_sweep_expected",
                "xs_mem_sweep_info", "xs_mem_sweep")
 
+# k_scalar_sweep (csrc/hip/scalar_sweep.hip): one 128-byte record per workgroup,
+# {xcd, cu, simd_mask, fail, 8 bad counts, 8 digests, bad_simds, 0, per SIMD the
+# OR of its waves' raw HW_REG_GPR_ALLOC words and the OR of their complements, 0 x 2}.
+SCALAR_RECORD_WORDS = 32
+SCALAR_SEED = 0x1B873593
+SCALAR_BLOCK = 1024
+SCALAR_COVER_WORD = 22  # the first of the eight coverage words
+# The C ABI of _hipscalar.so.
+SCALAR_SYMBOLS = ("xs_scalar_sweep_last_error", "xs_scalar_parts", "xs_scalar_shape", "xs_scalar_probe",
+                  "xs_scalar_sweep_expected", "xs_scalar_sweep_info", "xs_scalar_sweep")
+
 
 @dataclass(frozen=True)
 class PartSweep:
@@ -156,6 +173,9 @@ PART_SWEEPS = {
                      MEM_RECORD_WORDS, digests=11, bad=4, bad_simds=18),
 }
 MATRIX_SWEEP, LANE_SWEEP, VALU_SWEEP, MEM_SWEEP = PART_SWEEPS.values()
+# The scalar sweep's row stands beside the table: same record head as the lane sweep's.
+SCALAR_SWEEP = PartSweep("scalar", "xs_scalar_parts", "scalar part", "failed_parts", "parts", 32,
+                         digests=12, bad=4, bad_simds=20)
 
 # k_hbm_fill / k_hbm_verify (csrc/hip/hbm_sweep.hip)
 HBM_SWEEP_SEED = 0x5EED1E55
@@ -268,8 +288,9 @@ def decode_part_record(kind: PartSweep, names: list[str], w, expected: dict, ste
 
 
 class HipProbe:
-    def __init__(self, path: str | Path = _LIB, mem_path: str | Path = _MEM_LIB):
-        for built in (path, mem_path):
+    def __init__(self, path: str | Path = _LIB, mem_path: str | Path = _MEM_LIB,
+                 scalar_path: str | Path = _SCALAR_LIB):
+        for built in (path, mem_path, scalar_path):
             if not Path(built).exists():
                 raise ProbeError(f"{built} not built; run `python -m flex_gpu_scheduler_amd.build_ext --hip`")
         try:
@@ -383,6 +404,20 @@ class HipProbe:
                                    ctypes.POINTER(ctypes.c_double)]
         for name in MEM_SYMBOLS:
             setattr(L, name, getattr(M, name))
+        # scalar_sweep.hip's library, looked up through self.lib in the same way.
+        self.scalar_lib = ctypes.CDLL(str(scalar_path))
+        S = self.scalar_lib
+        S.xs_scalar_sweep_last_error.restype = ctypes.c_char_p
+        S.xs_scalar_parts.restype = ctypes.c_char_p
+        S.xs_scalar_shape.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        S.xs_scalar_probe.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]
+        S.xs_scalar_sweep_expected.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
+        S.xs_scalar_sweep_info.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        S.xs_scalar_sweep.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int,
+                                      ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int),
+                                      ctypes.POINTER(ctypes.c_double)]
+        for name in SCALAR_SYMBOLS:
+            setattr(L, name, getattr(S, name))
         L.xs_hbm_sweep_last_error.restype = ctypes.c_char_p
         L.xs_hbm_sweep_pattern.argtypes = [ctypes.c_uint64, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int,
                                            ctypes.c_void_p]
@@ -811,12 +846,14 @@ class HipProbe:
         return dict(zip(fields, out))
 
     def _part_sweep(self, kind: PartSweep, summarize, dev: int, blocks: int, chosen, inject, max_rounds: int,
-                    args: tuple = (), report: dict | None = None, steps=(), wording: dict | None = None) -> dict:
+                    args: tuple = (), report: dict | None = None, steps=(), wording: dict | None = None,
+                    tail=None) -> dict:
         """One sweep over the `chosen` parts (None: all), its verdict being
         summarize(records, compute_units, names). `args` stand between the mask
         and the injection in the C call and behind the mask in that of the
         expected digests; `report` goes into the summary before the selection;
-        `wording` as in _probe_error."""
+        `wording` as in _probe_error; `tail(w)` is what a record holds besides
+        decode_part_record's fields."""
         names = self._part_names(kind)
         mask = self._part_mask(kind, chosen)
         selected = [f for i, f in enumerate(names) if mask >> i & 1]
@@ -826,7 +863,7 @@ class HipProbe:
             f"{kind.prefix}_sweep", dev, blocks, max_rounds, kind.record_words,
             lambda nb, *out: sweep(dev, nb, mask, *args, ix, ic, im, *out),
             lambda: self._part_expected(kind, selected, *args),
-            lambda w, expected: decode_part_record(kind, names, w, expected, steps),
+            lambda w, expected: {**decode_part_record(kind, names, w, expected, steps), **(tail(w) if tail else {})},
             lambda records, cus: summarize(records, cus, names), wording)
         out["summary"].update(report or {}, **{kind.selection: selected})
         return out
@@ -1044,6 +1081,55 @@ class HipProbe:
         ms, blocks, routes, seed}."""
         return self._part_sweep(MEM_SWEEP, summarize_mem_sweep, dev, blocks, routes, inject, max_rounds, (seed,),
                                 {"seed": seed}, wording=MEM_WORDING)
+
+    # --------------------------------------------------------- scalar sweep
+    def scalar_parts(self) -> list[str]:
+        """Part names of the scalar sweep; the index is the part's bit."""
+        return self._part_names(SCALAR_SWEEP)
+
+    def scalar_shape(self, part: str) -> dict:
+        """`steps` of one part and the `words` every thread holds after it."""
+        out = self._part_shape(SCALAR_SWEEP, part, 2)
+        return {"steps": out[0], "words": out[1]}
+
+    def scalar_probe(self, dev: int, part: str, seed: int = SCALAR_SEED, raw: bool = False):
+        """k_scalar_probe: one workgroup of 1,024 threads runs `part` and stores
+        every word it received: uint32 [words, 1024] (thread = 64 x wave +
+        lane). With `raw`, (that, the HW_REG_GPR_ALLOC word of every thread,
+        the HW_REG_HW_ID word of every thread): where each wave ran and which
+        SGPRs it was given, as the hardware reports them."""
+        import numpy as np
+
+        words = self.scalar_shape(part)["words"]
+        out = np.zeros((words + 2, SCALAR_BLOCK), np.uint32)
+        self._call("scalar_sweep", "scalar_probe", dev, self.scalar_parts().index(part), seed, out.ctypes.data,
+                   out.size)
+        return (out[:words], out[words], out[words + 1]) if raw else out[:words]
+
+    def scalar_sweep_expected(self, parts=None, seed: int = SCALAR_SEED) -> dict:
+        """The workgroup digest a healthy CU leaves per selected part, computed
+        on the host from the ISA's definitions."""
+        return self._part_expected(SCALAR_SWEEP, parts, seed)
+
+    def scalar_sweep_info(self, dev: int = 0) -> dict:
+        """What the runtime reports for k_scalar_sweep: `num_regs`,
+        `scratch_bytes` per lane, `lds_bytes` per workgroup, `blocks_per_cu`
+        (workgroups that fit on a CU at once)."""
+        return self._sweep_info("scalar_sweep", dev, ("num_regs", "scratch_bytes", "lds_bytes", "blocks_per_cu"))
+
+    def scalar_sweep(self, dev: int = 0, blocks: int = 0, parts=None, seed: int = SCALAR_SEED,
+                     inject: tuple | None = None, max_rounds: int = 4) -> dict:
+        """k_scalar_sweep: every selected part (None: all) of the scalar unit
+        run on every CU a workgroup lands on. `inject` = (xcd, cu key or None
+        for every CU of that XCD, [part names]): those workgroups flip one bit
+        of one received value of those parts (tests the comparator on a healthy
+        GPU). `blocks` 0: 4 per CU. It allocates nothing but its records.
+
+        Relaunched while some CU has not been seen, as cu_sweep does. Returns
+        {"records": [...], "summary": summarize_scalar_sweep(...) plus rounds,
+        ms, blocks, parts, seed}."""
+        return self._part_sweep(SCALAR_SWEEP, summarize_scalar_sweep, dev, blocks, parts, inject, max_rounds,
+                                (seed,), {"seed": seed}, tail=scalar_record_tail)
 
     # ----------------------------------------------------------- VALU sweep
     def valu_units(self) -> list[str]:
@@ -1311,6 +1397,22 @@ def summarize_mem_sweep(records: list[dict], compute_units: int, routes: list[st
     bits (`routes` names them in bit order): adds `failed_routes` per XCD and
     overall."""
     return _name_fail_bits(summarize_sweep(records, compute_units), MEM_SWEEP.summary_key, routes)
+
+
+def scalar_record_tail(w) -> dict:
+    """`gpr_alloc` of a k_scalar_sweep record: per SIMD, (OR, AND) of the raw
+    HW_REG_GPR_ALLOC words its waves read; (0, 0xffffffff) for a SIMD without a
+    wave. The register's layout on the MI355X is not the documented GFX9 one,
+    so nothing is derived from it (csrc/hip/scalar_sweep.hip)."""
+    c = w[SCALAR_COVER_WORD:SCALAR_COVER_WORD + 8]
+    return {"gpr_alloc": [(int(c[2 * q]), ~int(c[2 * q + 1]) & 0xFFFFFFFF) for q in range(4)]}
+
+
+def summarize_scalar_sweep(records: list[dict], compute_units: int, parts: list[str]) -> dict:
+    """summarize_sweep over k_scalar_sweep records, whose fail bits are part
+    bits (`parts` names them in bit order): adds `failed_parts` per XCD and
+    overall. There is no figure for the SGPR rows reached: see scalar_record_tail."""
+    return _name_fail_bits(summarize_sweep(records, compute_units), SCALAR_SWEEP.summary_key, parts)
 
 
 def summarize_valu_sweep(records: list[dict], compute_units: int, units: list[str]) -> dict:
