@@ -1,6 +1,6 @@
 """In-tree native build: the C++ scheduler core (`_xsched`) and the HIP/CDNA4
-probe kernels (`ops/_hipprobe`, the memory sweep's `ops/_hipmem` and the scalar
-sweep's `ops/_hipscalar`).
+probe kernels (`ops/_hipprobe`, the memory sweep's `ops/_hipmem`, the scalar
+sweep's `ops/_hipscalar` and the consensus sweep's `ops/_hipconsensus`).
 
 Both land next to the Python sources (not site-packages) so the built `.so`
 files travel with the repo snapshot to the MI355X box and show up as loaded
@@ -146,9 +146,11 @@ def build_hip(verbose: bool = True) -> Path | None:
     # _hipprobe.so is pinned symbol by symbol and does not grow with it.
     mem = [s for s in srcs if s.name == "mem_sweep.hip"]
     scalar = [s for s in srcs if s.name == "scalar_sweep.hip"]  # ops/_hipscalar.so, by the same rule
+    consensus = [s for s in srcs if s.name == "consensus_sweep.hip"]  # ops/_hipconsensus.so, likewise
     out = PKG / "ops" / "_hipprobe.so"
-    for lib, lib_srcs in ((out, [s for s in srcs if s not in mem + scalar]), (PKG / "ops" / "_hipmem.so", mem),
-                          (PKG / "ops" / "_hipscalar.so", scalar)):
+    for lib, lib_srcs in ((out, [s for s in srcs if s not in mem + scalar + consensus]),
+                          (PKG / "ops" / "_hipmem.so", mem), (PKG / "ops" / "_hipscalar.so", scalar),
+                          (PKG / "ops" / "_hipconsensus.so", consensus)):
         newest = max([s.stat().st_mtime for s in lib_srcs] + [_headers_mtime()])
         if lib.exists() and lib.stat().st_mtime >= newest:
             continue

@@ -352,7 +352,8 @@ def _part_list_flag(args, kind: str, parts: str) -> dict:
 def health_fn_args(args) -> dict:
     """hip_health_fn's keywords from the node-agent flags.
     --health-matrix-sweep, --health-lane-sweep, --health-valu-sweep,
-    --health-scalar-sweep, --health-mem-sweep: as _part_list_flag says, but the matrix keys are always there (False, None).
+    --health-scalar-sweep, --health-consensus-sweep, --health-mem-sweep: as _part_list_flag says, but the matrix keys
+    are always there (False, None).
     --health-hbm-sweep: absent -> no hbm keys, bare -> all free HBM less the
     reserve (hbm_gib None), else that many GiB.
     --health-register-sweep: absent -> no regfile key."""
@@ -364,7 +365,8 @@ def health_fn_args(args) -> dict:
     if getattr(args, "health_register_sweep", False):
         kw.update(regfile=True)
     kw.update(**_part_list_flag(args, "lane", "paths"), **_part_list_flag(args, "valu", "units"),
-              **_part_list_flag(args, "scalar", "parts"), **_part_list_flag(args, "mem", "routes"))
+              **_part_list_flag(args, "scalar", "parts"), **_part_list_flag(args, "consensus", "parts"),
+              **_part_list_flag(args, "mem", "routes"))
     return kw
 
 
@@ -579,6 +581,14 @@ def build_parser() -> argparse.ArgumentParser:
                         "and every SGPR a wave can name) run on every CU (a comma list selects some; default all); a bad "
                         "XCD is fenced like --health-sweep's and its parts are published as scalarFaults. Implies "
                         "--health-probe; independent of the other sweeps")
+    p.add_argument("--health-consensus-sweep", nargs="?", const="all", default=None, metavar="PARTS",
+                   help="health probe plus the consensus sweep: trans, div, sr, edge, ldsx, mfma and smfmac (raw "
+                        "transcendentals, division helpers, stochastic roundings, NaN payloads and saturation, the narrow "
+                        "transposed LDS reads and float LDS atomics, the MFMA shapes the matrix sweep leaves out and the "
+                        "sparse SMFMAC family) run on every CU (a comma list selects some; default all) and judged by a "
+                        "vote across the GPU's CUs, no document fixing their bits; the XCD of a CU that disagrees with "
+                        "the majority is fenced like --health-sweep's and its parts are published as consensusFaults. "
+                        "Implies --health-probe; independent of the other sweeps")
     p.add_argument("--health-mem-sweep", nargs="?", const="all", default=None, metavar="ROUTES",
                    help="health probe plus the memory-path sweep: gwidth, buffer, flat, atomic, l1, l2 and scalar (global, "
                         "buffer and flat loads and stores of every width, the memory-side atomics, the vector L1, the "

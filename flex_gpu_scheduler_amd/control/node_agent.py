@@ -19,7 +19,9 @@ exporter + metrics-server:
     and the register files it reads back wrong as `registerFaults` and the
     cross-lane and LDS paths it moves data wrongly through as `laneFaults`
     and the vector-ALU units it mis-computes as `valuFaults` and the parts
-    of the scalar unit it gets wrong as `scalarFaults` and the routes
+    of the scalar unit it gets wrong as `scalarFaults` and the parts of
+    the consensus sweep on which one of its CUs disagrees with the majority
+    of the GPU's CUs as `consensusFaults` and the routes
     between registers and HBM it corrupts data on as `memFaults`;
     a verdict that carries an HBM fault (the HBM sweep) withholds the whole
     GPU, partitioned or not, and is published as `hbmFaults`;
@@ -105,6 +107,12 @@ MEM_SWEEP_KIND = SweepKind("mem", "mem_sweep", "mem", "memSweep", "routes", "mem
 # records, so it has no "unswept" outcome.
 SCALAR_SWEEP_KIND = SweepKind("scalar", "scalar_sweep", "scalar", "scalarSweep", "parts", "scalarFaults",
                               lambda v: list(v["failed_parts"]))
+# The consensus sweep runs after the scalar sweep and before the memory sweep,
+# through the same code, and stands beside SWEEP_KINDS for the same reason. Its
+# reference is the majority of the GPU's own CUs: a part without a majority is
+# undecided, which is logged and is no verdict at all.
+CONSENSUS_SWEEP_KIND = SweepKind("consensus", "consensus_sweep", "consensus", "consensusSweep", "parts",
+                                 "consensusFaults", lambda v: list(v["failed_parts"]))
 
 FAULT_KINDS = {
     # What the per-CU sweeps found on a faulty XCD. Informational: the XCD is
@@ -120,6 +128,8 @@ FAULT_KINDS = {
     MEM_SWEEP_KIND.faults_key: FaultKind(per_xcd=False),
     # What the scalar sweep found on the GPU: {XCD id: [part, ...]}, likewise.
     SCALAR_SWEEP_KIND.faults_key: FaultKind(per_xcd=False),
+    # What the consensus sweep found on the GPU: {XCD id: [part, ...]}, likewise.
+    CONSENSUS_SWEEP_KIND.faults_key: FaultKind(per_xcd=False),
 }
 
 
@@ -466,18 +476,22 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
                   lane_args: dict | None = None, valu: bool = False, valu_units: list | None = None,
                   valu_args: dict | None = None, mem: bool = False, mem_routes: list | None = None,
                   mem_args: dict | None = None, scalar: bool = False, scalar_parts: list | None = None,
-                  scalar_args: dict | None = None) -> Callable[[int], "bool | GpuHealth"]:
+                  scalar_args: dict | None = None, consensus: bool = False, consensus_parts: list | None = None,
+                  consensus_args: dict | None = None) -> Callable[[int], "bool | GpuHealth"]:
     """Health callback backed by the HIP probes (HBM pattern + checksum and an
     MFMA tile check per GPU).
 
-    Each kind of SWEEP_KINDS, SCALAR_SWEEP_KIND and MEM_SWEEP_KIND, in the order they run, has a switch `<kind>` that
-    also runs that per-CU sweep of HipProbe (`sweep`: the CU sweep), `<kind>_args` for its keywords
+    Each kind of SWEEP_KINDS, SCALAR_SWEEP_KIND, CONSENSUS_SWEEP_KIND and MEM_SWEEP_KIND, in the order they run,
+    has a switch `<kind>` that also runs that per-CU sweep of HipProbe (`sweep`: the CU sweep), `<kind>_args` for its keywords
     and, where it sweeps named parts, `<kind>_<parts>` to select some (None for
     all). Its summary and, the CU sweep apart, its {xcd: fault} go into the
     verdict's detail under the kind's keys. A fault is the list of the failed
-    formats, paths, units, scalar parts or routes; of `regfile`, {"files": [...], "cells": n,
+    formats, paths, units, scalar parts, consensus parts or routes; of `regfile`, {"files": [...], "cells": n,
     "flipMask": "0x...", "simds": n}. The VALU sweep's failed steps are in
-    detail["valuSweep"]. The memory sweep holds an arena in HBM while it runs;
+    detail["valuSweep"]. The consensus sweep judges a CU by the vote of the
+    GPU's CUs; a part the vote could not decide (detail["consensusSweep"]["undecided"])
+    is logged at WARNING, fails nothing and touches no other sweep's verdict.
+    The memory sweep holds an arena in HBM while it runs;
     where that cannot be had the device is logged as unswept, which neither
     fails it nor touches the other sweeps' verdicts.
     The callback runs on every heartbeat, so the sweeps' verdict is reused for
@@ -505,7 +519,8 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
     # The enabled kinds, each with the keywords of its probe method.
     per_cu_sweeps = [(k, {**({k.selection: given[f"{k.enabled_by}_{k.selection}"]} if k.selection else {}),
                           **(given[f"{k.enabled_by}_args"] or {})})
-                     for k in SWEEP_KINDS + (SCALAR_SWEEP_KIND, MEM_SWEEP_KIND) if given[k.enabled_by]]
+                     for k in SWEEP_KINDS + (SCALAR_SWEEP_KIND, CONSENSUS_SWEEP_KIND, MEM_SWEEP_KIND)
+                     if given[k.enabled_by]]
 
     def sweep_verdict(dev: int):
         now = time.monotonic()
@@ -529,6 +544,9 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
                     {x: n for x, n in s["uncovered"].items() if n}, "bad_xcds" if fault_of is None else "faults", found)
             if s.get("failed_steps"):
                 log.warning("%s sweep GPU %d: failed steps %s", k.label, dev, s["failed_steps"])
+            if s.get("undecided"):
+                log.warning("%s sweep GPU %d: no majority for %s: undecided, nothing failed for it", k.label, dev,
+                            s["undecided"])
             bad |= set(s["bad_xcds"])
             detail[k.summary_key] = s
             if k.faults_key:

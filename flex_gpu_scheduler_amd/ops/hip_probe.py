@@ -25,10 +25,17 @@ Sweeps of every CU (csrc/hip/<name>.hip), each naming the XCD of a CU that fails
     It is a library of its own, _hipmem.so;
   * scalar_sweep: every CU's scalar ALU (arithmetic, logic, bit, compare,
     branch, EXEC-mask and relative-move instructions) and the SGPRs a wave
-    can name; names the parts. It is a library of its own, _hipscalar.so.
+    can name; names the parts. It is a library of its own, _hipscalar.so;
+  * consensus_sweep: the instructions whose bits no document fixes (raw
+    transcendentals, division helpers, stochastic roundings, NaN payloads and
+    saturation, the narrow transposed LDS reads and float LDS atomics, the
+    MFMA shapes the matrix sweep leaves out and the sparse SMFMAC family),
+    judged not against the host but by a vote across the CUs of the GPU
+    (vote_consensus); names the parts. A library of its own, _hipconsensus.so.
 The matrix, lane, VALU and memory sweeps are sweeps over named parts:
 PART_SWEEPS describes each, and one implementation serves the four and the
-scalar sweep, whose row SCALAR_SWEEP stands beside the table.
+scalar sweep, whose row SCALAR_SWEEP stands beside the table, as does
+CONSENSUS_SWEEP, the consensus sweep's.
 
 hbm_sweep (csrc/hip/hbm_sweep.hip): all free HBM under an address-keyed
 pattern in both polarities; names the vectors and bits that read back wrong.
@@ -46,6 +53,8 @@ _LIB = Path(__file__).resolve().parent / "_hipprobe.so"
 _MEM_LIB = Path(__file__).resolve().parent / "_hipmem.so"
 # So is the scalar sweep.
 _SCALAR_LIB = Path(__file__).resolve().parent / "_hipscalar.so"
+# And the consensus sweep.
+_CONSENSUS_LIB = Path(__file__).resolve().parent / "_hipconsensus.so"
 MODES = {"read": 0, "write": 1, "copy": 2, "triad": 3}
 
 
@@ -142,6 +151,17 @@ SCALAR_COVER_WORD = 22  # the first of the eight coverage words
 SCALAR_SYMBOLS = ("xs_scalar_sweep_last_error", "xs_scalar_parts", "xs_scalar_shape", "xs_scalar_probe",
                   "xs_scalar_sweep_expected", "xs_scalar_sweep_info", "xs_scalar_sweep")
 
+# k_consensus_sweep (csrc/hip/consensus_sweep.hip): one 128-byte record per
+# workgroup, {xcd, cu, simd_mask, fail = 0, 7 digests, 0 x 21}. The device does
+# not judge; vote_consensus does.
+CONSENSUS_RECORD_WORDS = 32
+CONSENSUS_SEED = 0x1B873593
+CONSENSUS_ROUNDS = 4  # operand sets per step; measured in profiles/consensus_sweep_defaults.md
+CONSENSUS_BLOCK = 256
+# The C ABI of _hipconsensus.so.
+CONSENSUS_SYMBOLS = ("xs_consensus_sweep_last_error", "xs_consensus_parts", "xs_consensus_shape",
+                     "xs_consensus_probe", "xs_consensus_operands", "xs_consensus_sweep_info", "xs_consensus_sweep")
+
 
 @dataclass(frozen=True)
 class PartSweep:
@@ -176,6 +196,9 @@ MATRIX_SWEEP, LANE_SWEEP, VALU_SWEEP, MEM_SWEEP = PART_SWEEPS.values()
 # The scalar sweep's row stands beside the table: same record head as the lane sweep's.
 SCALAR_SWEEP = PartSweep("scalar", "xs_scalar_parts", "scalar part", "failed_parts", "parts", 32,
                          digests=12, bad=4, bad_simds=20)
+# So does the consensus sweep's: a record is the four head words and the digests.
+CONSENSUS_SWEEP = PartSweep("consensus", "xs_consensus_parts", "consensus part", "failed_parts", "parts",
+                            CONSENSUS_RECORD_WORDS, digests=4)
 
 # k_hbm_fill / k_hbm_verify (csrc/hip/hbm_sweep.hip)
 HBM_SWEEP_SEED = 0x5EED1E55
@@ -289,8 +312,8 @@ def decode_part_record(kind: PartSweep, names: list[str], w, expected: dict, ste
 
 class HipProbe:
     def __init__(self, path: str | Path = _LIB, mem_path: str | Path = _MEM_LIB,
-                 scalar_path: str | Path = _SCALAR_LIB):
-        for built in (path, mem_path, scalar_path):
+                 scalar_path: str | Path = _SCALAR_LIB, consensus_path: str | Path = _CONSENSUS_LIB):
+        for built in (path, mem_path, scalar_path, consensus_path):
             if not Path(built).exists():
                 raise ProbeError(f"{built} not built; run `python -m flex_gpu_scheduler_amd.build_ext --hip`")
         try:
@@ -418,6 +441,20 @@ class HipProbe:
                                       ctypes.POINTER(ctypes.c_double)]
         for name in SCALAR_SYMBOLS:
             setattr(L, name, getattr(S, name))
+        # consensus_sweep.hip's library, likewise.
+        self.consensus_lib = ctypes.CDLL(str(consensus_path))
+        C = self.consensus_lib
+        C.xs_consensus_sweep_last_error.restype = ctypes.c_char_p
+        C.xs_consensus_parts.restype = ctypes.c_char_p
+        C.xs_consensus_shape.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        C.xs_consensus_probe.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]
+        C.xs_consensus_operands.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]
+        C.xs_consensus_sweep_info.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        C.xs_consensus_sweep.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                         ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p,
+                                         ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]
+        for name in CONSENSUS_SYMBOLS:
+            setattr(L, name, getattr(C, name))
         L.xs_hbm_sweep_last_error.restype = ctypes.c_char_p
         L.xs_hbm_sweep_pattern.argtypes = [ctypes.c_uint64, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int,
                                            ctypes.c_void_p]
@@ -1131,6 +1168,81 @@ class HipProbe:
         return self._part_sweep(SCALAR_SWEEP, summarize_scalar_sweep, dev, blocks, parts, inject, max_rounds,
                                 (seed,), {"seed": seed}, tail=scalar_record_tail)
 
+    # ------------------------------------------------------ consensus sweep
+    def consensus_parts(self) -> list[str]:
+        """Part names of the consensus sweep; the index is the part's bit."""
+        return self._part_names(CONSENSUS_SWEEP)
+
+    def consensus_shape(self, part: str) -> dict:
+        """`steps` of one part, the result `words` every thread gets per round
+        and the `operand_words` it is given per round."""
+        out = self._part_shape(CONSENSUS_SWEEP, part, 3)
+        return {"steps": out[0], "words": out[1], "operand_words": out[2]}
+
+    def consensus_operands(self, part: str, seed: int = CONSENSUS_SEED, rounds: int = CONSENSUS_ROUNDS):
+        """The operand words of one workgroup, computed on the host: uint32
+        [rounds, operand_words, 256], per step the words of operand 0, then 1,
+        2 and 3, in the step table's order. No device call."""
+        import numpy as np
+
+        out = np.zeros((max(int(rounds), 0), self.consensus_shape(part)["operand_words"], CONSENSUS_BLOCK), np.uint32)
+        self._call("consensus_sweep", "consensus_operands", self.consensus_parts().index(part), seed, out.ctypes.data,
+                   out.size)
+        return out
+
+    def consensus_probe(self, dev: int, part: str, seed: int = CONSENSUS_SEED, rounds: int = CONSENSUS_ROUNDS):
+        """k_consensus_probe: one workgroup runs `part` and stores every word
+        it received: uint32 [rounds, words, 256] (thread = 64 x wave + lane)."""
+        import numpy as np
+
+        out = np.zeros((max(int(rounds), 0), self.consensus_shape(part)["words"], CONSENSUS_BLOCK), np.uint32)
+        self._call("consensus_sweep", "consensus_probe", dev, self.consensus_parts().index(part), seed,
+                   out.ctypes.data, out.size)
+        return out
+
+    def consensus_sweep_info(self, dev: int = 0) -> dict:
+        """What the runtime reports for k_consensus_sweep: `num_regs`,
+        `scratch_bytes` per lane, `lds_bytes` per workgroup and `blocks_per_cu`
+        (workgroups that fit on a CU at once)."""
+        return self._sweep_info("consensus_sweep", dev, ("num_regs", "scratch_bytes", "lds_bytes", "blocks_per_cu"))
+
+    def consensus_sweep(self, dev: int = 0, parts=None, blocks: int = 0, seed: int = CONSENSUS_SEED,
+                        rounds: int = CONSENSUS_ROUNDS, inject: tuple | None = None, inject_parts=None,
+                        max_rounds: int = 4) -> dict:
+        """k_consensus_sweep: every selected part (None: all) runs `rounds`
+        operand sets per step on every CU a workgroup lands on and leaves one
+        digest per part; the device judges nothing. The verdict is the vote of
+        vote_consensus: a CU fails a part when its records disagree among
+        themselves or with the digest that more than half of the CUs hold.
+        `inject` = (xcd, cu key or None for every CU of that XCD[, part
+        names]) with `inject_parts` (default: the names in `inject`, else all
+        selected): those workgroups flip one bit of one result of those parts
+        (tests the vote on a healthy GPU). `blocks` 0: 4 per CU.
+
+        Relaunched (at most `max_rounds` launches) while some CU has not been
+        seen, as cu_sweep does. Returns {"records": [...], "summary":
+        summarize_consensus_sweep(...) plus rounds (launches), ms, blocks,
+        parts, operand_rounds, seed}."""
+        kind = CONSENSUS_SWEEP
+        names = self._part_names(kind)
+        mask = self._part_mask(kind, parts)
+        selected = [f for i, f in enumerate(names) if mask >> i & 1]
+        ix, ic = _inject_target(inject)
+        if inject is None:
+            im = 0
+        else:
+            chosen = inject_parts if inject_parts is not None else inject[2] if len(inject) > 2 else selected
+            im = self._part_mask(kind, chosen)
+        out = self._sweep_until_covered(
+            "consensus_sweep", dev, blocks, max_rounds, kind.record_words,
+            lambda nb, *out: self.lib.xs_consensus_sweep(dev, nb, mask, seed, rounds, ix, ic, im, *out),
+            lambda: {},  # no host digests: the vote is the reference
+            lambda w, _: {"xcd": w[0], "cu": w[1], "simd_mask": w[2], "fail": w[3],
+                          "digests": dict(zip(names, w[kind.digests:kind.digests + len(names)]))},
+            lambda records, cus: summarize_consensus_sweep(records, cus, names, selected))
+        out["summary"].update(seed=seed, parts=selected, operand_rounds=rounds)
+        return out
+
     # ----------------------------------------------------------- VALU sweep
     def valu_units(self) -> list[str]:
         """Unit names of the VALU sweep; the index is the unit's bit."""
@@ -1413,6 +1525,62 @@ def summarize_scalar_sweep(records: list[dict], compute_units: int, parts: list[
     bits (`parts` names them in bit order): adds `failed_parts` per XCD and
     overall. There is no figure for the SGPR rows reached: see scalar_record_tail."""
     return _name_fail_bits(summarize_sweep(records, compute_units), SCALAR_SWEEP.summary_key, parts)
+
+
+def vote_consensus(records: list[dict], parts: list[str]) -> dict:
+    """The vote over k_consensus_sweep records ({"xcd", "cu", "digests": {part:
+    digest}, ...}; a CU may appear many times) on the selected `parts`. Per part:
+    a CU votes once, with the digest all its records share; a CU whose records
+    disagree casts no vote and fails the part. The consensus is the digest held
+    by strictly more than half of the CUs seen (those without a vote count in
+    the denominator); a CU that does not hold it fails the part. With fewer
+    than 3 CUs seen or no strict majority the part is undecided and nobody
+    fails it. A part outside `parts` is never judged.
+
+    Returns {"fail": one word of fail bits per record, in order (bit = the
+    part's position in the record's digests), "consensus": {part: "0x..."} of
+    the decided parts, "undecided": [part, ...]}. Nothing is changed in place."""
+    fail = [0] * len(records)
+    by_cu: dict[tuple[int, int], list[int]] = {}
+    for i, r in enumerate(records):
+        by_cu.setdefault((int(r["xcd"]), int(r["cu"])), []).append(i)
+    consensus: dict[str, str] = {}
+    undecided: list[str] = []
+    for part in parts:
+        votes: dict[tuple[int, int], int | None] = {}
+        for cu, rows in by_cu.items():
+            held = {int(records[i]["digests"][part]) for i in rows}
+            votes[cu] = held.pop() if len(held) == 1 else None
+        count: dict[int, int] = {}
+        for v in votes.values():
+            if v is not None:
+                count[v] = count.get(v, 0) + 1
+        top = max(count, key=count.get) if count else None
+        if len(votes) < 3 or top is None or 2 * count[top] <= len(votes):
+            undecided.append(part)
+            continue
+        consensus[part] = f"0x{top:08x}"
+        for cu, v in votes.items():
+            if v != top:
+                for i in by_cu[cu]:
+                    fail[i] |= 1 << list(records[i]["digests"]).index(part)
+    return {"fail": fail, "consensus": consensus, "undecided": undecided}
+
+
+def summarize_consensus_sweep(records: list[dict], compute_units: int, names: list[str],
+                              parts: list[str] | None = None) -> dict:
+    """The verdict of a consensus sweep: vote_consensus over the selected
+    `parts` (None: all of `names`, the parts in bit order) writes every
+    record's `fail` bits, the device having left them 0; then summarize_sweep
+    and the part names, as for the other sweeps over named parts: `failed_parts`
+    per XCD and overall, `bad_xcds`, `covered`, `uncovered`. Adds `consensus`
+    ({part: "0x..."}, to compare GPUs and nodes by) and `undecided`."""
+    vote = vote_consensus(records, list(names) if parts is None else parts)
+    for r, bits in zip(records, vote["fail"]):
+        r["fail"] = bits
+    s = _name_fail_bits(summarize_sweep(records, compute_units), CONSENSUS_SWEEP.summary_key, names)
+    s.update(consensus=vote["consensus"], undecided=vote["undecided"])
+    return s
 
 
 def summarize_valu_sweep(records: list[dict], compute_units: int, units: list[str]) -> dict:
