@@ -1,6 +1,7 @@
 """In-tree native build: the C++ scheduler core (`_xsched`) and the HIP/CDNA4
 probe kernels (`ops/_hipprobe`, the memory sweep's `ops/_hipmem`, the scalar
-sweep's `ops/_hipscalar` and the consensus sweep's `ops/_hipconsensus`).
+sweep's `ops/_hipscalar`, the consensus sweep's `ops/_hipconsensus` and the
+fetch sweep's `ops/_hipfetch`).
 
 Both land next to the Python sources (not site-packages) so the built `.so`
 files travel with the repo snapshot to the MI355X box and show up as loaded
@@ -147,10 +148,11 @@ def build_hip(verbose: bool = True) -> Path | None:
     mem = [s for s in srcs if s.name == "mem_sweep.hip"]
     scalar = [s for s in srcs if s.name == "scalar_sweep.hip"]  # ops/_hipscalar.so, by the same rule
     consensus = [s for s in srcs if s.name == "consensus_sweep.hip"]  # ops/_hipconsensus.so, likewise
+    fetch = [s for s in srcs if s.name == "fetch_sweep.hip"]  # ops/_hipfetch.so, likewise
     out = PKG / "ops" / "_hipprobe.so"
-    for lib, lib_srcs in ((out, [s for s in srcs if s not in mem + scalar + consensus]),
+    for lib, lib_srcs in ((out, [s for s in srcs if s not in mem + scalar + consensus + fetch]),
                           (PKG / "ops" / "_hipmem.so", mem), (PKG / "ops" / "_hipscalar.so", scalar),
-                          (PKG / "ops" / "_hipconsensus.so", consensus)):
+                          (PKG / "ops" / "_hipconsensus.so", consensus), (PKG / "ops" / "_hipfetch.so", fetch)):
         newest = max([s.stat().st_mtime for s in lib_srcs] + [_headers_mtime()])
         if lib.exists() and lib.stat().st_mtime >= newest:
             continue

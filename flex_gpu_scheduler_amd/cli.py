@@ -352,7 +352,8 @@ def _part_list_flag(args, kind: str, parts: str) -> dict:
 def health_fn_args(args) -> dict:
     """hip_health_fn's keywords from the node-agent flags.
     --health-matrix-sweep, --health-lane-sweep, --health-valu-sweep,
-    --health-scalar-sweep, --health-consensus-sweep, --health-mem-sweep: as _part_list_flag says, but the matrix keys
+    --health-scalar-sweep, --health-consensus-sweep, --health-fetch-sweep, --health-mem-sweep: as _part_list_flag
+    says, but the matrix keys
     are always there (False, None).
     --health-hbm-sweep: absent -> no hbm keys, bare -> all free HBM less the
     reserve (hbm_gib None), else that many GiB.
@@ -366,6 +367,7 @@ def health_fn_args(args) -> dict:
         kw.update(regfile=True)
     kw.update(**_part_list_flag(args, "lane", "paths"), **_part_list_flag(args, "valu", "units"),
               **_part_list_flag(args, "scalar", "parts"), **_part_list_flag(args, "consensus", "parts"),
+              **_part_list_flag(args, "fetch", "parts"),
               **_part_list_flag(args, "mem", "routes"))
     return kw
 
@@ -589,6 +591,13 @@ def build_parser() -> argparse.ArgumentParser:
                         "vote across the GPU's CUs, no document fixing their bits; the XCD of a CU that disagrees with "
                         "the majority is fenced like --health-sweep's and its parts are published as consensusFaults. "
                         "Implies --health-probe; independent of the other sweeps")
+    p.add_argument("--health-fetch-sweep", nargs="?", const="all", default=None, metavar="PARTS",
+                   help="health probe plus the fetch sweep: stream, loop, call, align and refill (256 KiB of straight-line "
+                        "code, counted backward loops, computed jumps and calls, jump targets at every dword of a cache "
+                        "line and across a page, a refetch after an instruction-cache invalidate; the test data are the "
+                        "literals in the sweep's own code) run on every CU (a comma list selects some; default all); a "
+                        "bad XCD is fenced like --health-sweep's and its parts are published as fetchFaults. Implies "
+                        "--health-probe; independent of the other sweeps")
     p.add_argument("--health-mem-sweep", nargs="?", const="all", default=None, metavar="ROUTES",
                    help="health probe plus the memory-path sweep: gwidth, buffer, flat, atomic, l1, l2 and scalar (global, "
                         "buffer and flat loads and stores of every width, the memory-side atomics, the vector L1, the "

@@ -21,7 +21,8 @@ exporter + metrics-server:
     and the vector-ALU units it mis-computes as `valuFaults` and the parts
     of the scalar unit it gets wrong as `scalarFaults` and the parts of
     the consensus sweep on which one of its CUs disagrees with the majority
-    of the GPU's CUs as `consensusFaults` and the routes
+    of the GPU's CUs as `consensusFaults` and the parts of the fetch
+    sweep (its own code, fetched wrongly) as `fetchFaults` and the routes
     between registers and HBM it corrupts data on as `memFaults`;
     a verdict that carries an HBM fault (the HBM sweep) withholds the whole
     GPU, partitioned or not, and is published as `hbmFaults`;
@@ -113,6 +114,11 @@ SCALAR_SWEEP_KIND = SweepKind("scalar", "scalar_sweep", "scalar", "scalarSweep",
 # undecided, which is logged and is no verdict at all.
 CONSENSUS_SWEEP_KIND = SweepKind("consensus", "consensus_sweep", "consensus", "consensusSweep", "parts",
                                  "consensusFaults", lambda v: list(v["failed_parts"]))
+# The fetch sweep runs after the consensus sweep and before the memory sweep,
+# through the same code, and stands beside SWEEP_KINDS for the same reason. It
+# allocates nothing but its records, so it has no "unswept" outcome.
+FETCH_SWEEP_KIND = SweepKind("fetch", "fetch_sweep", "fetch", "fetchSweep", "parts", "fetchFaults",
+                             lambda v: list(v["failed_parts"]))
 
 FAULT_KINDS = {
     # What the per-CU sweeps found on a faulty XCD. Informational: the XCD is
@@ -130,6 +136,8 @@ FAULT_KINDS = {
     SCALAR_SWEEP_KIND.faults_key: FaultKind(per_xcd=False),
     # What the consensus sweep found on the GPU: {XCD id: [part, ...]}, likewise.
     CONSENSUS_SWEEP_KIND.faults_key: FaultKind(per_xcd=False),
+    # What the fetch sweep found on the GPU: {XCD id: [part, ...]}, likewise.
+    FETCH_SWEEP_KIND.faults_key: FaultKind(per_xcd=False),
 }
 
 
@@ -477,16 +485,18 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
                   valu_args: dict | None = None, mem: bool = False, mem_routes: list | None = None,
                   mem_args: dict | None = None, scalar: bool = False, scalar_parts: list | None = None,
                   scalar_args: dict | None = None, consensus: bool = False, consensus_parts: list | None = None,
-                  consensus_args: dict | None = None) -> Callable[[int], "bool | GpuHealth"]:
+                  consensus_args: dict | None = None, fetch: bool = False, fetch_parts: list | None = None,
+                  fetch_args: dict | None = None) -> Callable[[int], "bool | GpuHealth"]:
     """Health callback backed by the HIP probes (HBM pattern + checksum and an
     MFMA tile check per GPU).
 
-    Each kind of SWEEP_KINDS, SCALAR_SWEEP_KIND, CONSENSUS_SWEEP_KIND and MEM_SWEEP_KIND, in the order they run,
+    Each kind of SWEEP_KINDS, SCALAR_SWEEP_KIND, CONSENSUS_SWEEP_KIND, FETCH_SWEEP_KIND and MEM_SWEEP_KIND, in the
+    order they run,
     has a switch `<kind>` that also runs that per-CU sweep of HipProbe (`sweep`: the CU sweep), `<kind>_args` for its keywords
     and, where it sweeps named parts, `<kind>_<parts>` to select some (None for
     all). Its summary and, the CU sweep apart, its {xcd: fault} go into the
     verdict's detail under the kind's keys. A fault is the list of the failed
-    formats, paths, units, scalar parts, consensus parts or routes; of `regfile`, {"files": [...], "cells": n,
+    formats, paths, units, scalar parts, consensus parts, fetch parts or routes; of `regfile`, {"files": [...], "cells": n,
     "flipMask": "0x...", "simds": n}. The VALU sweep's failed steps are in
     detail["valuSweep"]. The consensus sweep judges a CU by the vote of the
     GPU's CUs; a part the vote could not decide (detail["consensusSweep"]["undecided"])
@@ -519,7 +529,7 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
     # The enabled kinds, each with the keywords of its probe method.
     per_cu_sweeps = [(k, {**({k.selection: given[f"{k.enabled_by}_{k.selection}"]} if k.selection else {}),
                           **(given[f"{k.enabled_by}_args"] or {})})
-                     for k in SWEEP_KINDS + (SCALAR_SWEEP_KIND, CONSENSUS_SWEEP_KIND, MEM_SWEEP_KIND)
+                     for k in SWEEP_KINDS + (SCALAR_SWEEP_KIND, CONSENSUS_SWEEP_KIND, FETCH_SWEEP_KIND, MEM_SWEEP_KIND)
                      if given[k.enabled_by]]
 
     def sweep_verdict(dev: int):

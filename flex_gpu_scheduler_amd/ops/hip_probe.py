@@ -31,11 +31,16 @@ Sweeps of every CU (csrc/hip/<name>.hip), each naming the XCD of a CU that fails
     saturation, the narrow transposed LDS reads and float LDS atomics, the
     MFMA shapes the matrix sweep leaves out and the sparse SMFMAC family),
     judged not against the host but by a vote across the CUs of the GPU
-    (vote_consensus); names the parts. A library of its own, _hipconsensus.so.
+    (vote_consensus); names the parts. A library of its own, _hipconsensus.so;
+  * fetch_sweep: every CU's instruction fetch path and instruction cache
+    (256 KiB of straight-line code, counted backward loops, computed jumps
+    and calls, jump targets at every dword of a cache line and across a page,
+    a refetch after s_icache_inv), the test data being the literals in the
+    sweep's own code; names the parts. A library of its own, _hipfetch.so.
 The matrix, lane, VALU and memory sweeps are sweeps over named parts:
 PART_SWEEPS describes each, and one implementation serves the four and the
-scalar sweep, whose row SCALAR_SWEEP stands beside the table, as does
-CONSENSUS_SWEEP, the consensus sweep's.
+scalar sweep, whose row SCALAR_SWEEP stands beside the table, as do
+CONSENSUS_SWEEP, the consensus sweep's, and FETCH_SWEEP, the fetch sweep's.
 
 hbm_sweep (csrc/hip/hbm_sweep.hip): all free HBM under an address-keyed
 pattern in both polarities; names the vectors and bits that read back wrong.
@@ -55,6 +60,8 @@ _MEM_LIB = Path(__file__).resolve().parent / "_hipmem.so"
 _SCALAR_LIB = Path(__file__).resolve().parent / "_hipscalar.so"
 # And the consensus sweep.
 _CONSENSUS_LIB = Path(__file__).resolve().parent / "_hipconsensus.so"
+# And the fetch sweep.
+_FETCH_LIB = Path(__file__).resolve().parent / "_hipfetch.so"
 MODES = {"read": 0, "write": 1, "copy": 2, "triad": 3}
 
 
@@ -162,6 +169,18 @@ CONSENSUS_BLOCK = 256
 CONSENSUS_SYMBOLS = ("xs_consensus_sweep_last_error", "xs_consensus_parts", "xs_consensus_shape",
                      "xs_consensus_probe", "xs_consensus_operands", "xs_consensus_sweep_info", "xs_consensus_sweep")
 
+# k_fetch_sweep (csrc/hip/fetch_sweep.hip): one 128-byte record per workgroup,
+# {xcd, cu, simd_mask, fail, 5 bad counts, 5 digests, bad_simds, 0 x 17}. The
+# device holds no expected words: `bad` counts an injection only.
+FETCH_RECORD_WORDS = 32
+FETCH_SEED = 0x1B873593
+FETCH_ROUNDS = 2  # multiplies the loop trips and the call rounds; measured in profiles/fetch_sweep_defaults.md
+FETCH_BLOCK = 256
+FETCH_SEGMENTS = 32  # of 8 KiB: the rows of fetch_probe_clocks
+# The C ABI of _hipfetch.so.
+FETCH_SYMBOLS = ("xs_fetch_sweep_last_error", "xs_fetch_parts", "xs_fetch_shape", "xs_fetch_probe",
+                 "xs_fetch_sweep_expected", "xs_fetch_sweep_info", "xs_fetch_sweep")
+
 
 @dataclass(frozen=True)
 class PartSweep:
@@ -199,6 +218,9 @@ SCALAR_SWEEP = PartSweep("scalar", "xs_scalar_parts", "scalar part", "failed_par
 # So does the consensus sweep's: a record is the four head words and the digests.
 CONSENSUS_SWEEP = PartSweep("consensus", "xs_consensus_parts", "consensus part", "failed_parts", "parts",
                             CONSENSUS_RECORD_WORDS, digests=4)
+# And the fetch sweep's: the lane sweep's head with five parts.
+FETCH_SWEEP = PartSweep("fetch", "xs_fetch_parts", "fetch part", "failed_parts", "parts", FETCH_RECORD_WORDS,
+                        digests=9, bad=4, bad_simds=14)
 
 # k_hbm_fill / k_hbm_verify (csrc/hip/hbm_sweep.hip)
 HBM_SWEEP_SEED = 0x5EED1E55
@@ -312,8 +334,9 @@ def decode_part_record(kind: PartSweep, names: list[str], w, expected: dict, ste
 
 class HipProbe:
     def __init__(self, path: str | Path = _LIB, mem_path: str | Path = _MEM_LIB,
-                 scalar_path: str | Path = _SCALAR_LIB, consensus_path: str | Path = _CONSENSUS_LIB):
-        for built in (path, mem_path, scalar_path, consensus_path):
+                 scalar_path: str | Path = _SCALAR_LIB, consensus_path: str | Path = _CONSENSUS_LIB,
+                 fetch_path: str | Path = _FETCH_LIB):
+        for built in (path, mem_path, scalar_path, consensus_path, fetch_path):
             if not Path(built).exists():
                 raise ProbeError(f"{built} not built; run `python -m flex_gpu_scheduler_amd.build_ext --hip`")
         try:
@@ -455,6 +478,22 @@ class HipProbe:
                                          ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]
         for name in CONSENSUS_SYMBOLS:
             setattr(L, name, getattr(C, name))
+        # fetch_sweep.hip's library, likewise.
+        self.fetch_lib = ctypes.CDLL(str(fetch_path))
+        F = self.fetch_lib
+        F.xs_fetch_sweep_last_error.restype = ctypes.c_char_p
+        F.xs_fetch_parts.restype = ctypes.c_char_p
+        F.xs_fetch_shape.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        F.xs_fetch_probe.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                     ctypes.c_size_t]
+        F.xs_fetch_sweep_expected.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                              ctypes.POINTER(ctypes.c_uint32)]
+        F.xs_fetch_sweep_info.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        F.xs_fetch_sweep.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                     ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p,
+                                     ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]
+        for name in FETCH_SYMBOLS:
+            setattr(L, name, getattr(F, name))
         L.xs_hbm_sweep_last_error.restype = ctypes.c_char_p
         L.xs_hbm_sweep_pattern.argtypes = [ctypes.c_uint64, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int,
                                            ctypes.c_void_p]
@@ -1243,6 +1282,74 @@ class HipProbe:
         out["summary"].update(seed=seed, parts=selected, operand_rounds=rounds)
         return out
 
+    # ---------------------------------------------------------- fetch sweep
+    def fetch_parts(self) -> list[str]:
+        """Part names of the fetch sweep; the index is the part's bit."""
+        return self._part_names(FETCH_SWEEP)
+
+    def fetch_shape(self, part: str, rounds: int = FETCH_ROUNDS) -> dict:
+        """`rows` of 256 words one part hands over at `rounds`: `fixed_rows`
+        whatever the rounds plus `rows_per_round` for each."""
+        out = self._part_shape(FETCH_SWEEP, part, 2)
+        return {"fixed_rows": out[0], "rows_per_round": out[1], "rows": out[0] + out[1] * max(int(rounds), 0)}
+
+    def fetch_probe(self, dev: int, parts=None, seed: int = FETCH_SEED, rounds: int = FETCH_ROUNDS) -> dict:
+        """k_fetch_probe: one workgroup runs the selected parts (one name,
+        several, None: all) in one launch and stores every word it hands over:
+        {part: uint32 [rows, 256]} (thread = 64 x wave + lane)."""
+        import numpy as np
+
+        names = self.fetch_parts()
+        mask = self._part_mask(FETCH_SWEEP, parts)
+        selected = [f for i, f in enumerate(names) if mask >> i & 1]
+        rows = [self.fetch_shape(f, rounds)["rows"] for f in selected]
+        out = np.zeros((sum(rows), FETCH_BLOCK), np.uint32)
+        self._call("fetch_sweep", "fetch_probe", dev, mask, seed, rounds, out.ctypes.data, out.size)
+        ends = np.cumsum(rows)
+        return {f: out[e - n:e] for f, n, e in zip(selected, rows, ends)}
+
+    def fetch_probe_clocks(self, dev: int, repeats: int = 8):
+        """k_fetch_probe's timing mode: for k = 1..32 one workgroup calls the
+        stream segments 0..k-1 (8 k KiB of code) once untimed and `repeats`
+        times between two s_memtime reads. Returns float64 [32, 256]: every
+        thread's clocks per byte of code at each footprint."""
+        import numpy as np
+
+        out = np.zeros((FETCH_SEGMENTS, FETCH_BLOCK), np.uint32)
+        self._call("fetch_sweep", "fetch_probe", dev, 1 << len(self.fetch_parts()), 0, repeats, out.ctypes.data,
+                   out.size)
+        nbytes = 8192.0 * repeats * np.arange(1, FETCH_SEGMENTS + 1)
+        return out / nbytes[:, None]
+
+    def fetch_sweep_expected(self, parts=None, seed: int = FETCH_SEED, rounds: int = FETCH_ROUNDS) -> dict:
+        """The workgroup digest a healthy CU leaves per selected part, computed
+        on the host from the region and step tables."""
+        return self._part_expected(FETCH_SWEEP, parts, seed, rounds)
+
+    def fetch_sweep_info(self, dev: int = 0) -> dict:
+        """What the runtime reports for k_fetch_sweep: `num_regs`,
+        `scratch_bytes` per lane, `lds_bytes` per workgroup, `blocks_per_cu`
+        (workgroups that fit on a CU at once)."""
+        return self._sweep_info("fetch_sweep", dev, ("num_regs", "scratch_bytes", "lds_bytes", "blocks_per_cu"))
+
+    def fetch_sweep(self, dev: int = 0, blocks: int = 0, parts=None, seed: int = FETCH_SEED,
+                    rounds: int = FETCH_ROUNDS, inject: tuple | None = None, max_rounds: int = 4) -> dict:
+        """k_fetch_sweep: every selected part (None: all) of the instruction
+        fetch path run on every CU a workgroup lands on; `rounds` multiplies
+        the loop trips and the call rounds. `inject` = (xcd, cu key or None for
+        every CU of that XCD, [part names]): those workgroups flip one bit of
+        one word of those parts (tests the comparator on a healthy GPU).
+        `blocks` 0: 4 per CU. It allocates nothing but its records.
+
+        Relaunched (at most `max_rounds` launches) while some CU has not been
+        seen, as cu_sweep does. Returns {"records": [...], "summary":
+        summarize_fetch_sweep(...) plus rounds (launches), ms, blocks, parts,
+        code_rounds, seed}."""
+        out = self._part_sweep(FETCH_SWEEP, summarize_fetch_sweep, dev, blocks, parts, inject, max_rounds,
+                               (seed, rounds), {"seed": seed})
+        out["summary"].update(code_rounds=rounds)
+        return out
+
     # ----------------------------------------------------------- VALU sweep
     def valu_units(self) -> list[str]:
         """Unit names of the VALU sweep; the index is the unit's bit."""
@@ -1525,6 +1632,14 @@ def summarize_scalar_sweep(records: list[dict], compute_units: int, parts: list[
     bits (`parts` names them in bit order): adds `failed_parts` per XCD and
     overall. There is no figure for the SGPR rows reached: see scalar_record_tail."""
     return _name_fail_bits(summarize_sweep(records, compute_units), SCALAR_SWEEP.summary_key, parts)
+
+
+def summarize_fetch_sweep(records: list[dict], compute_units: int, parts: list[str]) -> dict:
+    """summarize_sweep over k_fetch_sweep records, whose fail bits are part
+    bits (`parts` names them in bit order): adds `failed_parts` per XCD and
+    overall. The record names the CU that ran, not the neighbour that shares
+    its instruction cache."""
+    return _name_fail_bits(summarize_sweep(records, compute_units), FETCH_SWEEP.summary_key, parts)
 
 
 def vote_consensus(records: list[dict], parts: list[str]) -> dict:
