@@ -69,6 +69,27 @@ class AmdSmiSampler:
         self._clock = clock
         self._prev: dict[int, tuple[float, int]] = {}
 
+    def _stamps(self) -> list[int]:
+        return [int(d.get("firmware_timestamp_10ns") or 0) for d in self._read()]
+
+    def wait_refresh(self, timeout: float = 2.0, period: float = 0.01) -> bool:
+        """Blocks until every GPU's firmware has published a metrics table
+        newer than the one readable now, so the next sample() reflects load
+        as it is at the time of the call. The table is a snapshot, and hosts
+        differ in how often it is renewed: a GPU passed to a virtual machine
+        was seen to get one a second (firmware timestamps 1.0 s apart), and
+        until then reads return the old activity figures. False
+        when no table carries a timestamp or none changed within `timeout`."""
+        first = self._stamps()
+        if not first or not all(first):
+            return False
+        t_end = time.monotonic() + timeout
+        while time.monotonic() < t_end:
+            time.sleep(period)
+            if all(b != a for a, b in zip(first, self._stamps())):
+                return True
+        return False
+
     def sample(self) -> list[GpuCounters]:
         now = self._clock()
         out = []

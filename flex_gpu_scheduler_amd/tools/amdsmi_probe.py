@@ -38,6 +38,7 @@ def run(seconds: float = 2.0, period: float = 0.05) -> dict:
     if not ok:
         return {"available": False, "error": err}
     smi = AmdSmiSampler()
+    smi.wait_refresh()  # the idle phase must not read a table from before this process
     first = smi.sample()
     out = {"available": True, "gpus": len(first),
            "gpu0": {"bdf": first[0].bdf, "links_up": first[0].links_up, "xcc": len(first[0].xcc_busy)} if first else None}

@@ -41,6 +41,16 @@ def sample_for(tel, seconds: float, period: float) -> int:
     return n
 
 
+def await_fresh_counters(hs) -> None:
+    """amd-smi serves the firmware's last metrics table, which on some hosts
+    is renewed only once a second: without this wait a phase starts on the
+    figures of whatever the GPU did before it. Injected samplers have no
+    table to wait for."""
+    smi = getattr(hs, "smi", None)
+    if smi is not None and hasattr(smi, "wait_refresh"):
+        smi.wait_refresh()
+
+
 def copy_loop_load(device: int = 0):
     """Keeps cuda:`device` busy with 1 GiB device copies until the returned
     stop()."""
@@ -75,10 +85,12 @@ def run(seconds: float = 2.0, period: float = 0.05, *, sampler=None, start_load=
 
     hs = sampler if sampler is not None else HostSampler(gpu_source="amdsmi")
     idle, busy = NodeTelemetry(IDLE, hs), NodeTelemetry(BUSY, hs)
+    await_fresh_counters(hs)  # not the tail of an earlier process's load
     n_idle = sample_for(idle, min(1.0, seconds / 2), period)
     end_load = start_load()
     try:
         time.sleep(0.3)  # let the activity counters ramp
+        await_fresh_counters(hs)
         n_busy = sample_for(busy, seconds, period)
     finally:
         end_load()

@@ -11,13 +11,14 @@ from flex_gpu_scheduler_amd.models import GPU, make_node, make_pod, make_pod_gro
 from test_trimaran import explain_scores, metrics, only_score
 
 
-def smi_doc(index=0, gfx=30, umc=60, used=100_000, total=294_896, read_kb=(0,) * 8, write_kb=(0,) * 8, up=7):
+def smi_doc(index=0, gfx=30, umc=60, used=100_000, total=294_896, read_kb=(0,) * 8, write_kb=(0,) * 8, up=7,
+            stamp=0):
     return {"index": index, "bdf": f"0000:{index + 5:02x}:00.0", "gfx_activity": gfx, "umc_activity": umc,
             "mm_activity": 0, "xcc_busy": [gfx] * 8, "vram_total_mb": total, "vram_used_mb": used,
             "socket_power_w": 640, "temp_hotspot_c": 55, "temp_mem_c": 48,
             "xgmi_read_kb": list(read_kb), "xgmi_write_kb": list(write_kb),
             "xgmi_link_up": [1] * up + [0] * (8 - up), "xgmi_link_speed": 32, "xgmi_link_width": 16,
-            "vram_max_bandwidth_gbs": 8000, "firmware_timestamp_10ns": 0, "num_partition": 1}
+            "vram_max_bandwidth_gbs": 8000, "firmware_timestamp_10ns": stamp, "num_partition": 1}
 
 
 class FakeReader:
@@ -47,6 +48,22 @@ def test_xgmi_rate_from_accumulators():
     assert abs(second.xgmi_gbps - 30.0) < 0.01  # 60 GB over 2 s
     assert abs(second.xgmi_pct - 100 * 30.0 / (7 * 2 * XGMI_LINK_GBPS)) < 0.01
     assert second.links_up == 7 and second.xcc_busy == [30.0] * 8
+
+
+def test_wait_refresh_returns_on_a_newer_table_of_every_gpu():
+    # GPU 1's table is renewed one read after GPU 0's: wait for both.
+    r = FakeReader([[smi_doc(0, stamp=100), smi_doc(1, stamp=100)], [smi_doc(0, stamp=100), smi_doc(1, stamp=100)],
+                    [smi_doc(0, stamp=200), smi_doc(1, stamp=100)], [smi_doc(0, stamp=200), smi_doc(1, stamp=200)]])
+    assert AmdSmiSampler(reader=r).wait_refresh(timeout=5.0, period=0.0) is True
+    assert r.frames == []
+
+
+def test_wait_refresh_gives_up_without_timestamps_or_change():
+    r = FakeReader([[smi_doc(stamp=0)]])  # metrics table unreadable: nothing to wait for
+    assert AmdSmiSampler(reader=r).wait_refresh(timeout=5.0) is False
+    assert r.frames == []
+    assert AmdSmiSampler(reader=lambda: [smi_doc(stamp=100)]).wait_refresh(timeout=0.02, period=0.001) is False
+    assert AmdSmiSampler(reader=lambda: []).wait_refresh() is False
 
 
 def test_host_sampler_prefers_injected_amdsmi():

@@ -116,3 +116,38 @@ def test_tlp_live_tool_logic_with_injected_load():
     # idle: 3% + 1/8 GPU = 15.5% -> round(60*15.5/40+40) = 63; busy: 104.5% -> 0
     assert sc[tlp_live.IDLE] == 63 and sc[tlp_live.BUSY] == 0
     assert r["predicted"] == r["landed"] == tlp_live.IDLE
+
+
+def test_tlp_live_samples_each_phase_on_a_fresh_metrics_table():
+    """amd-smi serves the firmware's last metrics table, renewed as rarely as
+    once a second on some hosts: each phase waits for a newer one, the busy
+    phase once the load runs, so neither averages in the phase before it."""
+    import time as _t
+
+    from flex_gpu_scheduler_amd.gpu.telemetry import Sample
+    from flex_gpu_scheduler_amd.tools import tlp_live
+
+    state = {"busy": False}
+    events = []
+
+    class FakeSmi:
+        def wait_refresh(self):
+            events.append(("fresh", state["busy"]))
+            return True
+
+    class FakeSampler:
+        smi = FakeSmi()
+
+        def sample(self):
+            events.append(("sample", state["busy"]))
+            return Sample(_t.time(), 10.0, 20.0, 92.0 if state["busy"] else 3.0, 5.0)
+
+    def start_load():
+        state["busy"] = True
+        return lambda: state.update(busy=False)
+
+    tlp_live.run(0.05, 0.01, sampler=FakeSampler(), start_load=start_load)
+    assert events[0] == ("fresh", False) and events[1] == ("sample", False)
+    first_busy = events.index(("fresh", True))
+    assert events[first_busy - 1] == ("sample", False) and events[first_busy + 1] == ("sample", True)
+    assert [e for e in events if e[0] == "fresh"] == [("fresh", False), ("fresh", True)]
