@@ -352,9 +352,10 @@ def _part_list_flag(args, kind: str, parts: str) -> dict:
 def health_fn_args(args) -> dict:
     """hip_health_fn's keywords from the node-agent flags.
     --health-matrix-sweep, --health-lane-sweep, --health-valu-sweep,
-    --health-scalar-sweep, --health-consensus-sweep, --health-fetch-sweep, --health-mem-sweep: as _part_list_flag
-    says, but the matrix keys
+    --health-scalar-sweep, --health-consensus-sweep, --health-fetch-sweep, --health-mem-sweep,
+    --health-load-sweep: as _part_list_flag says, but the matrix keys
     are always there (False, None).
+    --health-load-sweep-laps: with --health-load-sweep, load_args = {"laps": N}.
     --health-hbm-sweep: absent -> no hbm keys, bare -> all free HBM less the
     reserve (hbm_gib None), else that many GiB.
     --health-register-sweep: absent -> no regfile key."""
@@ -368,7 +369,9 @@ def health_fn_args(args) -> dict:
     kw.update(**_part_list_flag(args, "lane", "paths"), **_part_list_flag(args, "valu", "units"),
               **_part_list_flag(args, "scalar", "parts"), **_part_list_flag(args, "consensus", "parts"),
               **_part_list_flag(args, "fetch", "parts"),
-              **_part_list_flag(args, "mem", "routes"))
+              **_part_list_flag(args, "mem", "routes"), **_part_list_flag(args, "load", "parts"))
+    if kw.get("load") and getattr(args, "health_load_sweep_laps", None) is not None:
+        kw.update(load_args={"laps": args.health_load_sweep_laps})
     return kw
 
 
@@ -598,6 +601,15 @@ def build_parser() -> argparse.ArgumentParser:
                         "literals in the sweep's own code) run on every CU (a comma list selects some; default all); a "
                         "bad XCD is fenced like --health-sweep's and its parts are published as fetchFaults. Implies "
                         "--health-probe; independent of the other sweeps")
+    p.add_argument("--health-load-sweep", nargs="?", const="all", default=None, metavar="PARTS",
+                   help="health probe plus the load sweep: stage, lds, gemm and valu (a checked int8 GEMM pipeline on "
+                        "every CU: full-entropy operands from memory through registers and LDS into the matrix cores, "
+                        "two waves on every SIMD, an integer chain on the VALU, many laps in one launch, every result "
+                        "compared on the device; a comma list selects what is judged, default all); it runs last of "
+                        "the per-CU sweeps, a bad XCD is fenced like --health-sweep's and its parts are published as "
+                        "loadFaults. Implies --health-probe; independent of the other sweeps")
+    p.add_argument("--health-load-sweep-laps", type=int, default=None, metavar="N",
+                   help="laps (macro tiles per workgroup) of one --health-load-sweep launch; default: the measured one")
     p.add_argument("--health-mem-sweep", nargs="?", const="all", default=None, metavar="ROUTES",
                    help="health probe plus the memory-path sweep: gwidth, buffer, flat, atomic, l1, l2 and scalar (global, "
                         "buffer and flat loads and stores of every width, the memory-side atomics, the vector L1, the "

@@ -36,11 +36,18 @@ Sweeps of every CU (csrc/hip/<name>.hip), each naming the XCD of a CU that fails
     (256 KiB of straight-line code, counted backward loops, computed jumps
     and calls, jump targets at every dword of a cache line and across a page,
     a refetch after s_icache_inv), the test data being the literals in the
-    sweep's own code; names the parts. A library of its own, _hipfetch.so.
+    sweep's own code; names the parts. A library of its own, _hipfetch.so;
+  * load_sweep: every CU under load: a checked int8 GEMM pipeline (full-entropy
+    operands from memory through registers and LDS into the matrix cores, two
+    waves on every SIMD, an integer chain on the VALU between the MFMAs, many
+    laps in one launch), every result compared on the device after each lap;
+    names the parts (stage, lds, gemm, valu) and when in the launch a mismatch
+    occurred. A library of its own, _hipload.so.
 The matrix, lane, VALU and memory sweeps are sweeps over named parts:
 PART_SWEEPS describes each, and one implementation serves the four and the
 scalar sweep, whose row SCALAR_SWEEP stands beside the table, as do
-CONSENSUS_SWEEP, the consensus sweep's, and FETCH_SWEEP, the fetch sweep's.
+CONSENSUS_SWEEP, the consensus sweep's, FETCH_SWEEP, the fetch sweep's, and
+LOAD_SWEEP, the load sweep's.
 
 hbm_sweep (csrc/hip/hbm_sweep.hip): all free HBM under an address-keyed
 pattern in both polarities; names the vectors and bits that read back wrong.
@@ -62,6 +69,8 @@ _SCALAR_LIB = Path(__file__).resolve().parent / "_hipscalar.so"
 _CONSENSUS_LIB = Path(__file__).resolve().parent / "_hipconsensus.so"
 # And the fetch sweep.
 _FETCH_LIB = Path(__file__).resolve().parent / "_hipfetch.so"
+# And the load sweep.
+_LOAD_LIB = Path(__file__).resolve().parent / "_hipload.so"
 MODES = {"read": 0, "write": 1, "copy": 2, "triad": 3}
 
 
@@ -181,6 +190,24 @@ FETCH_SEGMENTS = 32  # of 8 KiB: the rows of fetch_probe_clocks
 FETCH_SYMBOLS = ("xs_fetch_sweep_last_error", "xs_fetch_parts", "xs_fetch_shape", "xs_fetch_probe",
                  "xs_fetch_sweep_expected", "xs_fetch_sweep_info", "xs_fetch_sweep")
 
+# k_load_sweep (csrc/hip/load_sweep.hip): one 128-byte record per workgroup,
+# {xcd, cu, simd_mask, fail, 4 bad counts, 4 digests, bad_simds, 0, the sub-tiles,
+# the sets and the 32 spans of the launch's laps that mis-compared, 0 x 15}.
+LOAD_RECORD_WORDS = 32
+LOAD_SEED = 0x1B873593
+LOAD_BLOCK = 512  # threads per workgroup: 8 waves, two on every SIMD
+LOAD_LAPS = 1024  # macro tiles per workgroup and launch; measured in profiles/load_sweep_defaults.md
+LOAD_KSTEPS = 32  # the sweep's shape: K = 64 x 32 = 2,048
+LOAD_SETS = 8  # and 8 operand sets of 768 KiB
+LOAD_TILE = (128, 256)  # C of one lap
+LOAD_MASK_WORD = 14  # the first of the three mask words
+# xs_load_sweep could not allocate its arena or its table: nothing was launched (the meaning MEM_UNSWEPT has).
+LOAD_UNSWEPT = -1003
+LOAD_WORDING = {LOAD_UNSWEPT: "no memory could be had for the arena: nothing was swept"}
+# The C ABI of _hipload.so.
+LOAD_SYMBOLS = ("xs_load_sweep_last_error", "xs_load_parts", "xs_load_shape", "xs_load_probe",
+                "xs_load_sweep_expected", "xs_load_sweep_info", "xs_load_sweep", "xs_load_operands")
+
 
 @dataclass(frozen=True)
 class PartSweep:
@@ -221,6 +248,9 @@ CONSENSUS_SWEEP = PartSweep("consensus", "xs_consensus_parts", "consensus part",
 # And the fetch sweep's: the lane sweep's head with five parts.
 FETCH_SWEEP = PartSweep("fetch", "xs_fetch_parts", "fetch part", "failed_parts", "parts", FETCH_RECORD_WORDS,
                         digests=9, bad=4, bad_simds=14)
+# And the load sweep's: the same head with four parts.
+LOAD_SWEEP = PartSweep("load", "xs_load_parts", "load part", "failed_parts", "parts", LOAD_RECORD_WORDS,
+                       digests=8, bad=4, bad_simds=12)
 
 # k_hbm_fill / k_hbm_verify (csrc/hip/hbm_sweep.hip)
 HBM_SWEEP_SEED = 0x5EED1E55
@@ -335,8 +365,8 @@ def decode_part_record(kind: PartSweep, names: list[str], w, expected: dict, ste
 class HipProbe:
     def __init__(self, path: str | Path = _LIB, mem_path: str | Path = _MEM_LIB,
                  scalar_path: str | Path = _SCALAR_LIB, consensus_path: str | Path = _CONSENSUS_LIB,
-                 fetch_path: str | Path = _FETCH_LIB):
-        for built in (path, mem_path, scalar_path, consensus_path, fetch_path):
+                 fetch_path: str | Path = _FETCH_LIB, load_path: str | Path = _LOAD_LIB):
+        for built in (path, mem_path, scalar_path, consensus_path, fetch_path, load_path):
             if not Path(built).exists():
                 raise ProbeError(f"{built} not built; run `python -m flex_gpu_scheduler_amd.build_ext --hip`")
         try:
@@ -494,6 +524,24 @@ class HipProbe:
                                      ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]
         for name in FETCH_SYMBOLS:
             setattr(L, name, getattr(F, name))
+        # load_sweep.hip's library, likewise.
+        self.load_lib = ctypes.CDLL(str(load_path))
+        G = self.load_lib
+        G.xs_load_sweep_last_error.restype = ctypes.c_char_p
+        G.xs_load_parts.restype = ctypes.c_char_p
+        G.xs_load_shape.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        G.xs_load_probe.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                    ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]
+        G.xs_load_operands.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                       ctypes.c_void_p]
+        G.xs_load_sweep_expected.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                             ctypes.POINTER(ctypes.c_uint32)]
+        G.xs_load_sweep_info.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+        G.xs_load_sweep.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                    ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_void_p,
+                                    ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]
+        for name in LOAD_SYMBOLS:
+            setattr(L, name, getattr(G, name))
         L.xs_hbm_sweep_last_error.restype = ctypes.c_char_p
         L.xs_hbm_sweep_pattern.argtypes = [ctypes.c_uint64, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int,
                                            ctypes.c_void_p]
@@ -1350,6 +1398,75 @@ class HipProbe:
         out["summary"].update(code_rounds=rounds)
         return out
 
+    # ----------------------------------------------------------- load sweep
+    def load_parts(self) -> list[str]:
+        """Part names of the load sweep; the index is the part's bit."""
+        return self._part_names(LOAD_SWEEP)
+
+    def load_shape(self, part: str, laps: int = LOAD_LAPS) -> dict:
+        """`words` one part has in load_probe's dump at `laps`: `fixed_words`
+        whatever the laps plus `words_per_lap` for each."""
+        out = self._part_shape(LOAD_SWEEP, part, 2)
+        return {"fixed_words": out[0], "words_per_lap": out[1], "words": out[0] + out[1] * max(int(laps), 0)}
+
+    def load_operands(self, seed: int = LOAD_SEED, set_: int = 0, ksteps: int = LOAD_KSTEPS):
+        """The bytes the arena holds for one operand set, computed on the host:
+        (A int8 [128, 64 ksteps], Bt int8 [256, 64 ksteps]). No device call."""
+        import numpy as np
+
+        k = 64 * max(int(ksteps), 0)
+        a, bt = np.zeros((LOAD_TILE[0], k), np.int8), np.zeros((LOAD_TILE[1], k), np.int8)
+        self._call("load_sweep", "load_operands", seed, set_, ksteps, a.ctypes.data, bt.ctypes.data)
+        return a, bt
+
+    def load_probe(self, dev: int, parts=None, seed: int = LOAD_SEED, laps: int = 1, ksteps: int = LOAD_KSTEPS,
+                   sets: int = LOAD_SETS) -> dict:
+        """k_load_probe: one workgroup of 512 threads runs `laps` laps at any
+        shape and stores what it holds: {"gemm": int32 [laps, 128, 256], C of
+        every lap; "stage", "lds": uint32 [512], every thread's fold; "valu":
+        uint32 [512], every thread's final chain value}. `parts` selects
+        whether the chain runs (the pipeline always does)."""
+        import numpy as np
+
+        mask = self._part_mask(LOAD_SWEEP, parts)
+        c = max(int(laps), 0) * LOAD_TILE[0] * LOAD_TILE[1]
+        out = np.zeros(c + 3 * LOAD_BLOCK, np.uint32)
+        self._call("load_sweep", "load_probe", dev, mask, seed, laps, ksteps, sets, out.ctypes.data, out.size,
+                   wording=LOAD_WORDING)
+        folds = out[c:].reshape(3, LOAD_BLOCK)
+        return {"gemm": out[:c].view(np.int32).reshape(-1, *LOAD_TILE), "stage": folds[0], "lds": folds[1],
+                "valu": folds[2]}
+
+    def load_sweep_expected(self, parts=None, seed: int = LOAD_SEED, laps: int = LOAD_LAPS) -> dict:
+        """The workgroup digest a healthy CU leaves per selected part at the
+        sweep's shape, computed on the host (the product in plain int32)."""
+        return self._part_expected(LOAD_SWEEP, parts, seed, laps)
+
+    def load_sweep_info(self, dev: int = 0) -> dict:
+        """What the runtime reports for k_load_sweep: `num_regs`,
+        `scratch_bytes` per lane, `lds_bytes` per workgroup, `blocks_per_cu`
+        (workgroups that fit on a CU at once)."""
+        return self._sweep_info("load_sweep", dev, ("num_regs", "scratch_bytes", "lds_bytes", "blocks_per_cu"))
+
+    def load_sweep(self, dev: int = 0, blocks: int = 0, parts=None, seed: int = LOAD_SEED, laps: int = LOAD_LAPS,
+                   inject: tuple | None = None, max_rounds: int = 4) -> dict:
+        """k_load_sweep: `laps` macro tiles of a checked int8 GEMM on every CU a
+        workgroup lands on, every selected part (None: all) judged. `inject` =
+        (xcd, cu key or None for every CU of that XCD, [part names]): those
+        workgroups flip one bit of one word of those parts (tests the
+        comparator on a healthy GPU). `blocks` 0: 4 per CU. Arena (6 MiB) and
+        table (1 MiB) stay on the device for the life of the process.
+
+        Raises ProbeError with rc LOAD_UNSWEPT when they could not be had
+        (nothing ran). Relaunched (at most `max_rounds` launches) while some CU
+        has not been seen, as cu_sweep does. Returns {"records": [...],
+        "summary": summarize_load_sweep(...) plus rounds (launches), ms,
+        blocks, parts, laps, seed}."""
+        out = self._part_sweep(LOAD_SWEEP, summarize_load_sweep, dev, blocks, parts, inject, max_rounds,
+                               (seed, laps), {"seed": seed}, wording=LOAD_WORDING, tail=load_record_tail)
+        out["summary"].update(laps=laps)
+        return out
+
     # ----------------------------------------------------------- VALU sweep
     def valu_units(self) -> list[str]:
         """Unit names of the VALU sweep; the index is the unit's bit."""
@@ -1640,6 +1757,32 @@ def summarize_fetch_sweep(records: list[dict], compute_units: int, parts: list[s
     overall. The record names the CU that ran, not the neighbour that shares
     its instruction cache."""
     return _name_fail_bits(summarize_sweep(records, compute_units), FETCH_SWEEP.summary_key, parts)
+
+
+def load_record_tail(w) -> dict:
+    """The three masks of a k_load_sweep record: the sub-tiles (bit = sub-tile
+    of the 2 x 4) and the sets (bit = set & 31) that mis-compared, and the 32
+    equal spans of the launch's laps in which one did."""
+    m = w[LOAD_MASK_WORD:LOAD_MASK_WORD + 3]
+    return {"bad_subtiles": int(m[0]), "bad_sets": int(m[1]), "bad_spans": int(m[2])}
+
+
+def summarize_load_sweep(records: list[dict], compute_units: int, parts: list[str]) -> dict:
+    """summarize_sweep over k_load_sweep records, whose fail bits are part bits
+    (`parts` names them in bit order): adds `failed_parts` per XCD and overall,
+    and `late_only` = {xcd: [cu, ...]}: the CUs whose span mask has a bit but
+    none in its first half, the fault that only appears late in a launch."""
+    s = _name_fail_bits(summarize_sweep(records, compute_units), LOAD_SWEEP.summary_key, parts)
+    spans: dict[tuple[int, int], int] = {}
+    for r in records:
+        k = int(r["xcd"]), int(r["cu"])
+        spans[k] = spans.get(k, 0) | int(r.get("bad_spans", 0))
+    late: dict[int, list[int]] = {}
+    for (x, c), m in sorted(spans.items()):
+        if m and not m & 0xFFFF:
+            late.setdefault(x, []).append(c)
+    s["late_only"] = late
+    return s
 
 
 def vote_consensus(records: list[dict], parts: list[str]) -> dict:
