@@ -147,11 +147,6 @@ XS_HD uint32_t operand_word(uint32_t seed, uint32_t set, uint32_t panel, uint32_
   return fmix32(seed ^ (set << 23 | panel << 22 | w));
 }
 XS_HD uint32_t chain_start(uint32_t seed, uint32_t t) { return fmix32(seed ^ 0x80000000u ^ t); }
-// The set workgroup g reads in lap l.
-XS_HD uint32_t set_of(uint32_t g, uint32_t l, uint32_t laps, uint32_t sets) {
-  return ((l < laps - laps % sets ? g : 0u) + l) % sets;
-}
-XS_HD uint32_t rotl(uint32_t x, uint32_t s) { return (x << (s & 31u)) | (x >> ((32u - s) & 31u)); }
 
 struct LoadRecord {
   PartRecordHead<kNumParts> head;

@@ -25,6 +25,16 @@ __host__ __device__ __forceinline__ uint32_t fmix32(uint32_t h) {
   return h;
 }
 
+// What the load sweeps (load_sweep.hip, mxload_sweep.hip) fold a word with, and
+// the operand set their workgroup g reads in lap l: rotated by g while l is
+// below the last multiple of `sets` that fits in `laps`, plain l % sets behind it.
+__host__ __device__ __forceinline__ uint32_t rotl(uint32_t x, uint32_t s) {
+  return (x << (s & 31u)) | (x >> ((32u - s) & 31u));
+}
+__host__ __device__ __forceinline__ uint32_t set_of(uint32_t g, uint32_t l, uint32_t laps, uint32_t sets) {
+  return ((l < laps - laps % sets ? g : 0u) + l) % sets;
+}
+
 // One thread's mismatches and digest of one part.
 struct Tally {
   uint32_t bad = 0, digest = 0;

@@ -353,9 +353,10 @@ def health_fn_args(args) -> dict:
     """hip_health_fn's keywords from the node-agent flags.
     --health-matrix-sweep, --health-lane-sweep, --health-valu-sweep,
     --health-scalar-sweep, --health-consensus-sweep, --health-fetch-sweep, --health-mem-sweep,
-    --health-load-sweep: as _part_list_flag says, but the matrix keys
+    --health-load-sweep, --health-mxload-sweep: as _part_list_flag says, but the matrix keys
     are always there (False, None).
-    --health-load-sweep-laps: with --health-load-sweep, load_args = {"laps": N}.
+    --health-load-sweep-laps: with --health-load-sweep, load_args = {"laps": N};
+    --health-mxload-sweep-laps: with --health-mxload-sweep, mxload_args likewise.
     --health-hbm-sweep: absent -> no hbm keys, bare -> all free HBM less the
     reserve (hbm_gib None), else that many GiB.
     --health-register-sweep: absent -> no regfile key."""
@@ -369,9 +370,12 @@ def health_fn_args(args) -> dict:
     kw.update(**_part_list_flag(args, "lane", "paths"), **_part_list_flag(args, "valu", "units"),
               **_part_list_flag(args, "scalar", "parts"), **_part_list_flag(args, "consensus", "parts"),
               **_part_list_flag(args, "fetch", "parts"),
-              **_part_list_flag(args, "mem", "routes"), **_part_list_flag(args, "load", "parts"))
-    if kw.get("load") and getattr(args, "health_load_sweep_laps", None) is not None:
-        kw.update(load_args={"laps": args.health_load_sweep_laps})
+              **_part_list_flag(args, "mem", "routes"), **_part_list_flag(args, "load", "parts"),
+              **_part_list_flag(args, "mxload", "parts"))
+    for kind in ("load", "mxload"):
+        laps = getattr(args, f"health_{kind}_sweep_laps", None)
+        if kw.get(kind) and laps is not None:
+            kw[f"{kind}_args"] = {"laps": laps}
     return kw
 
 
@@ -610,6 +614,16 @@ def build_parser() -> argparse.ArgumentParser:
                         "loadFaults. Implies --health-probe; independent of the other sweeps")
     p.add_argument("--health-load-sweep-laps", type=int, default=None, metavar="N",
                    help="laps (macro tiles per workgroup) of one --health-load-sweep launch; default: the measured one")
+    p.add_argument("--health-mxload-sweep", nargs="?", const="all", default=None, metavar="PARTS",
+                   help="health probe plus the MX load sweep: operand, scale and gemm (a checked block-scaled FP4 GEMM "
+                        "pipeline on every CU: e2m1 operands and E8M0 scales from memory by LDS DMA through a ring of "
+                        "LDS stages into the scaled MFMA, two waves on every SIMD, many laps in one launch, every "
+                        "result compared on the device by equality; a comma list selects what is judged, default "
+                        "all); it runs directly after the load sweep, last of all, a bad XCD is fenced like "
+                        "--health-sweep's and its parts are published as mxLoadFaults. Implies --health-probe; "
+                        "independent of the other sweeps")
+    p.add_argument("--health-mxload-sweep-laps", type=int, default=None, metavar="N",
+                   help="laps (macro tiles per workgroup) of one --health-mxload-sweep launch; default: the measured one")
     p.add_argument("--health-mem-sweep", nargs="?", const="all", default=None, metavar="ROUTES",
                    help="health probe plus the memory-path sweep: gwidth, buffer, flat, atomic, l1, l2 and scalar (global, "
                         "buffer and flat loads and stores of every width, the memory-side atomics, the vector L1, the "

@@ -42,12 +42,17 @@ Sweeps of every CU (csrc/hip/<name>.hip), each naming the XCD of a CU that fails
     waves on every SIMD, an integer chain on the VALU between the MFMAs, many
     laps in one launch), every result compared on the device after each lap;
     names the parts (stage, lds, gemm, valu) and when in the launch a mismatch
-    occurred. A library of its own, _hipload.so.
+    occurred. A library of its own, _hipload.so;
+  * mxload_sweep: the same under a checked block-scaled FP4 GEMM: e2m1 operands
+    and E8M0 scale bytes from memory by LDS DMA through a ring of three LDS
+    stages into v_mfma_scale_f32_32x32x64_f8f6f4, every sum one exact float,
+    compared after each lap; names the parts (operand, scale, gemm). A library
+    of its own, _hipmxload.so.
 The matrix, lane, VALU and memory sweeps are sweeps over named parts:
 PART_SWEEPS describes each, and one implementation serves the four and the
 scalar sweep, whose row SCALAR_SWEEP stands beside the table, as do
-CONSENSUS_SWEEP, the consensus sweep's, FETCH_SWEEP, the fetch sweep's, and
-LOAD_SWEEP, the load sweep's.
+CONSENSUS_SWEEP, the consensus sweep's, FETCH_SWEEP, the fetch sweep's,
+LOAD_SWEEP, the load sweep's, and MXLOAD_SWEEP, the MX load sweep's.
 
 hbm_sweep (csrc/hip/hbm_sweep.hip): all free HBM under an address-keyed
 pattern in both polarities; names the vectors and bits that read back wrong.
@@ -71,6 +76,8 @@ _CONSENSUS_LIB = Path(__file__).resolve().parent / "_hipconsensus.so"
 _FETCH_LIB = Path(__file__).resolve().parent / "_hipfetch.so"
 # And the load sweep.
 _LOAD_LIB = Path(__file__).resolve().parent / "_hipload.so"
+# And the MX load sweep.
+_MXLOAD_LIB = Path(__file__).resolve().parent / "_hipmxload.so"
 MODES = {"read": 0, "write": 1, "copy": 2, "triad": 3}
 
 
@@ -208,6 +215,25 @@ LOAD_WORDING = {LOAD_UNSWEPT: "no memory could be had for the arena: nothing was
 LOAD_SYMBOLS = ("xs_load_sweep_last_error", "xs_load_parts", "xs_load_shape", "xs_load_probe",
                 "xs_load_sweep_expected", "xs_load_sweep_info", "xs_load_sweep", "xs_load_operands")
 
+# k_mxload_sweep (csrc/hip/mxload_sweep.hip): one 128-byte record per workgroup,
+# {xcd, cu, simd_mask, fail, 3 bad counts, 3 digests, bad_simds, 0, the load
+# sweep's three masks, 0 x 17}.
+MXLOAD_RECORD_WORDS = 32
+MXLOAD_SEED = 0x2545F491
+MXLOAD_BLOCK = 512  # threads per workgroup: 8 waves, two on every SIMD
+MXLOAD_LAPS = 1024  # macro tiles per workgroup and launch; measured in profiles/mxload_sweep_defaults.md
+MXLOAD_KSTEPS = 16  # the sweep's shape: K = 128 x 16 = 2,048 e2m1
+MXLOAD_MAX_KSTEPS = 56  # beyond it a sum may leave the 2^24 units a float holds exactly
+MXLOAD_SETS = 16  # and 16 operand sets of 408 KiB
+MXLOAD_TILE = LOAD_TILE  # C of one lap
+MXLOAD_MASK_WORD = 12  # the first of the three mask words
+# xs_mxload_sweep could not allocate its arena or its table: nothing was launched.
+MXLOAD_UNSWEPT = LOAD_UNSWEPT
+MXLOAD_WORDING = LOAD_WORDING
+# The C ABI of _hipmxload.so.
+MXLOAD_SYMBOLS = ("xs_mxload_sweep_last_error", "xs_mxload_parts", "xs_mxload_shape", "xs_mxload_probe",
+                  "xs_mxload_sweep_expected", "xs_mxload_sweep_info", "xs_mxload_sweep", "xs_mxload_operands")
+
 
 @dataclass(frozen=True)
 class PartSweep:
@@ -251,6 +277,9 @@ FETCH_SWEEP = PartSweep("fetch", "xs_fetch_parts", "fetch part", "failed_parts",
 # And the load sweep's: the same head with four parts.
 LOAD_SWEEP = PartSweep("load", "xs_load_parts", "load part", "failed_parts", "parts", LOAD_RECORD_WORDS,
                        digests=8, bad=4, bad_simds=12)
+# And the MX load sweep's: the same head with three parts.
+MXLOAD_SWEEP = PartSweep("mxload", "xs_mxload_parts", "MX load part", "failed_parts", "parts", MXLOAD_RECORD_WORDS,
+                         digests=7, bad=4, bad_simds=10)
 
 # k_hbm_fill / k_hbm_verify (csrc/hip/hbm_sweep.hip)
 HBM_SWEEP_SEED = 0x5EED1E55
@@ -365,8 +394,9 @@ def decode_part_record(kind: PartSweep, names: list[str], w, expected: dict, ste
 class HipProbe:
     def __init__(self, path: str | Path = _LIB, mem_path: str | Path = _MEM_LIB,
                  scalar_path: str | Path = _SCALAR_LIB, consensus_path: str | Path = _CONSENSUS_LIB,
-                 fetch_path: str | Path = _FETCH_LIB, load_path: str | Path = _LOAD_LIB):
-        for built in (path, mem_path, scalar_path, consensus_path, fetch_path, load_path):
+                 fetch_path: str | Path = _FETCH_LIB, load_path: str | Path = _LOAD_LIB,
+                 mxload_path: str | Path = _MXLOAD_LIB):
+        for built in (path, mem_path, scalar_path, consensus_path, fetch_path, load_path, mxload_path):
             if not Path(built).exists():
                 raise ProbeError(f"{built} not built; run `python -m flex_gpu_scheduler_amd.build_ext --hip`")
         try:
@@ -542,6 +572,16 @@ class HipProbe:
                                     ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]
         for name in LOAD_SYMBOLS:
             setattr(L, name, getattr(G, name))
+        # mxload_sweep.hip's library, likewise: the load sweep's signatures but for the operands' two scale arrays.
+        self.mxload_lib = ctypes.CDLL(str(mxload_path))
+        X = self.mxload_lib
+        X.xs_mxload_sweep_last_error.restype = ctypes.c_char_p
+        X.xs_mxload_parts.restype = ctypes.c_char_p
+        X.xs_mxload_operands.argtypes = [ctypes.c_uint32] * 3 + [ctypes.c_void_p] * 4
+        for what in ("shape", "probe", "sweep_expected", "sweep_info", "sweep"):
+            getattr(X, f"xs_mxload_{what}").argtypes = getattr(G, f"xs_load_{what}").argtypes
+        for name in MXLOAD_SYMBOLS:
+            setattr(L, name, getattr(X, name))
         L.xs_hbm_sweep_last_error.restype = ctypes.c_char_p
         L.xs_hbm_sweep_pattern.argtypes = [ctypes.c_uint64, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int,
                                            ctypes.c_void_p]
@@ -1467,6 +1507,69 @@ class HipProbe:
         out["summary"].update(laps=laps)
         return out
 
+    # -------------------------------------------------------- MX load sweep
+    def mxload_parts(self) -> list[str]:
+        """Part names of the MX load sweep; the index is the part's bit."""
+        return self._part_names(MXLOAD_SWEEP)
+
+    def mxload_shape(self, part: str, laps: int = MXLOAD_LAPS) -> dict:
+        """`words` one part has in mxload_probe's dump at `laps`: `fixed_words`
+        whatever the laps plus `words_per_lap` for each."""
+        out = self._part_shape(MXLOAD_SWEEP, part, 2)
+        return {"fixed_words": out[0], "words_per_lap": out[1], "words": out[0] + out[1] * max(int(laps), 0)}
+
+    def mxload_operands(self, seed: int = MXLOAD_SEED, set_: int = 0, ksteps: int = MXLOAD_KSTEPS):
+        """One operand set in its logical order, computed on the host: (A uint8
+        [128, 64 ksteps], Bt uint8 [256, 64 ksteps]: two e2m1 per byte, low
+        nibble first; A's E8M0 scales uint8 [128, 4 ksteps], Bt's [256, 4
+        ksteps]: one per 32 elements of k). No device call."""
+        import numpy as np
+
+        k = max(int(ksteps), 0)
+        out = [np.zeros((rows, n * k), np.uint8) for n in (64, 4) for rows in MXLOAD_TILE]
+        self._call("mxload_sweep", "mxload_operands", seed, set_, ksteps, *(a.ctypes.data for a in out))
+        return tuple(out)
+
+    def mxload_probe(self, dev: int, parts=None, seed: int = MXLOAD_SEED, laps: int = 1, ksteps: int = MXLOAD_KSTEPS,
+                     sets: int = MXLOAD_SETS) -> dict:
+        """k_mxload_probe: one workgroup of 512 threads runs `laps` laps at any
+        shape and stores what it holds: {"gemm": float32 [laps, 128, 256], C of
+        every lap as the accumulators' bits; "operand", "scale": uint32 [512],
+        every thread's fold}. `parts` selects which folds are issued (the
+        pipeline always runs)."""
+        import numpy as np
+
+        mask = self._part_mask(MXLOAD_SWEEP, parts)
+        c = max(int(laps), 0) * MXLOAD_TILE[0] * MXLOAD_TILE[1]
+        out = np.zeros(c + 2 * MXLOAD_BLOCK, np.uint32)
+        self._call("mxload_sweep", "mxload_probe", dev, mask, seed, laps, ksteps, sets, out.ctypes.data, out.size,
+                   wording=MXLOAD_WORDING)
+        folds = out[c:].reshape(2, MXLOAD_BLOCK)
+        return {"gemm": out[:c].view(np.float32).reshape(-1, *MXLOAD_TILE), "operand": folds[0], "scale": folds[1]}
+
+    def mxload_sweep_expected(self, parts=None, seed: int = MXLOAD_SEED, laps: int = MXLOAD_LAPS) -> dict:
+        """The workgroup digest a healthy CU leaves per selected part at the
+        sweep's shape, computed on the host (8 C in plain int32)."""
+        return self._part_expected(MXLOAD_SWEEP, parts, seed, laps)
+
+    def mxload_sweep_info(self, dev: int = 0) -> dict:
+        """What the runtime reports for k_mxload_sweep: `num_regs`,
+        `scratch_bytes` per lane, `lds_bytes` per workgroup, `blocks_per_cu`."""
+        return self._sweep_info("mxload_sweep", dev, ("num_regs", "scratch_bytes", "lds_bytes", "blocks_per_cu"))
+
+    def mxload_sweep(self, dev: int = 0, blocks: int = 0, parts=None, seed: int = MXLOAD_SEED,
+                     laps: int = MXLOAD_LAPS, inject: tuple | None = None, max_rounds: int = 4) -> dict:
+        """k_mxload_sweep: `laps` macro tiles of a checked MXFP4 GEMM on every
+        CU a workgroup lands on, every selected part (None: all) judged.
+        `inject`, `blocks`, `max_rounds`, the ProbeError with rc MXLOAD_UNSWEPT
+        and the result are load_sweep's; arena (6.4 MiB) and table (2 MiB) stay
+        on the device for the life of the process."""
+        out = self._part_sweep(MXLOAD_SWEEP, summarize_load_sweep, dev, blocks, parts, inject, max_rounds,
+                               (seed, laps), {"seed": seed}, wording=MXLOAD_WORDING,
+                               tail=lambda w: load_record_tail(w, MXLOAD_MASK_WORD))
+        out["summary"].update(laps=laps)
+        return out
+
     # ----------------------------------------------------------- VALU sweep
     def valu_units(self) -> list[str]:
         """Unit names of the VALU sweep; the index is the unit's bit."""
@@ -1759,16 +1862,17 @@ def summarize_fetch_sweep(records: list[dict], compute_units: int, parts: list[s
     return _name_fail_bits(summarize_sweep(records, compute_units), FETCH_SWEEP.summary_key, parts)
 
 
-def load_record_tail(w) -> dict:
-    """The three masks of a k_load_sweep record: the sub-tiles (bit = sub-tile
+def load_record_tail(w, first: int = LOAD_MASK_WORD) -> dict:
+    """The three masks of a k_load_sweep record (of a k_mxload_sweep record
+    with `first` = MXLOAD_MASK_WORD): the sub-tiles (bit = sub-tile
     of the 2 x 4) and the sets (bit = set & 31) that mis-compared, and the 32
     equal spans of the launch's laps in which one did."""
-    m = w[LOAD_MASK_WORD:LOAD_MASK_WORD + 3]
+    m = w[first:first + 3]
     return {"bad_subtiles": int(m[0]), "bad_sets": int(m[1]), "bad_spans": int(m[2])}
 
 
 def summarize_load_sweep(records: list[dict], compute_units: int, parts: list[str]) -> dict:
-    """summarize_sweep over k_load_sweep records, whose fail bits are part bits
+    """summarize_sweep over k_load_sweep or k_mxload_sweep records, whose fail bits are part bits
     (`parts` names them in bit order): adds `failed_parts` per XCD and overall,
     and `late_only` = {xcd: [cu, ...]}: the CUs whose span mask has a bit but
     none in its first half, the fault that only appears late in a launch."""
