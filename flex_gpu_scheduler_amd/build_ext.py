@@ -1,8 +1,8 @@
 """In-tree native build: the C++ scheduler core (`_xsched`) and the HIP/CDNA4
 probe kernels (`ops/_hipprobe`, the memory sweep's `ops/_hipmem`, the scalar
 sweep's `ops/_hipscalar`, the consensus sweep's `ops/_hipconsensus`, the
-fetch sweep's `ops/_hipfetch`, the load sweep's `ops/_hipload` and the MX load
-sweep's `ops/_hipmxload`).
+fetch sweep's `ops/_hipfetch`, the load sweep's `ops/_hipload`, the MX load
+sweep's `ops/_hipmxload` and the bf16 load sweep's `ops/_hipbfload`).
 
 Both land next to the Python sources (not site-packages) so the built `.so`
 files travel with the repo snapshot to the MI355X box and show up as loaded
@@ -152,11 +152,13 @@ def build_hip(verbose: bool = True) -> Path | None:
     fetch = [s for s in srcs if s.name == "fetch_sweep.hip"]  # ops/_hipfetch.so, likewise
     load = [s for s in srcs if s.name == "load_sweep.hip"]  # ops/_hipload.so, likewise
     mxload = [s for s in srcs if s.name == "mxload_sweep.hip"]  # ops/_hipmxload.so, likewise
+    bfload = [s for s in srcs if s.name == "bfload_sweep.hip"]  # ops/_hipbfload.so, likewise
     out = PKG / "ops" / "_hipprobe.so"
-    for lib, lib_srcs in ((out, [s for s in srcs if s not in mem + scalar + consensus + fetch + load + mxload]),
+    for lib, lib_srcs in ((out, [s for s in srcs if s not in mem + scalar + consensus + fetch + load + mxload + bfload]),
                           (PKG / "ops" / "_hipmem.so", mem), (PKG / "ops" / "_hipscalar.so", scalar),
                           (PKG / "ops" / "_hipconsensus.so", consensus), (PKG / "ops" / "_hipfetch.so", fetch),
-                          (PKG / "ops" / "_hipload.so", load), (PKG / "ops" / "_hipmxload.so", mxload)):
+                          (PKG / "ops" / "_hipload.so", load), (PKG / "ops" / "_hipmxload.so", mxload),
+                          (PKG / "ops" / "_hipbfload.so", bfload)):
         newest = max([s.stat().st_mtime for s in lib_srcs] + [_headers_mtime()])
         if lib.exists() and lib.stat().st_mtime >= newest:
             continue

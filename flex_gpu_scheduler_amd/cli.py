@@ -353,10 +353,11 @@ def health_fn_args(args) -> dict:
     """hip_health_fn's keywords from the node-agent flags.
     --health-matrix-sweep, --health-lane-sweep, --health-valu-sweep,
     --health-scalar-sweep, --health-consensus-sweep, --health-fetch-sweep, --health-mem-sweep,
-    --health-load-sweep, --health-mxload-sweep: as _part_list_flag says, but the matrix keys
-    are always there (False, None).
+    --health-load-sweep, --health-mxload-sweep, --health-bfload-sweep: as _part_list_flag says,
+    but the matrix keys are always there (False, None).
     --health-load-sweep-laps: with --health-load-sweep, load_args = {"laps": N};
-    --health-mxload-sweep-laps: with --health-mxload-sweep, mxload_args likewise.
+    --health-mxload-sweep-laps: with --health-mxload-sweep, mxload_args likewise;
+    --health-bfload-sweep-laps: with --health-bfload-sweep, bfload_args likewise.
     --health-hbm-sweep: absent -> no hbm keys, bare -> all free HBM less the
     reserve (hbm_gib None), else that many GiB.
     --health-register-sweep: absent -> no regfile key."""
@@ -371,8 +372,8 @@ def health_fn_args(args) -> dict:
               **_part_list_flag(args, "scalar", "parts"), **_part_list_flag(args, "consensus", "parts"),
               **_part_list_flag(args, "fetch", "parts"),
               **_part_list_flag(args, "mem", "routes"), **_part_list_flag(args, "load", "parts"),
-              **_part_list_flag(args, "mxload", "parts"))
-    for kind in ("load", "mxload"):
+              **_part_list_flag(args, "mxload", "parts"), **_part_list_flag(args, "bfload", "parts"))
+    for kind in ("load", "mxload", "bfload"):
         laps = getattr(args, f"health_{kind}_sweep_laps", None)
         if kw.get(kind) and laps is not None:
             kw[f"{kind}_args"] = {"laps": laps}
@@ -624,6 +625,17 @@ def build_parser() -> argparse.ArgumentParser:
                         "independent of the other sweeps")
     p.add_argument("--health-mxload-sweep-laps", type=int, default=None, metavar="N",
                    help="laps (macro tiles per workgroup) of one --health-mxload-sweep launch; default: the measured one")
+    p.add_argument("--health-bfload-sweep", nargs="?", const="all", default=None, metavar="PARTS",
+                   help="health probe plus the bf16 load sweep: stage, operand, transpose and gemm (a checked bf16 GEMM "
+                        "pipeline in the NN layout on every CU: bf16 operands of one binade from memory through "
+                        "registers and LDS, B through the transposed LDS read, into the bf16 MFMA, two waves on every "
+                        "SIMD, many laps in one launch, every result compared on the device by equality; a comma list "
+                        "selects what is judged, default all); it runs directly after the MX load sweep, last of all, "
+                        "a bad XCD is fenced like --health-sweep's and its parts are published as bfLoadFaults. "
+                        "Implies --health-probe; independent of the other sweeps")
+    p.add_argument("--health-bfload-sweep-laps", type=int, default=None, metavar="N",
+                   help="laps (macro tiles per workgroup) of one --health-bfload-sweep launch; default: "
+                        "the measured one")
     p.add_argument("--health-mem-sweep", nargs="?", const="all", default=None, metavar="ROUTES",
                    help="health probe plus the memory-path sweep: gwidth, buffer, flat, atomic, l1, l2 and scalar (global, "
                         "buffer and flat loads and stores of every width, the memory-side atomics, the vector L1, the "

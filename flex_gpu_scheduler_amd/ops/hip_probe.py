@@ -47,12 +47,18 @@ Sweeps of every CU (csrc/hip/<name>.hip), each naming the XCD of a CU that fails
     and E8M0 scale bytes from memory by LDS DMA through a ring of three LDS
     stages into v_mfma_scale_f32_32x32x64_f8f6f4, every sum one exact float,
     compared after each lap; names the parts (operand, scale, gemm). A library
-    of its own, _hipmxload.so.
+    of its own, _hipmxload.so;
+  * bfload_sweep: the same under a checked bf16 GEMM in the NN layout: bf16
+    operands of one binade from memory through registers and LDS, B through
+    ds_read_b64_tr_b16, into v_mfma_f32_32x32x16_bf16, every sum one exact
+    float, compared after each lap; names the parts (stage, operand,
+    transpose, gemm). A library of its own, _hipbfload.so.
 The matrix, lane, VALU and memory sweeps are sweeps over named parts:
 PART_SWEEPS describes each, and one implementation serves the four and the
 scalar sweep, whose row SCALAR_SWEEP stands beside the table, as do
 CONSENSUS_SWEEP, the consensus sweep's, FETCH_SWEEP, the fetch sweep's,
-LOAD_SWEEP, the load sweep's, and MXLOAD_SWEEP, the MX load sweep's.
+LOAD_SWEEP, the load sweep's, MXLOAD_SWEEP, the MX load sweep's, and
+BFLOAD_SWEEP, the bf16 load sweep's.
 
 hbm_sweep (csrc/hip/hbm_sweep.hip): all free HBM under an address-keyed
 pattern in both polarities; names the vectors and bits that read back wrong.
@@ -78,6 +84,8 @@ _FETCH_LIB = Path(__file__).resolve().parent / "_hipfetch.so"
 _LOAD_LIB = Path(__file__).resolve().parent / "_hipload.so"
 # And the MX load sweep.
 _MXLOAD_LIB = Path(__file__).resolve().parent / "_hipmxload.so"
+# And the bf16 load sweep.
+_BFLOAD_LIB = Path(__file__).resolve().parent / "_hipbfload.so"
 MODES = {"read": 0, "write": 1, "copy": 2, "triad": 3}
 
 
@@ -234,6 +242,24 @@ MXLOAD_WORDING = LOAD_WORDING
 MXLOAD_SYMBOLS = ("xs_mxload_sweep_last_error", "xs_mxload_parts", "xs_mxload_shape", "xs_mxload_probe",
                   "xs_mxload_sweep_expected", "xs_mxload_sweep_info", "xs_mxload_sweep", "xs_mxload_operands")
 
+# k_bfload_sweep (csrc/hip/bfload_sweep.hip): one 128-byte record per workgroup,
+# laid out as k_load_sweep's: four parts and the three masks.
+BFLOAD_RECORD_WORDS = 32
+BFLOAD_SEED = 0x27D4EB2F
+BFLOAD_BLOCK = 512  # threads per workgroup: 8 waves, two on every SIMD
+BFLOAD_LAPS = 2048  # macro tiles per workgroup and launch; measured in profiles/bfload_sweep_defaults.md
+BFLOAD_KSTEPS = 8  # the sweep's shape: K = 32 x 8 = 256 bf16
+BFLOAD_MAX_KSTEPS = 8  # beyond K = 258 a sum may leave the 2^24 units a float holds exactly
+BFLOAD_SETS = 32  # and 32 operand sets of 192 KiB
+BFLOAD_TILE = LOAD_TILE  # C of one lap
+BFLOAD_MASK_WORD = LOAD_MASK_WORD  # the first of the three mask words
+# xs_bfload_sweep could not allocate its arena or its table: nothing was launched.
+BFLOAD_UNSWEPT = LOAD_UNSWEPT
+BFLOAD_WORDING = LOAD_WORDING
+# The C ABI of _hipbfload.so.
+BFLOAD_SYMBOLS = ("xs_bfload_sweep_last_error", "xs_bfload_parts", "xs_bfload_shape", "xs_bfload_probe",
+                  "xs_bfload_sweep_expected", "xs_bfload_sweep_info", "xs_bfload_sweep", "xs_bfload_operands")
+
 
 @dataclass(frozen=True)
 class PartSweep:
@@ -280,6 +306,9 @@ LOAD_SWEEP = PartSweep("load", "xs_load_parts", "load part", "failed_parts", "pa
 # And the MX load sweep's: the same head with three parts.
 MXLOAD_SWEEP = PartSweep("mxload", "xs_mxload_parts", "MX load part", "failed_parts", "parts", MXLOAD_RECORD_WORDS,
                          digests=7, bad=4, bad_simds=10)
+# And the bf16 load sweep's: the load sweep's head, four parts.
+BFLOAD_SWEEP = PartSweep("bfload", "xs_bfload_parts", "bf16 load part", "failed_parts", "parts", BFLOAD_RECORD_WORDS,
+                         digests=8, bad=4, bad_simds=12)
 
 # k_hbm_fill / k_hbm_verify (csrc/hip/hbm_sweep.hip)
 HBM_SWEEP_SEED = 0x5EED1E55
@@ -395,8 +424,8 @@ class HipProbe:
     def __init__(self, path: str | Path = _LIB, mem_path: str | Path = _MEM_LIB,
                  scalar_path: str | Path = _SCALAR_LIB, consensus_path: str | Path = _CONSENSUS_LIB,
                  fetch_path: str | Path = _FETCH_LIB, load_path: str | Path = _LOAD_LIB,
-                 mxload_path: str | Path = _MXLOAD_LIB):
-        for built in (path, mem_path, scalar_path, consensus_path, fetch_path, load_path, mxload_path):
+                 mxload_path: str | Path = _MXLOAD_LIB, bfload_path: str | Path = _BFLOAD_LIB):
+        for built in (path, mem_path, scalar_path, consensus_path, fetch_path, load_path, mxload_path, bfload_path):
             if not Path(built).exists():
                 raise ProbeError(f"{built} not built; run `python -m flex_gpu_scheduler_amd.build_ext --hip`")
         try:
@@ -582,6 +611,15 @@ class HipProbe:
             getattr(X, f"xs_mxload_{what}").argtypes = getattr(G, f"xs_load_{what}").argtypes
         for name in MXLOAD_SYMBOLS:
             setattr(L, name, getattr(X, name))
+        # bfload_sweep.hip's library, likewise: the load sweep's signatures throughout.
+        self.bfload_lib = ctypes.CDLL(str(bfload_path))
+        B = self.bfload_lib
+        B.xs_bfload_sweep_last_error.restype = ctypes.c_char_p
+        B.xs_bfload_parts.restype = ctypes.c_char_p
+        for what in ("shape", "probe", "operands", "sweep_expected", "sweep_info", "sweep"):
+            getattr(B, f"xs_bfload_{what}").argtypes = getattr(G, f"xs_load_{what}").argtypes
+        for name in BFLOAD_SYMBOLS:
+            setattr(L, name, getattr(B, name))
         L.xs_hbm_sweep_last_error.restype = ctypes.c_char_p
         L.xs_hbm_sweep_pattern.argtypes = [ctypes.c_uint64, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int,
                                            ctypes.c_void_p]
@@ -1567,6 +1605,69 @@ class HipProbe:
         out = self._part_sweep(MXLOAD_SWEEP, summarize_load_sweep, dev, blocks, parts, inject, max_rounds,
                                (seed, laps), {"seed": seed}, wording=MXLOAD_WORDING,
                                tail=lambda w: load_record_tail(w, MXLOAD_MASK_WORD))
+        out["summary"].update(laps=laps)
+        return out
+
+    # ------------------------------------------------------ bf16 load sweep
+    def bfload_parts(self) -> list[str]:
+        """Part names of the bf16 load sweep; the index is the part's bit."""
+        return self._part_names(BFLOAD_SWEEP)
+
+    def bfload_shape(self, part: str, laps: int = BFLOAD_LAPS) -> dict:
+        """`words` one part has in bfload_probe's dump at `laps`: `fixed_words`
+        whatever the laps plus `words_per_lap` for each."""
+        out = self._part_shape(BFLOAD_SWEEP, part, 2)
+        return {"fixed_words": out[0], "words_per_lap": out[1], "words": out[0] + out[1] * max(int(laps), 0)}
+
+    def bfload_operands(self, seed: int = BFLOAD_SEED, set_: int = 0, ksteps: int = BFLOAD_KSTEPS):
+        """The bf16 bits the arena holds for one operand set, computed on the
+        host: (A uint16 [128, 32 ksteps], B uint16 [32 ksteps, 256], n
+        contiguous). No device call."""
+        import numpy as np
+
+        k = 32 * max(int(ksteps), 0)
+        a, b = np.zeros((BFLOAD_TILE[0], k), np.uint16), np.zeros((k, BFLOAD_TILE[1]), np.uint16)
+        self._call("bfload_sweep", "bfload_operands", seed, set_, ksteps, a.ctypes.data, b.ctypes.data)
+        return a, b
+
+    def bfload_probe(self, dev: int, parts=None, seed: int = BFLOAD_SEED, laps: int = 1, ksteps: int = BFLOAD_KSTEPS,
+                     sets: int = BFLOAD_SETS) -> dict:
+        """k_bfload_probe: one workgroup of 512 threads runs `laps` laps at any
+        shape and stores what it holds: {"gemm": float32 [laps, 128, 256], C of
+        every lap; "stage", "operand", "transpose": uint32 [512], every
+        thread's fold}. `parts` selects which folds are issued (the pipeline
+        always runs)."""
+        import numpy as np
+
+        mask = self._part_mask(BFLOAD_SWEEP, parts)
+        c = max(int(laps), 0) * BFLOAD_TILE[0] * BFLOAD_TILE[1]
+        out = np.zeros(c + 3 * BFLOAD_BLOCK, np.uint32)
+        self._call("bfload_sweep", "bfload_probe", dev, mask, seed, laps, ksteps, sets, out.ctypes.data, out.size,
+                   wording=BFLOAD_WORDING)
+        folds = out[c:].reshape(3, BFLOAD_BLOCK)
+        return {"gemm": out[:c].view(np.float32).reshape(-1, *BFLOAD_TILE), "stage": folds[0], "operand": folds[1],
+                "transpose": folds[2]}
+
+    def bfload_sweep_expected(self, parts=None, seed: int = BFLOAD_SEED, laps: int = BFLOAD_LAPS) -> dict:
+        """The workgroup digest a healthy CU leaves per selected part at the
+        sweep's shape, computed on the host (C 2^14 in plain int32)."""
+        return self._part_expected(BFLOAD_SWEEP, parts, seed, laps)
+
+    def bfload_sweep_info(self, dev: int = 0) -> dict:
+        """What the runtime reports for k_bfload_sweep: `num_regs`,
+        `scratch_bytes` per lane, `lds_bytes` per workgroup, `blocks_per_cu`."""
+        return self._sweep_info("bfload_sweep", dev, ("num_regs", "scratch_bytes", "lds_bytes", "blocks_per_cu"))
+
+    def bfload_sweep(self, dev: int = 0, blocks: int = 0, parts=None, seed: int = BFLOAD_SEED,
+                     laps: int = BFLOAD_LAPS, inject: tuple | None = None, max_rounds: int = 4) -> dict:
+        """k_bfload_sweep: `laps` macro tiles of a checked bf16 GEMM (B not
+        transposed in memory) on every CU a workgroup lands on, every selected
+        part (None: all) judged. `inject`, `blocks`, `max_rounds`, the
+        ProbeError with rc BFLOAD_UNSWEPT and the result are load_sweep's;
+        arena (6 MiB) and table (4 MiB) stay on the device for the life of the
+        process."""
+        out = self._part_sweep(BFLOAD_SWEEP, summarize_load_sweep, dev, blocks, parts, inject, max_rounds,
+                               (seed, laps), {"seed": seed}, wording=BFLOAD_WORDING, tail=load_record_tail)
         out["summary"].update(laps=laps)
         return out
 
