@@ -353,11 +353,12 @@ def health_fn_args(args) -> dict:
     """hip_health_fn's keywords from the node-agent flags.
     --health-matrix-sweep, --health-lane-sweep, --health-valu-sweep,
     --health-scalar-sweep, --health-consensus-sweep, --health-fetch-sweep, --health-mem-sweep,
-    --health-load-sweep, --health-mxload-sweep, --health-bfload-sweep: as _part_list_flag says,
-    but the matrix keys are always there (False, None).
+    --health-load-sweep, --health-mxload-sweep, --health-bfload-sweep, --health-attnload-sweep: as
+    _part_list_flag says, but the matrix keys are always there (False, None).
     --health-load-sweep-laps: with --health-load-sweep, load_args = {"laps": N};
     --health-mxload-sweep-laps: with --health-mxload-sweep, mxload_args likewise;
-    --health-bfload-sweep-laps: with --health-bfload-sweep, bfload_args likewise.
+    --health-bfload-sweep-laps: with --health-bfload-sweep, bfload_args likewise;
+    --health-attnload-sweep-laps: with --health-attnload-sweep, attnload_args likewise.
     --health-hbm-sweep: absent -> no hbm keys, bare -> all free HBM less the
     reserve (hbm_gib None), else that many GiB.
     --health-register-sweep: absent -> no regfile key."""
@@ -372,8 +373,9 @@ def health_fn_args(args) -> dict:
               **_part_list_flag(args, "scalar", "parts"), **_part_list_flag(args, "consensus", "parts"),
               **_part_list_flag(args, "fetch", "parts"),
               **_part_list_flag(args, "mem", "routes"), **_part_list_flag(args, "load", "parts"),
-              **_part_list_flag(args, "mxload", "parts"), **_part_list_flag(args, "bfload", "parts"))
-    for kind in ("load", "mxload", "bfload"):
+              **_part_list_flag(args, "mxload", "parts"), **_part_list_flag(args, "bfload", "parts"),
+              **_part_list_flag(args, "attnload", "parts"))
+    for kind in ("load", "mxload", "bfload", "attnload"):
         laps = getattr(args, f"health_{kind}_sweep_laps", None)
         if kw.get(kind) and laps is not None:
             kw[f"{kind}_args"] = {"laps": laps}
@@ -635,6 +637,18 @@ def build_parser() -> argparse.ArgumentParser:
                         "Implies --health-probe; independent of the other sweeps")
     p.add_argument("--health-bfload-sweep-laps", type=int, default=None, metavar="N",
                    help="laps (macro tiles per workgroup) of one --health-bfload-sweep launch; default: "
+                        "the measured one")
+    p.add_argument("--health-attnload-sweep", nargs="?", const="all", default=None, metavar="PARTS",
+                   help="health probe plus the attention load sweep: stage, score, stat, transpose and out (a checked "
+                        "attention forward pass on every CU: the scores' accumulators go through floor, clamp, max, "
+                        "v_exp_f32, the exchange between lane halves and the bf16 conversion straight back into the "
+                        "matrix core, with the online softmax's rescale and V through the transposed LDS read, two "
+                        "waves on every SIMD, many laps in one launch, every result compared on the device by "
+                        "equality; a comma list selects what is judged, default all); it runs directly after the "
+                        "bf16 load sweep, last of all, a bad XCD is fenced like --health-sweep's and its parts are "
+                        "published as attnLoadFaults. Implies --health-probe; independent of the other sweeps")
+    p.add_argument("--health-attnload-sweep-laps", type=int, default=None, metavar="N",
+                   help="laps (attention tiles per workgroup) of one --health-attnload-sweep launch; default: "
                         "the measured one")
     p.add_argument("--health-mem-sweep", nargs="?", const="all", default=None, metavar="ROUTES",
                    help="health probe plus the memory-path sweep: gwidth, buffer, flat, atomic, l1, l2 and scalar (global, "

@@ -27,7 +27,9 @@ exporter + metrics-server:
     of the load sweep (a checked int8 GEMM with every unit busy) as `loadFaults`
     and those of the MX load sweep (a checked block-scaled FP4 GEMM fed by LDS
     DMA) as `mxLoadFaults` and those of the bf16 load sweep (a checked bf16 GEMM
-    whose B goes through the transposed LDS read) as `bfLoadFaults`;
+    whose B goes through the transposed LDS read) as `bfLoadFaults` and those
+    of the attention load sweep (a checked attention forward pass, one matrix
+    product feeding the next through the softmax) as `attnLoadFaults`;
     a verdict that carries an HBM fault (the HBM sweep) withholds the whole
     GPU, partitioned or not, and is published as `hbmFaults`;
   * samples load (gpu/telemetry.py) and publishes its WatcherMetrics document
@@ -134,6 +136,9 @@ MXLOAD_SWEEP_KIND = SweepKind("mxload", "mxload_sweep", "mxload", "mxLoadSweep",
 # And the bf16 load sweep directly after that one: now it is the last of all.
 BFLOAD_SWEEP_KIND = SweepKind("bfload", "bfload_sweep", "bfload", "bfLoadSweep", "parts", "bfLoadFaults",
                               lambda v: list(v["failed_parts"]))
+# And the attention load sweep directly after that one: now it is the last of all.
+ATTNLOAD_SWEEP_KIND = SweepKind("attnload", "attnload_sweep", "attnload", "attnLoadSweep", "parts", "attnLoadFaults",
+                                lambda v: list(v["failed_parts"]))
 
 FAULT_KINDS = {
     # What the per-CU sweeps found on a faulty XCD. Informational: the XCD is
@@ -159,6 +164,8 @@ FAULT_KINDS = {
     MXLOAD_SWEEP_KIND.faults_key: FaultKind(per_xcd=False),
     # What the bf16 load sweep found on the GPU: {XCD id: [part, ...]}, likewise.
     BFLOAD_SWEEP_KIND.faults_key: FaultKind(per_xcd=False),
+    # What the attention load sweep found on the GPU: {XCD id: [part, ...]}, likewise.
+    ATTNLOAD_SWEEP_KIND.faults_key: FaultKind(per_xcd=False),
 }
 
 
@@ -510,30 +517,32 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
                   fetch_args: dict | None = None, load: bool = False, load_parts: list | None = None,
                   load_args: dict | None = None, mxload: bool = False, mxload_parts: list | None = None,
                   mxload_args: dict | None = None, bfload: bool = False, bfload_parts: list | None = None,
-                  bfload_args: dict | None = None) -> Callable[[int], "bool | GpuHealth"]:
+                  bfload_args: dict | None = None, attnload: bool = False, attnload_parts: list | None = None,
+                  attnload_args: dict | None = None) -> Callable[[int], "bool | GpuHealth"]:
     """Health callback backed by the HIP probes (HBM pattern + checksum and an
     MFMA tile check per GPU).
 
     Each kind of SWEEP_KINDS, SCALAR_SWEEP_KIND, CONSENSUS_SWEEP_KIND, FETCH_SWEEP_KIND, MEM_SWEEP_KIND,
-    LOAD_SWEEP_KIND, MXLOAD_SWEEP_KIND and BFLOAD_SWEEP_KIND, in the order they run,
+    LOAD_SWEEP_KIND, MXLOAD_SWEEP_KIND, BFLOAD_SWEEP_KIND and ATTNLOAD_SWEEP_KIND, in the order they run,
     has a switch `<kind>` that also runs that per-CU sweep of HipProbe (`sweep`: the CU sweep), `<kind>_args` for its keywords
     and, where it sweeps named parts, `<kind>_<parts>` to select some (None for
     all). Its summary and, the CU sweep apart, its {xcd: fault} go into the
     verdict's detail under the kind's keys. A fault is the list of the failed
-    formats, paths, units, scalar parts, consensus parts, fetch parts, routes, load parts, MX load parts or bf16 load parts;
+    formats, paths, units, scalar parts, consensus parts, fetch parts, routes, load parts, MX load parts, bf16 load parts
+    or attention load parts;
     of `regfile`, {"files": [...], "cells": n,
     "flipMask": "0x...", "simds": n}. The VALU sweep's failed steps are in
     detail["valuSweep"]. The consensus sweep judges a CU by the vote of the
     GPU's CUs; a part the vote could not decide (detail["consensusSweep"]["undecided"])
     is logged at WARNING, fails nothing and touches no other sweep's verdict.
     The memory sweep holds an arena in HBM while it runs, the load sweep, the
-    MX load sweep and the bf16 load sweep an arena and a table each for the
-    life of the process;
+    MX load sweep, the bf16 load sweep and the attention load sweep an arena
+    and a table each for the life of the process;
     where that cannot be had the device is logged as unswept, which neither
     fails it nor touches the other sweeps' verdicts. The load sweep and, behind
-    it, the MX load sweep and the bf16 load sweep run last: they heat the part
-    (`load_args={"laps": n}`, `mxload_args={"laps": n}` and
-    `bfload_args={"laps": n}` set their lengths).
+    it, the MX load sweep, the bf16 load sweep and the attention load sweep run
+    last: they heat the part (`load_args={"laps": n}`, `mxload_args={"laps": n}`,
+    `bfload_args={"laps": n}` and `attnload_args={"laps": n}` set their lengths).
     The callback runs on every heartbeat, so the sweeps' verdict is reused for
     `sweep_period_s`. On a device that shows all 8 XCDs the verdict is a
     GpuHealth naming the bad physical XCDs of any of these sweeps; a
@@ -552,8 +561,8 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
     memory could be had is logged as unswept and a sweep that got less than it
     asked for as short; neither fails the device."""
     given = locals()  # the parameters by name, for SWEEP_KINDS
-    from ..ops.hip_probe import (BFLOAD_UNSWEPT, HBM_UNSWEPT, LOAD_UNSWEPT, MEM_UNSWEPT, MXLOAD_UNSWEPT, ProbeError,
-                                 probe)
+    from ..ops.hip_probe import (ATTNLOAD_UNSWEPT, BFLOAD_UNSWEPT, HBM_UNSWEPT, LOAD_UNSWEPT, MEM_UNSWEPT,
+                                 MXLOAD_UNSWEPT, ProbeError, probe)
 
     p = probe()
     last: dict[int, tuple[float, object]] = {}  # dev -> (monotonic time, sweep verdict)
@@ -561,10 +570,11 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
     per_cu_sweeps = [(k, {**({k.selection: given[f"{k.enabled_by}_{k.selection}"]} if k.selection else {}),
                           **(given[f"{k.enabled_by}_args"] or {})})
                      for k in SWEEP_KINDS + (SCALAR_SWEEP_KIND, CONSENSUS_SWEEP_KIND, FETCH_SWEEP_KIND, MEM_SWEEP_KIND,
-                                             LOAD_SWEEP_KIND, MXLOAD_SWEEP_KIND, BFLOAD_SWEEP_KIND)
+                                             LOAD_SWEEP_KIND, MXLOAD_SWEEP_KIND, BFLOAD_SWEEP_KIND,
+                                             ATTNLOAD_SWEEP_KIND)
                      if given[k.enabled_by]]
     unswept = {MEM_SWEEP_KIND: MEM_UNSWEPT, LOAD_SWEEP_KIND: LOAD_UNSWEPT, MXLOAD_SWEEP_KIND: MXLOAD_UNSWEPT,
-               BFLOAD_SWEEP_KIND: BFLOAD_UNSWEPT}
+               BFLOAD_SWEEP_KIND: BFLOAD_UNSWEPT, ATTNLOAD_SWEEP_KIND: ATTNLOAD_UNSWEPT}
 
     def sweep_verdict(dev: int):
         now = time.monotonic()

@@ -52,13 +52,21 @@ Sweeps of every CU (csrc/hip/<name>.hip), each naming the XCD of a CU that fails
     operands of one binade from memory through registers and LDS, B through
     ds_read_b64_tr_b16, into v_mfma_f32_32x32x16_bf16, every sum one exact
     float, compared after each lap; names the parts (stage, operand,
-    transpose, gemm). A library of its own, _hipbfload.so.
+    transpose, gemm). A library of its own, _hipbfload.so;
+  * attnload_sweep: the same under a checked attention forward pass: the
+    accumulators of S^T = K Q^T go through floor, clamp, max, v_exp_f32, the
+    exchange between a wave's lane halves and v_cvt_pk_bf16_f32 straight back
+    into the matrix core as an operand of O^T += V^T P^T, with the online
+    softmax's rescale in between and V through ds_read_b64_tr_b16; every
+    value one exact float, compared after each lap; names the parts (stage,
+    score, stat, transpose, out). A library of its own, _hipattnload.so.
 The matrix, lane, VALU and memory sweeps are sweeps over named parts:
 PART_SWEEPS describes each, and one implementation serves the four and the
 scalar sweep, whose row SCALAR_SWEEP stands beside the table, as do
 CONSENSUS_SWEEP, the consensus sweep's, FETCH_SWEEP, the fetch sweep's,
-LOAD_SWEEP, the load sweep's, MXLOAD_SWEEP, the MX load sweep's, and
-BFLOAD_SWEEP, the bf16 load sweep's.
+LOAD_SWEEP, the load sweep's, MXLOAD_SWEEP, the MX load sweep's,
+BFLOAD_SWEEP, the bf16 load sweep's, and ATTNLOAD_SWEEP, the attention load
+sweep's.
 
 hbm_sweep (csrc/hip/hbm_sweep.hip): all free HBM under an address-keyed
 pattern in both polarities; names the vectors and bits that read back wrong.
@@ -86,6 +94,8 @@ _LOAD_LIB = Path(__file__).resolve().parent / "_hipload.so"
 _MXLOAD_LIB = Path(__file__).resolve().parent / "_hipmxload.so"
 # And the bf16 load sweep.
 _BFLOAD_LIB = Path(__file__).resolve().parent / "_hipbfload.so"
+# And the attention load sweep.
+_ATTNLOAD_LIB = Path(__file__).resolve().parent / "_hipattnload.so"
 MODES = {"read": 0, "write": 1, "copy": 2, "triad": 3}
 
 
@@ -260,6 +270,27 @@ BFLOAD_WORDING = LOAD_WORDING
 BFLOAD_SYMBOLS = ("xs_bfload_sweep_last_error", "xs_bfload_parts", "xs_bfload_shape", "xs_bfload_probe",
                   "xs_bfload_sweep_expected", "xs_bfload_sweep_info", "xs_bfload_sweep", "xs_bfload_operands")
 
+# k_attnload_sweep (csrc/hip/attnload_sweep.hip): one 128-byte record per
+# workgroup, {xcd, cu, simd_mask, fail, 5 bad counts, 5 digests, bad_simds, 0,
+# the query blocks, the sets and the 32 spans of the launch's laps that
+# mis-compared, 0 x 13}.
+ATTNLOAD_RECORD_WORDS = 32
+ATTNLOAD_SEED = 0x165667B1
+ATTNLOAD_BLOCK = 512  # threads per workgroup: 8 waves, two on every SIMD
+ATTNLOAD_LAPS = 1024  # attention tiles per workgroup and launch; measured in profiles/attnload_sweep_defaults.md
+ATTNLOAD_KVSTEPS = 8  # the sweep's shape: N = 64 x 8 = 512 keys
+ATTNLOAD_MAX_KVSTEPS = 16  # beyond N = 1,032 a sum may leave the 2^24 units a float holds exactly
+ATTNLOAD_SETS = 32  # and 32 operand sets of 160 KiB
+ATTNLOAD_TILE = (256, 64)  # O of one lap: queries x head dimension
+ATTNLOAD_MASK_WORD = 16  # the first of the three mask words
+# xs_attnload_sweep could not allocate its arena or its table: nothing was launched.
+ATTNLOAD_UNSWEPT = LOAD_UNSWEPT
+ATTNLOAD_WORDING = LOAD_WORDING
+# The C ABI of _hipattnload.so.
+ATTNLOAD_SYMBOLS = ("xs_attnload_sweep_last_error", "xs_attnload_parts", "xs_attnload_shape", "xs_attnload_probe",
+                    "xs_attnload_sweep_expected", "xs_attnload_sweep_info", "xs_attnload_sweep",
+                    "xs_attnload_operands")
+
 
 @dataclass(frozen=True)
 class PartSweep:
@@ -309,6 +340,9 @@ MXLOAD_SWEEP = PartSweep("mxload", "xs_mxload_parts", "MX load part", "failed_pa
 # And the bf16 load sweep's: the load sweep's head, four parts.
 BFLOAD_SWEEP = PartSweep("bfload", "xs_bfload_parts", "bf16 load part", "failed_parts", "parts", BFLOAD_RECORD_WORDS,
                          digests=8, bad=4, bad_simds=12)
+# And the attention load sweep's: the same head with five parts.
+ATTNLOAD_SWEEP = PartSweep("attnload", "xs_attnload_parts", "attention load part", "failed_parts", "parts",
+                           ATTNLOAD_RECORD_WORDS, digests=9, bad=4, bad_simds=14)
 
 # k_hbm_fill / k_hbm_verify (csrc/hip/hbm_sweep.hip)
 HBM_SWEEP_SEED = 0x5EED1E55
@@ -424,8 +458,10 @@ class HipProbe:
     def __init__(self, path: str | Path = _LIB, mem_path: str | Path = _MEM_LIB,
                  scalar_path: str | Path = _SCALAR_LIB, consensus_path: str | Path = _CONSENSUS_LIB,
                  fetch_path: str | Path = _FETCH_LIB, load_path: str | Path = _LOAD_LIB,
-                 mxload_path: str | Path = _MXLOAD_LIB, bfload_path: str | Path = _BFLOAD_LIB):
-        for built in (path, mem_path, scalar_path, consensus_path, fetch_path, load_path, mxload_path, bfload_path):
+                 mxload_path: str | Path = _MXLOAD_LIB, bfload_path: str | Path = _BFLOAD_LIB,
+                 attnload_path: str | Path = _ATTNLOAD_LIB):
+        for built in (path, mem_path, scalar_path, consensus_path, fetch_path, load_path, mxload_path, bfload_path,
+                      attnload_path):
             if not Path(built).exists():
                 raise ProbeError(f"{built} not built; run `python -m flex_gpu_scheduler_amd.build_ext --hip`")
         try:
@@ -620,6 +656,16 @@ class HipProbe:
             getattr(B, f"xs_bfload_{what}").argtypes = getattr(G, f"xs_load_{what}").argtypes
         for name in BFLOAD_SYMBOLS:
             setattr(L, name, getattr(B, name))
+        # attnload_sweep.hip's library, likewise: the load sweep's signatures but for the operands' three panels.
+        self.attnload_lib = ctypes.CDLL(str(attnload_path))
+        T = self.attnload_lib
+        T.xs_attnload_sweep_last_error.restype = ctypes.c_char_p
+        T.xs_attnload_parts.restype = ctypes.c_char_p
+        T.xs_attnload_operands.argtypes = [ctypes.c_uint32] * 3 + [ctypes.c_void_p] * 3
+        for what in ("shape", "probe", "sweep_expected", "sweep_info", "sweep"):
+            getattr(T, f"xs_attnload_{what}").argtypes = getattr(G, f"xs_load_{what}").argtypes
+        for name in ATTNLOAD_SYMBOLS:
+            setattr(L, name, getattr(T, name))
         L.xs_hbm_sweep_last_error.restype = ctypes.c_char_p
         L.xs_hbm_sweep_pattern.argtypes = [ctypes.c_uint64, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int,
                                            ctypes.c_void_p]
@@ -1668,6 +1714,74 @@ class HipProbe:
         process."""
         out = self._part_sweep(BFLOAD_SWEEP, summarize_load_sweep, dev, blocks, parts, inject, max_rounds,
                                (seed, laps), {"seed": seed}, wording=BFLOAD_WORDING, tail=load_record_tail)
+        out["summary"].update(laps=laps)
+        return out
+
+    # ------------------------------------------------- attention load sweep
+    def attnload_parts(self) -> list[str]:
+        """Part names of the attention load sweep; the index is the part's bit."""
+        return self._part_names(ATTNLOAD_SWEEP)
+
+    def attnload_shape(self, part: str, laps: int = ATTNLOAD_LAPS) -> dict:
+        """`words` one part has in attnload_probe's dump at `laps`:
+        `fixed_words` whatever the laps plus `words_per_lap` for each."""
+        out = self._part_shape(ATTNLOAD_SWEEP, part, 2)
+        return {"fixed_words": out[0], "words_per_lap": out[1], "words": out[0] + out[1] * max(int(laps), 0)}
+
+    def attnload_operands(self, seed: int = ATTNLOAD_SEED, set_: int = 0, kvsteps: int = ATTNLOAD_KVSTEPS):
+        """The bf16 bits of one operand set in their logical order, computed on
+        the host: (Q uint16 [256, 64], K uint16 [64 kvsteps, 64], V uint16
+        [64 kvsteps, 64]). No device call."""
+        import numpy as np
+
+        n = 64 * max(int(kvsteps), 0)
+        q, k, v = (np.zeros((rows, ATTNLOAD_TILE[1]), np.uint16) for rows in (ATTNLOAD_TILE[0], n, n))
+        self._call("attnload_sweep", "attnload_operands", seed, set_, kvsteps, q.ctypes.data, k.ctypes.data,
+                   v.ctypes.data)
+        return q, k, v
+
+    def attnload_probe(self, dev: int, parts=None, seed: int = ATTNLOAD_SEED, laps: int = 1,
+                       kvsteps: int = ATTNLOAD_KVSTEPS, sets: int = ATTNLOAD_SETS) -> dict:
+        """k_attnload_probe: one workgroup of 512 threads runs `laps` laps at
+        any shape and stores what it holds: {"out": float32 [laps, 256, 64],
+        the unnormalised O of every lap; "l": float32 [laps, 256]; "m": int32
+        [laps, 256]; "stage", "score", "transpose": uint32 [512], every
+        thread's fold}. `parts` selects which folds are issued (the pipeline
+        always runs)."""
+        import numpy as np
+
+        mask = self._part_mask(ATTNLOAD_SWEEP, parts)
+        rows, dim = ATTNLOAD_TILE
+        n, c = max(int(laps), 0), max(int(laps), 0) * rows * dim
+        out = np.zeros(c + 2 * n * rows + 3 * ATTNLOAD_BLOCK, np.uint32)
+        self._call("attnload_sweep", "attnload_probe", dev, mask, seed, laps, kvsteps, sets, out.ctypes.data, out.size,
+                   wording=ATTNLOAD_WORDING)
+        stat, folds = out[c:c + 2 * n * rows].reshape(2, n, rows), out[c + 2 * n * rows:].reshape(3, ATTNLOAD_BLOCK)
+        return {"out": out[:c].view(np.float32).reshape(n, rows, dim), "l": stat[0].view(np.float32),
+                "m": stat[1].view(np.int32), "stage": folds[0], "score": folds[1], "transpose": folds[2]}
+
+    def attnload_sweep_expected(self, parts=None, seed: int = ATTNLOAD_SEED, laps: int = ATTNLOAD_LAPS) -> dict:
+        """The workgroup digest a healthy CU leaves per selected part at the
+        sweep's shape, computed on the host in plain integers."""
+        return self._part_expected(ATTNLOAD_SWEEP, parts, seed, laps)
+
+    def attnload_sweep_info(self, dev: int = 0) -> dict:
+        """What the runtime reports for k_attnload_sweep: `num_regs`,
+        `scratch_bytes` per lane, `lds_bytes` per workgroup, `blocks_per_cu`."""
+        return self._sweep_info("attnload_sweep", dev, ("num_regs", "scratch_bytes", "lds_bytes", "blocks_per_cu"))
+
+    def attnload_sweep(self, dev: int = 0, blocks: int = 0, parts=None, seed: int = ATTNLOAD_SEED,
+                       laps: int = ATTNLOAD_LAPS, inject: tuple | None = None, max_rounds: int = 4) -> dict:
+        """k_attnload_sweep: `laps` tiles of a checked attention forward pass
+        (256 queries, 512 keys, head dimension 64, no mask, unnormalised) on
+        every CU a workgroup lands on, every selected part (None: all) judged.
+        `inject`, `blocks`, `max_rounds`, the ProbeError with rc
+        ATTNLOAD_UNSWEPT and the result are load_sweep's (`bad_subtiles` are
+        query blocks of 32 rows here); arena (5 MiB) and table (2.1 MiB) stay
+        on the device for the life of the process."""
+        out = self._part_sweep(ATTNLOAD_SWEEP, summarize_load_sweep, dev, blocks, parts, inject, max_rounds,
+                               (seed, laps), {"seed": seed}, wording=ATTNLOAD_WORDING,
+                               tail=lambda w: load_record_tail(w, ATTNLOAD_MASK_WORD))
         out["summary"].update(laps=laps)
         return out
 
