@@ -353,12 +353,13 @@ def health_fn_args(args) -> dict:
     """hip_health_fn's keywords from the node-agent flags.
     --health-matrix-sweep, --health-lane-sweep, --health-valu-sweep,
     --health-scalar-sweep, --health-consensus-sweep, --health-fetch-sweep, --health-mem-sweep,
-    --health-load-sweep, --health-mxload-sweep, --health-bfload-sweep, --health-attnload-sweep: as
-    _part_list_flag says, but the matrix keys are always there (False, None).
+    --health-load-sweep, --health-mxload-sweep, --health-bfload-sweep, --health-attnload-sweep,
+    --health-streamload-sweep: as _part_list_flag says, but the matrix keys are always there (False, None).
     --health-load-sweep-laps: with --health-load-sweep, load_args = {"laps": N};
     --health-mxload-sweep-laps: with --health-mxload-sweep, mxload_args likewise;
     --health-bfload-sweep-laps: with --health-bfload-sweep, bfload_args likewise;
-    --health-attnload-sweep-laps: with --health-attnload-sweep, attnload_args likewise.
+    --health-attnload-sweep-laps: with --health-attnload-sweep, attnload_args likewise;
+    --health-streamload-sweep-laps: with --health-streamload-sweep, streamload_args likewise.
     --health-hbm-sweep: absent -> no hbm keys, bare -> all free HBM less the
     reserve (hbm_gib None), else that many GiB.
     --health-register-sweep: absent -> no regfile key."""
@@ -374,8 +375,8 @@ def health_fn_args(args) -> dict:
               **_part_list_flag(args, "fetch", "parts"),
               **_part_list_flag(args, "mem", "routes"), **_part_list_flag(args, "load", "parts"),
               **_part_list_flag(args, "mxload", "parts"), **_part_list_flag(args, "bfload", "parts"),
-              **_part_list_flag(args, "attnload", "parts"))
-    for kind in ("load", "mxload", "bfload", "attnload"):
+              **_part_list_flag(args, "attnload", "parts"), **_part_list_flag(args, "streamload", "parts"))
+    for kind in ("load", "mxload", "bfload", "attnload", "streamload"):
         laps = getattr(args, f"health_{kind}_sweep_laps", None)
         if kw.get(kind) and laps is not None:
             kw[f"{kind}_args"] = {"laps": laps}
@@ -650,6 +651,18 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--health-attnload-sweep-laps", type=int, default=None, metavar="N",
                    help="laps (attention tiles per workgroup) of one --health-attnload-sweep launch; default: "
                         "the measured one")
+    p.add_argument("--health-streamload-sweep", nargs="?", const="all", default=None, metavar="PARTS",
+                   help="health probe plus the stream load sweep: stage, act and gemm (a checked int8 GEMM of 16 tokens "
+                        "on every CU: the weights stream from an arena of HBM size through a ring of outstanding loads "
+                        "straight into v_mfma_i32_16x16x64_i8, the activations come from LDS, two waves on every SIMD, "
+                        "every workgroup reads the whole arena once in one launch, every result compared on the device "
+                        "by equality; a comma list selects what is judged, default all); the arena is held in HBM for "
+                        "the length of the launch only; it runs directly after the attention load sweep, last of all, "
+                        "a bad XCD is fenced like --health-sweep's and its parts are published as streamLoadFaults. "
+                        "Implies --health-probe; independent of the other sweeps")
+    p.add_argument("--health-streamload-sweep-laps", type=int, default=None, metavar="N",
+                   help="laps (panels of 16 weight rows per wave) of one --health-streamload-sweep launch; default: "
+                        "one round, the whole arena once per workgroup")
     p.add_argument("--health-mem-sweep", nargs="?", const="all", default=None, metavar="ROUTES",
                    help="health probe plus the memory-path sweep: gwidth, buffer, flat, atomic, l1, l2 and scalar (global, "
                         "buffer and flat loads and stores of every width, the memory-side atomics, the vector L1, the "

@@ -29,7 +29,9 @@ exporter + metrics-server:
     DMA) as `mxLoadFaults` and those of the bf16 load sweep (a checked bf16 GEMM
     whose B goes through the transposed LDS read) as `bfLoadFaults` and those
     of the attention load sweep (a checked attention forward pass, one matrix
-    product feeding the next through the softmax) as `attnLoadFaults`;
+    product feeding the next through the softmax) as `attnLoadFaults` and those
+    of the stream load sweep (a checked int8 GEMM of 16 tokens whose weights
+    stream from an arena of HBM size into the matrix core) as `streamLoadFaults`;
     a verdict that carries an HBM fault (the HBM sweep) withholds the whole
     GPU, partitioned or not, and is published as `hbmFaults`;
   * samples load (gpu/telemetry.py) and publishes its WatcherMetrics document
@@ -139,6 +141,9 @@ BFLOAD_SWEEP_KIND = SweepKind("bfload", "bfload_sweep", "bfload", "bfLoadSweep",
 # And the attention load sweep directly after that one: now it is the last of all.
 ATTNLOAD_SWEEP_KIND = SweepKind("attnload", "attnload_sweep", "attnload", "attnLoadSweep", "parts", "attnLoadFaults",
                                 lambda v: list(v["failed_parts"]))
+# And the stream load sweep directly after that one: now it is the last of all.
+STREAMLOAD_SWEEP_KIND = SweepKind("streamload", "streamload_sweep", "streamload", "streamLoadSweep", "parts",
+                                  "streamLoadFaults", lambda v: list(v["failed_parts"]))
 
 FAULT_KINDS = {
     # What the per-CU sweeps found on a faulty XCD. Informational: the XCD is
@@ -166,6 +171,8 @@ FAULT_KINDS = {
     BFLOAD_SWEEP_KIND.faults_key: FaultKind(per_xcd=False),
     # What the attention load sweep found on the GPU: {XCD id: [part, ...]}, likewise.
     ATTNLOAD_SWEEP_KIND.faults_key: FaultKind(per_xcd=False),
+    # What the stream load sweep found on the GPU: {XCD id: [part, ...]}, likewise.
+    STREAMLOAD_SWEEP_KIND.faults_key: FaultKind(per_xcd=False),
 }
 
 
@@ -518,18 +525,20 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
                   load_args: dict | None = None, mxload: bool = False, mxload_parts: list | None = None,
                   mxload_args: dict | None = None, bfload: bool = False, bfload_parts: list | None = None,
                   bfload_args: dict | None = None, attnload: bool = False, attnload_parts: list | None = None,
-                  attnload_args: dict | None = None) -> Callable[[int], "bool | GpuHealth"]:
+                  attnload_args: dict | None = None, streamload: bool = False, streamload_parts: list | None = None,
+                  streamload_args: dict | None = None) -> Callable[[int], "bool | GpuHealth"]:
     """Health callback backed by the HIP probes (HBM pattern + checksum and an
     MFMA tile check per GPU).
 
     Each kind of SWEEP_KINDS, SCALAR_SWEEP_KIND, CONSENSUS_SWEEP_KIND, FETCH_SWEEP_KIND, MEM_SWEEP_KIND,
-    LOAD_SWEEP_KIND, MXLOAD_SWEEP_KIND, BFLOAD_SWEEP_KIND and ATTNLOAD_SWEEP_KIND, in the order they run,
+    LOAD_SWEEP_KIND, MXLOAD_SWEEP_KIND, BFLOAD_SWEEP_KIND, ATTNLOAD_SWEEP_KIND and STREAMLOAD_SWEEP_KIND, in the
+    order they run,
     has a switch `<kind>` that also runs that per-CU sweep of HipProbe (`sweep`: the CU sweep), `<kind>_args` for its keywords
     and, where it sweeps named parts, `<kind>_<parts>` to select some (None for
     all). Its summary and, the CU sweep apart, its {xcd: fault} go into the
     verdict's detail under the kind's keys. A fault is the list of the failed
     formats, paths, units, scalar parts, consensus parts, fetch parts, routes, load parts, MX load parts, bf16 load parts
-    or attention load parts;
+    attention load parts or stream load parts;
     of `regfile`, {"files": [...], "cells": n,
     "flipMask": "0x...", "simds": n}. The VALU sweep's failed steps are in
     detail["valuSweep"]. The consensus sweep judges a CU by the vote of the
@@ -537,12 +546,14 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
     is logged at WARNING, fails nothing and touches no other sweep's verdict.
     The memory sweep holds an arena in HBM while it runs, the load sweep, the
     MX load sweep, the bf16 load sweep and the attention load sweep an arena
-    and a table each for the life of the process;
+    and a table each for the life of the process, the stream load sweep an
+    arena of HBM size for the length of one launch;
     where that cannot be had the device is logged as unswept, which neither
     fails it nor touches the other sweeps' verdicts. The load sweep and, behind
-    it, the MX load sweep, the bf16 load sweep and the attention load sweep run
-    last: they heat the part (`load_args={"laps": n}`, `mxload_args={"laps": n}`,
-    `bfload_args={"laps": n}` and `attnload_args={"laps": n}` set their lengths).
+    it, the MX load sweep, the bf16 load sweep, the attention load sweep and the
+    stream load sweep run last: they heat the part (`load_args={"laps": n}`,
+    `mxload_args={"laps": n}`, `bfload_args={"laps": n}`, `attnload_args={"laps": n}`
+    and `streamload_args={"laps": n}` set their lengths).
     The callback runs on every heartbeat, so the sweeps' verdict is reused for
     `sweep_period_s`. On a device that shows all 8 XCDs the verdict is a
     GpuHealth naming the bad physical XCDs of any of these sweeps; a
@@ -562,7 +573,7 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
     asked for as short; neither fails the device."""
     given = locals()  # the parameters by name, for SWEEP_KINDS
     from ..ops.hip_probe import (ATTNLOAD_UNSWEPT, BFLOAD_UNSWEPT, HBM_UNSWEPT, LOAD_UNSWEPT, MEM_UNSWEPT,
-                                 MXLOAD_UNSWEPT, ProbeError, probe)
+                                 MXLOAD_UNSWEPT, STREAMLOAD_UNSWEPT, ProbeError, probe)
 
     p = probe()
     last: dict[int, tuple[float, object]] = {}  # dev -> (monotonic time, sweep verdict)
@@ -571,10 +582,11 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
                           **(given[f"{k.enabled_by}_args"] or {})})
                      for k in SWEEP_KINDS + (SCALAR_SWEEP_KIND, CONSENSUS_SWEEP_KIND, FETCH_SWEEP_KIND, MEM_SWEEP_KIND,
                                              LOAD_SWEEP_KIND, MXLOAD_SWEEP_KIND, BFLOAD_SWEEP_KIND,
-                                             ATTNLOAD_SWEEP_KIND)
+                                             ATTNLOAD_SWEEP_KIND, STREAMLOAD_SWEEP_KIND)
                      if given[k.enabled_by]]
     unswept = {MEM_SWEEP_KIND: MEM_UNSWEPT, LOAD_SWEEP_KIND: LOAD_UNSWEPT, MXLOAD_SWEEP_KIND: MXLOAD_UNSWEPT,
-               BFLOAD_SWEEP_KIND: BFLOAD_UNSWEPT, ATTNLOAD_SWEEP_KIND: ATTNLOAD_UNSWEPT}
+               BFLOAD_SWEEP_KIND: BFLOAD_UNSWEPT, ATTNLOAD_SWEEP_KIND: ATTNLOAD_UNSWEPT,
+               STREAMLOAD_SWEEP_KIND: STREAMLOAD_UNSWEPT}
 
     def sweep_verdict(dev: int):
         now = time.monotonic()

@@ -59,14 +59,19 @@ Sweeps of every CU (csrc/hip/<name>.hip), each naming the XCD of a CU that fails
     into the matrix core as an operand of O^T += V^T P^T, with the online
     softmax's rescale in between and V through ds_read_b64_tr_b16; every
     value one exact float, compared after each lap; names the parts (stage,
-    score, stat, transpose, out). A library of its own, _hipattnload.so.
+    score, stat, transpose, out). A library of its own, _hipattnload.so;
+  * streamload_sweep: the same under a checked int8 GEMM of 16 tokens whose
+    weights stream from an arena of HBM size through a register ring straight
+    into v_mfma_i32_16x16x64_i8, the activations from LDS; every sum one exact
+    int32, compared after each lap; names the parts (stage, act, gemm). A
+    library of its own, _hipstreamload.so.
 The matrix, lane, VALU and memory sweeps are sweeps over named parts:
 PART_SWEEPS describes each, and one implementation serves the four and the
 scalar sweep, whose row SCALAR_SWEEP stands beside the table, as do
 CONSENSUS_SWEEP, the consensus sweep's, FETCH_SWEEP, the fetch sweep's,
 LOAD_SWEEP, the load sweep's, MXLOAD_SWEEP, the MX load sweep's,
-BFLOAD_SWEEP, the bf16 load sweep's, and ATTNLOAD_SWEEP, the attention load
-sweep's.
+BFLOAD_SWEEP, the bf16 load sweep's, ATTNLOAD_SWEEP, the attention load
+sweep's, and STREAMLOAD_SWEEP, the stream load sweep's.
 
 hbm_sweep (csrc/hip/hbm_sweep.hip): all free HBM under an address-keyed
 pattern in both polarities; names the vectors and bits that read back wrong.
@@ -96,6 +101,8 @@ _MXLOAD_LIB = Path(__file__).resolve().parent / "_hipmxload.so"
 _BFLOAD_LIB = Path(__file__).resolve().parent / "_hipbfload.so"
 # And the attention load sweep.
 _ATTNLOAD_LIB = Path(__file__).resolve().parent / "_hipattnload.so"
+# And the stream load sweep.
+_STREAMLOAD_LIB = Path(__file__).resolve().parent / "_hipstreamload.so"
 MODES = {"read": 0, "write": 1, "copy": 2, "triad": 3}
 
 
@@ -291,6 +298,28 @@ ATTNLOAD_SYMBOLS = ("xs_attnload_sweep_last_error", "xs_attnload_parts", "xs_att
                     "xs_attnload_sweep_expected", "xs_attnload_sweep_info", "xs_attnload_sweep",
                     "xs_attnload_operands")
 
+# k_streamload_sweep (csrc/hip/streamload_sweep.hip): one 128-byte record per
+# workgroup, {xcd, cu, simd_mask, fail, 3 bad counts, 3 digests, bad_simds, 0,
+# the waves, the panels (bit = panel & 31) and the 32 spans of the launch's
+# laps that mis-compared, 0 x 17}.
+STREAMLOAD_RECORD_WORDS = 32
+STREAMLOAD_SEED = 0x27D4EB2F
+STREAMLOAD_BLOCK = 512  # threads per workgroup: 8 waves, two on every SIMD
+STREAMLOAD_KSTEPS = 64  # the sweep's shape: K = 64 x 64 = 4,096
+STREAMLOAD_MAX_KSTEPS = 64  # X, 1 KiB per step, lies in LDS whole
+STREAMLOAD_PANELS = 16384  # panels of 16 rows x K: 1 GiB; measured in profiles/streamload_sweep_defaults.md
+STREAMLOAD_LAPS = STREAMLOAD_PANELS // 8  # one round: every workgroup reads the whole arena once
+STREAMLOAD_DEPTH = 8  # global_load_dwordx4 a wave keeps in flight
+STREAMLOAD_TILE = (128, 16)  # Ct of one lap: 8 panels of 16 weight rows x tokens
+STREAMLOAD_MASK_WORD = 12  # the first of the three mask words
+# xs_streamload_sweep could not allocate its arena or its table: nothing was launched.
+STREAMLOAD_UNSWEPT = LOAD_UNSWEPT
+STREAMLOAD_WORDING = LOAD_WORDING
+# The C ABI of _hipstreamload.so.
+STREAMLOAD_SYMBOLS = ("xs_streamload_sweep_last_error", "xs_streamload_parts", "xs_streamload_shape",
+                      "xs_streamload_probe", "xs_streamload_sweep_expected", "xs_streamload_sweep_info",
+                      "xs_streamload_sweep", "xs_streamload_operands")
+
 
 @dataclass(frozen=True)
 class PartSweep:
@@ -343,6 +372,9 @@ BFLOAD_SWEEP = PartSweep("bfload", "xs_bfload_parts", "bf16 load part", "failed_
 # And the attention load sweep's: the same head with five parts.
 ATTNLOAD_SWEEP = PartSweep("attnload", "xs_attnload_parts", "attention load part", "failed_parts", "parts",
                            ATTNLOAD_RECORD_WORDS, digests=9, bad=4, bad_simds=14)
+# And the stream load sweep's: the same head with three parts.
+STREAMLOAD_SWEEP = PartSweep("streamload", "xs_streamload_parts", "stream load part", "failed_parts", "parts",
+                             STREAMLOAD_RECORD_WORDS, digests=7, bad=4, bad_simds=10)
 
 # k_hbm_fill / k_hbm_verify (csrc/hip/hbm_sweep.hip)
 HBM_SWEEP_SEED = 0x5EED1E55
@@ -459,9 +491,9 @@ class HipProbe:
                  scalar_path: str | Path = _SCALAR_LIB, consensus_path: str | Path = _CONSENSUS_LIB,
                  fetch_path: str | Path = _FETCH_LIB, load_path: str | Path = _LOAD_LIB,
                  mxload_path: str | Path = _MXLOAD_LIB, bfload_path: str | Path = _BFLOAD_LIB,
-                 attnload_path: str | Path = _ATTNLOAD_LIB):
+                 attnload_path: str | Path = _ATTNLOAD_LIB, streamload_path: str | Path = _STREAMLOAD_LIB):
         for built in (path, mem_path, scalar_path, consensus_path, fetch_path, load_path, mxload_path, bfload_path,
-                      attnload_path):
+                      attnload_path, streamload_path):
             if not Path(built).exists():
                 raise ProbeError(f"{built} not built; run `python -m flex_gpu_scheduler_amd.build_ext --hip`")
         try:
@@ -666,6 +698,19 @@ class HipProbe:
             getattr(T, f"xs_attnload_{what}").argtypes = getattr(G, f"xs_load_{what}").argtypes
         for name in ATTNLOAD_SYMBOLS:
             setattr(L, name, getattr(T, name))
+        # streamload_sweep.hip's library, likewise: the load sweep's signatures, with ksteps and panels behind the
+        # laps of the sweep and of its expected digests.
+        self.streamload_lib = ctypes.CDLL(str(streamload_path))
+        W = self.streamload_lib
+        W.xs_streamload_sweep_last_error.restype = ctypes.c_char_p
+        W.xs_streamload_parts.restype = ctypes.c_char_p
+        for what in ("shape", "probe", "operands", "sweep_info"):
+            getattr(W, f"xs_streamload_{what}").argtypes = getattr(G, f"xs_load_{what}").argtypes
+        W.xs_streamload_sweep_expected.argtypes = [ctypes.c_uint32] * 5 + [ctypes.POINTER(ctypes.c_uint32)]
+        sweep_types = G.xs_load_sweep.argtypes
+        W.xs_streamload_sweep.argtypes = sweep_types[:5] + [ctypes.c_uint32] * 2 + sweep_types[5:]
+        for name in STREAMLOAD_SYMBOLS:
+            setattr(L, name, getattr(W, name))
         L.xs_hbm_sweep_last_error.restype = ctypes.c_char_p
         L.xs_hbm_sweep_pattern.argtypes = [ctypes.c_uint64, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int,
                                            ctypes.c_void_p]
@@ -1783,6 +1828,74 @@ class HipProbe:
                                (seed, laps), {"seed": seed}, wording=ATTNLOAD_WORDING,
                                tail=lambda w: load_record_tail(w, ATTNLOAD_MASK_WORD))
         out["summary"].update(laps=laps)
+        return out
+
+    # ---------------------------------------------------- stream load sweep
+    def streamload_parts(self) -> list[str]:
+        """Part names of the stream load sweep; the index is the part's bit."""
+        return self._part_names(STREAMLOAD_SWEEP)
+
+    def streamload_shape(self, part: str, laps: int = STREAMLOAD_LAPS) -> dict:
+        """`words` one part has in streamload_probe's dump at `laps`:
+        `fixed_words` whatever the laps plus `words_per_lap` for each."""
+        out = self._part_shape(STREAMLOAD_SWEEP, part, 2)
+        return {"fixed_words": out[0], "words_per_lap": out[1], "words": out[0] + out[1] * max(int(laps), 0)}
+
+    def streamload_operands(self, seed: int = STREAMLOAD_SEED, panel: int = 0, ksteps: int = STREAMLOAD_KSTEPS):
+        """The bytes the arena holds for one panel and those of X, untiled and
+        computed on the host: (Wt int8 [16, 64 ksteps], X int8 [16, 64 ksteps]).
+        No device call."""
+        import numpy as np
+
+        k = 64 * max(int(ksteps), 0)
+        wt, x = np.zeros((16, k), np.int8), np.zeros((16, k), np.int8)
+        self._call("streamload_sweep", "streamload_operands", seed, panel, ksteps, wt.ctypes.data, x.ctypes.data)
+        return wt, x
+
+    def streamload_probe(self, dev: int, parts=None, seed: int = STREAMLOAD_SEED, laps: int = 1,
+                         ksteps: int = STREAMLOAD_KSTEPS, panels: int = 8) -> dict:
+        """k_streamload_probe: one workgroup of 512 threads runs `laps` laps at
+        any legal shape on an arena of its own and stores what it holds:
+        {"gemm": int32 [laps, 128, 16], Ct of every lap with wave w's panel at
+        rows 16 w ..; "stage", "act": uint32 [512], every thread's fold}.
+        `parts` selects which folds are issued (the pipeline always runs)."""
+        import numpy as np
+
+        mask = self._part_mask(STREAMLOAD_SWEEP, parts)
+        c = max(int(laps), 0) * STREAMLOAD_TILE[0] * STREAMLOAD_TILE[1]
+        out = np.zeros(c + 2 * STREAMLOAD_BLOCK, np.uint32)
+        self._call("streamload_sweep", "streamload_probe", dev, mask, seed, laps, ksteps, panels, out.ctypes.data,
+                   out.size, wording=STREAMLOAD_WORDING)
+        folds = out[c:].reshape(2, STREAMLOAD_BLOCK)
+        return {"gemm": out[:c].view(np.int32).reshape(-1, *STREAMLOAD_TILE), "stage": folds[0], "act": folds[1]}
+
+    def streamload_sweep_expected(self, parts=None, seed: int = STREAMLOAD_SEED, laps: int = STREAMLOAD_LAPS,
+                                  ksteps: int = STREAMLOAD_KSTEPS, panels: int = STREAMLOAD_PANELS) -> dict:
+        """The workgroup digest a healthy CU leaves per selected part, computed
+        on the host (the product in plain int32). The first call of a (seed,
+        ksteps, panels) generates the whole arena once, chunk by chunk."""
+        return self._part_expected(STREAMLOAD_SWEEP, parts, seed, laps, ksteps, panels)
+
+    def streamload_sweep_info(self, dev: int = 0) -> dict:
+        """What the runtime reports for k_streamload_sweep: `num_regs`,
+        `scratch_bytes` per lane, `lds_bytes` per workgroup, `blocks_per_cu`."""
+        return self._sweep_info("streamload_sweep", dev, ("num_regs", "scratch_bytes", "lds_bytes", "blocks_per_cu"))
+
+    def streamload_sweep(self, dev: int = 0, blocks: int = 0, parts=None, seed: int = STREAMLOAD_SEED,
+                         laps: int = STREAMLOAD_LAPS, inject: tuple | None = None, max_rounds: int = 4,
+                         ksteps: int = STREAMLOAD_KSTEPS, panels: int = STREAMLOAD_PANELS) -> dict:
+        """k_streamload_sweep: `laps` laps of a checked int8 GEMM of 16 tokens
+        on every CU a workgroup lands on, the weights streamed from an arena of
+        `panels` panels of 16 rows x 64 `ksteps` (the default: 1 GiB, read
+        once by every workgroup; smaller ones are for tests), every selected
+        part (None: all) judged. `inject`, `blocks`, `max_rounds`, the
+        ProbeError with rc STREAMLOAD_UNSWEPT and the result are load_sweep's
+        (`bad_subtiles` are waves and `bad_sets` panels & 31 here). Arena and
+        table are allocated on the device per launch and freed after it."""
+        out = self._part_sweep(STREAMLOAD_SWEEP, summarize_load_sweep, dev, blocks, parts, inject, max_rounds,
+                               (seed, laps, ksteps, panels), {"seed": seed}, wording=STREAMLOAD_WORDING,
+                               tail=lambda w: load_record_tail(w, STREAMLOAD_MASK_WORD))
+        out["summary"].update(laps=laps, ksteps=ksteps, panels=panels)
         return out
 
     # ----------------------------------------------------------- VALU sweep
