@@ -354,12 +354,14 @@ def health_fn_args(args) -> dict:
     --health-matrix-sweep, --health-lane-sweep, --health-valu-sweep,
     --health-scalar-sweep, --health-consensus-sweep, --health-fetch-sweep, --health-mem-sweep,
     --health-load-sweep, --health-mxload-sweep, --health-bfload-sweep, --health-attnload-sweep,
-    --health-streamload-sweep: as _part_list_flag says, but the matrix keys are always there (False, None).
+    --health-streamload-sweep, --health-gradload-sweep: as _part_list_flag says, but the matrix keys are always
+    there (False, None).
     --health-load-sweep-laps: with --health-load-sweep, load_args = {"laps": N};
     --health-mxload-sweep-laps: with --health-mxload-sweep, mxload_args likewise;
     --health-bfload-sweep-laps: with --health-bfload-sweep, bfload_args likewise;
     --health-attnload-sweep-laps: with --health-attnload-sweep, attnload_args likewise;
-    --health-streamload-sweep-laps: with --health-streamload-sweep, streamload_args likewise.
+    --health-streamload-sweep-laps: with --health-streamload-sweep, streamload_args likewise;
+    --health-gradload-sweep-laps: with --health-gradload-sweep, gradload_args likewise.
     --health-hbm-sweep: absent -> no hbm keys, bare -> all free HBM less the
     reserve (hbm_gib None), else that many GiB.
     --health-register-sweep: absent -> no regfile key."""
@@ -375,8 +377,9 @@ def health_fn_args(args) -> dict:
               **_part_list_flag(args, "fetch", "parts"),
               **_part_list_flag(args, "mem", "routes"), **_part_list_flag(args, "load", "parts"),
               **_part_list_flag(args, "mxload", "parts"), **_part_list_flag(args, "bfload", "parts"),
-              **_part_list_flag(args, "attnload", "parts"), **_part_list_flag(args, "streamload", "parts"))
-    for kind in ("load", "mxload", "bfload", "attnload", "streamload"):
+              **_part_list_flag(args, "attnload", "parts"), **_part_list_flag(args, "streamload", "parts"),
+              **_part_list_flag(args, "gradload", "parts"))
+    for kind in ("load", "mxload", "bfload", "attnload", "streamload", "gradload"):
         laps = getattr(args, f"health_{kind}_sweep_laps", None)
         if kw.get(kind) and laps is not None:
             kw[f"{kind}_args"] = {"laps": laps}
@@ -663,6 +666,19 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--health-streamload-sweep-laps", type=int, default=None, metavar="N",
                    help="laps (panels of 16 weight rows per wave) of one --health-streamload-sweep launch; default: "
                         "one round, the whole arena once per workgroup")
+    p.add_argument("--health-gradload-sweep", nargs="?", const="all", default=None, metavar="PARTS",
+                   help="health probe plus the gradient load sweep: stage, transpose, gemm and accum (a checked bf16 "
+                        "weight-gradient GEMM dW = X^T dY on every CU: both operands token-major through the transposed "
+                        "LDS read into v_mfma_f32_32x32x16_bf16, two waves on every SIMD, split-K between two waves "
+                        "through global_atomic_add_f32 into device memory, read back and cleared with "
+                        "global_atomic_swap after every epoch, every register partial and every accumulated sum "
+                        "compared on the device by equality; a comma list selects what is judged, default all); its "
+                        "slabs (512 MiB) are held for the length of the launch only; it runs directly after the stream "
+                        "load sweep, last of all, a bad XCD is fenced like --health-sweep's and its parts are published "
+                        "as gradLoadFaults. Implies --health-probe; independent of the other sweeps")
+    p.add_argument("--health-gradload-sweep-laps", type=int, default=None, metavar="N",
+                   help="laps (gradient tiles per workgroup) of one --health-gradload-sweep launch; default: "
+                        "the measured one")
     p.add_argument("--health-mem-sweep", nargs="?", const="all", default=None, metavar="ROUTES",
                    help="health probe plus the memory-path sweep: gwidth, buffer, flat, atomic, l1, l2 and scalar (global, "
                         "buffer and flat loads and stores of every width, the memory-side atomics, the vector L1, the "

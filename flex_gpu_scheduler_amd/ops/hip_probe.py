@@ -64,14 +64,22 @@ Sweeps of every CU (csrc/hip/<name>.hip), each naming the XCD of a CU that fails
     weights stream from an arena of HBM size through a register ring straight
     into v_mfma_i32_16x16x64_i8, the activations from LDS; every sum one exact
     int32, compared after each lap; names the parts (stage, act, gemm). A
-    library of its own, _hipstreamload.so.
+    library of its own, _hipstreamload.so;
+  * gradload_sweep: the same under a checked bf16 weight-gradient GEMM
+    dW = X^T dY in the TN layout: both operands through ds_read_b64_tr_b16,
+    split-K between two waves through global_atomic_add_f32 into a slab in
+    device memory, which is read back and cleared with global_atomic_swap
+    after every epoch; every sum one exact float, the register partials
+    compared after each lap and the slab after each epoch; names the parts
+    (stage, transpose, gemm, accum). A library of its own, _hipgradload.so.
 The matrix, lane, VALU and memory sweeps are sweeps over named parts:
 PART_SWEEPS describes each, and one implementation serves the four and the
 scalar sweep, whose row SCALAR_SWEEP stands beside the table, as do
 CONSENSUS_SWEEP, the consensus sweep's, FETCH_SWEEP, the fetch sweep's,
 LOAD_SWEEP, the load sweep's, MXLOAD_SWEEP, the MX load sweep's,
 BFLOAD_SWEEP, the bf16 load sweep's, ATTNLOAD_SWEEP, the attention load
-sweep's, and STREAMLOAD_SWEEP, the stream load sweep's.
+sweep's, STREAMLOAD_SWEEP, the stream load sweep's, and GRADLOAD_SWEEP, the
+gradient load sweep's.
 
 hbm_sweep (csrc/hip/hbm_sweep.hip): all free HBM under an address-keyed
 pattern in both polarities; names the vectors and bits that read back wrong.
@@ -103,6 +111,8 @@ _BFLOAD_LIB = Path(__file__).resolve().parent / "_hipbfload.so"
 _ATTNLOAD_LIB = Path(__file__).resolve().parent / "_hipattnload.so"
 # And the stream load sweep.
 _STREAMLOAD_LIB = Path(__file__).resolve().parent / "_hipstreamload.so"
+# And the gradient load sweep.
+_GRADLOAD_LIB = Path(__file__).resolve().parent / "_hipgradload.so"
 MODES = {"read": 0, "write": 1, "copy": 2, "triad": 3}
 
 
@@ -320,6 +330,27 @@ STREAMLOAD_SYMBOLS = ("xs_streamload_sweep_last_error", "xs_streamload_parts", "
                       "xs_streamload_probe", "xs_streamload_sweep_expected", "xs_streamload_sweep_info",
                       "xs_streamload_sweep", "xs_streamload_operands")
 
+# k_gradload_sweep (csrc/hip/gradload_sweep.hip): one 128-byte record per workgroup,
+# laid out as k_load_sweep's: four parts and the three masks.
+GRADLOAD_RECORD_WORDS = 32
+GRADLOAD_SEED = 0x2C1B3C6D
+GRADLOAD_BLOCK = 512  # threads per workgroup: 8 waves, two on every SIMD
+GRADLOAD_LAPS = 2048  # macro tiles per workgroup and launch; measured in profiles/gradload_sweep_defaults.md
+GRADLOAD_KSTEPS = 8  # the sweep's shape: K = 32 x 8 = 256 tokens per lap
+GRADLOAD_EPOCH = 32  # laps that accumulate in a slab before it is read back and cleared
+GRADLOAD_MAX_TOKENS = 32 * 257  # of an epoch (epoch x ksteps <= 257): beyond it a sum may leave 2^24 units
+GRADLOAD_SLABS = 8  # slabs of 64 KiB per workgroup: 512 MiB at 4 workgroups per CU
+GRADLOAD_SETS = 32  # operand sets of 128 KiB at the sweep's shape, in groups of `epoch`
+GRADLOAD_TILE = (128, 128)  # dW of one lap
+GRADLOAD_MASK_WORD = LOAD_MASK_WORD  # the first of the three mask words
+# xs_gradload_sweep could not allocate its arena, its tables or its slabs: nothing was launched.
+GRADLOAD_UNSWEPT = LOAD_UNSWEPT
+GRADLOAD_WORDING = LOAD_WORDING
+# The C ABI of _hipgradload.so.
+GRADLOAD_SYMBOLS = ("xs_gradload_sweep_last_error", "xs_gradload_parts", "xs_gradload_shape", "xs_gradload_probe",
+                    "xs_gradload_sweep_expected", "xs_gradload_sweep_info", "xs_gradload_sweep",
+                    "xs_gradload_operands")
+
 
 @dataclass(frozen=True)
 class PartSweep:
@@ -375,6 +406,9 @@ ATTNLOAD_SWEEP = PartSweep("attnload", "xs_attnload_parts", "attention load part
 # And the stream load sweep's: the same head with three parts.
 STREAMLOAD_SWEEP = PartSweep("streamload", "xs_streamload_parts", "stream load part", "failed_parts", "parts",
                              STREAMLOAD_RECORD_WORDS, digests=7, bad=4, bad_simds=10)
+# And the gradient load sweep's: the load sweep's head, four parts.
+GRADLOAD_SWEEP = PartSweep("gradload", "xs_gradload_parts", "gradient load part", "failed_parts", "parts",
+                           GRADLOAD_RECORD_WORDS, digests=8, bad=4, bad_simds=12)
 
 # k_hbm_fill / k_hbm_verify (csrc/hip/hbm_sweep.hip)
 HBM_SWEEP_SEED = 0x5EED1E55
@@ -491,9 +525,10 @@ class HipProbe:
                  scalar_path: str | Path = _SCALAR_LIB, consensus_path: str | Path = _CONSENSUS_LIB,
                  fetch_path: str | Path = _FETCH_LIB, load_path: str | Path = _LOAD_LIB,
                  mxload_path: str | Path = _MXLOAD_LIB, bfload_path: str | Path = _BFLOAD_LIB,
-                 attnload_path: str | Path = _ATTNLOAD_LIB, streamload_path: str | Path = _STREAMLOAD_LIB):
+                 attnload_path: str | Path = _ATTNLOAD_LIB, streamload_path: str | Path = _STREAMLOAD_LIB,
+                 gradload_path: str | Path = _GRADLOAD_LIB):
         for built in (path, mem_path, scalar_path, consensus_path, fetch_path, load_path, mxload_path, bfload_path,
-                      attnload_path, streamload_path):
+                      attnload_path, streamload_path, gradload_path):
             if not Path(built).exists():
                 raise ProbeError(f"{built} not built; run `python -m flex_gpu_scheduler_amd.build_ext --hip`")
         try:
@@ -711,6 +746,19 @@ class HipProbe:
         W.xs_streamload_sweep.argtypes = sweep_types[:5] + [ctypes.c_uint32] * 2 + sweep_types[5:]
         for name in STREAMLOAD_SYMBOLS:
             setattr(L, name, getattr(W, name))
+        # gradload_sweep.hip's library, likewise: the load sweep's signatures, with ksteps, epoch and slabs behind
+        # the laps of the sweep, of its expected digests and of the probe.
+        self.gradload_lib = ctypes.CDLL(str(gradload_path))
+        D = self.gradload_lib
+        D.xs_gradload_sweep_last_error.restype = ctypes.c_char_p
+        D.xs_gradload_parts.restype = ctypes.c_char_p
+        for what in ("shape", "operands", "sweep_info"):
+            getattr(D, f"xs_gradload_{what}").argtypes = getattr(G, f"xs_load_{what}").argtypes
+        D.xs_gradload_probe.argtypes = [ctypes.c_int] + [ctypes.c_uint32] * 6 + [ctypes.c_void_p, ctypes.c_size_t]
+        D.xs_gradload_sweep_expected.argtypes = [ctypes.c_uint32] * 6 + [ctypes.POINTER(ctypes.c_uint32)]
+        D.xs_gradload_sweep.argtypes = sweep_types[:5] + [ctypes.c_uint32] * 3 + sweep_types[5:]
+        for name in GRADLOAD_SYMBOLS:
+            setattr(L, name, getattr(D, name))
         L.xs_hbm_sweep_last_error.restype = ctypes.c_char_p
         L.xs_hbm_sweep_pattern.argtypes = [ctypes.c_uint64, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int,
                                            ctypes.c_void_p]
@@ -1896,6 +1944,75 @@ class HipProbe:
                                (seed, laps, ksteps, panels), {"seed": seed}, wording=STREAMLOAD_WORDING,
                                tail=lambda w: load_record_tail(w, STREAMLOAD_MASK_WORD))
         out["summary"].update(laps=laps, ksteps=ksteps, panels=panels)
+        return out
+
+    # -------------------------------------------------- gradient load sweep
+    def gradload_parts(self) -> list[str]:
+        """Part names of the gradient load sweep; the index is the part's bit."""
+        return self._part_names(GRADLOAD_SWEEP)
+
+    def gradload_operands(self, seed: int = GRADLOAD_SEED, set_: int = 0, ksteps: int = GRADLOAD_KSTEPS):
+        """The bf16 bits of one operand set, computed on the host: (X uint16
+        [32 ksteps, 128], dY uint16 [32 ksteps, 128]), token-major both. No
+        device call."""
+        import numpy as np
+
+        k = 32 * max(int(ksteps), 0)
+        x, dy = np.zeros((k, GRADLOAD_TILE[0]), np.uint16), np.zeros((k, GRADLOAD_TILE[1]), np.uint16)
+        self._call("gradload_sweep", "gradload_operands", seed, set_, ksteps, x.ctypes.data, dy.ctypes.data)
+        return x, dy
+
+    def gradload_probe(self, dev: int, parts=None, seed: int = GRADLOAD_SEED, laps: int = 1,
+                       ksteps: int = GRADLOAD_KSTEPS, epoch: int = GRADLOAD_EPOCH, slabs: int = 1) -> dict:
+        """k_gradload_probe: one workgroup of 512 threads runs `laps` laps at
+        any legal shape (epoch x ksteps <= 257) and stores what it holds:
+        {"gemm": float32 [laps, 2, 128, 128], the register partials of either
+        k-half; "accum": float32 [epochs, 128, 128], the slab as read back
+        after every epoch, the last of which may be partial; "stage",
+        "transpose": uint32 [512], every thread's fold}. `parts` selects which
+        folds are issued (the pipeline always runs)."""
+        import numpy as np
+
+        mask = self._part_mask(GRADLOAD_SWEEP, parts)
+        n, tile = max(int(laps), 0), GRADLOAD_TILE[0] * GRADLOAD_TILE[1]
+        epochs = -(-n // max(int(epoch), 1))
+        out = np.zeros((2 * n + epochs) * tile + 2 * GRADLOAD_BLOCK, np.uint32)
+        self._call("gradload_sweep", "gradload_probe", dev, mask, seed, laps, ksteps, epoch, slabs, out.ctypes.data,
+                   out.size, wording=GRADLOAD_WORDING)
+        floats, folds = out[:(2 * n + epochs) * tile].view(np.float32), out[(2 * n + epochs) * tile:]
+        return {"gemm": floats[:2 * n * tile].reshape(n, 2, *GRADLOAD_TILE),
+                "accum": floats[2 * n * tile:].reshape(epochs, *GRADLOAD_TILE),
+                "stage": folds[:GRADLOAD_BLOCK], "transpose": folds[GRADLOAD_BLOCK:]}
+
+    def gradload_sweep_expected(self, parts=None, seed: int = GRADLOAD_SEED, laps: int = GRADLOAD_LAPS,
+                                ksteps: int = GRADLOAD_KSTEPS, epoch: int = GRADLOAD_EPOCH,
+                                slabs: int = GRADLOAD_SLABS) -> dict:
+        """The workgroup digest a healthy CU leaves per selected part, computed
+        on the host (dW 2^7 in plain int32). ProbeError with rc -1000 when
+        epoch x ksteps is above 257: a sum could leave the exact range."""
+        return self._part_expected(GRADLOAD_SWEEP, parts, seed, laps, ksteps, epoch, slabs)
+
+    def gradload_sweep_info(self, dev: int = 0) -> dict:
+        """What the runtime reports for k_gradload_sweep: `num_regs`,
+        `scratch_bytes` per lane, `lds_bytes` per workgroup, `blocks_per_cu`."""
+        return self._sweep_info("gradload_sweep", dev, ("num_regs", "scratch_bytes", "lds_bytes", "blocks_per_cu"))
+
+    def gradload_sweep(self, dev: int = 0, blocks: int = 0, parts=None, seed: int = GRADLOAD_SEED,
+                       laps: int = GRADLOAD_LAPS, inject: tuple | None = None, max_rounds: int = 4,
+                       ksteps: int = GRADLOAD_KSTEPS, epoch: int = GRADLOAD_EPOCH,
+                       slabs: int = GRADLOAD_SLABS) -> dict:
+        """k_gradload_sweep: `laps` laps of a checked bf16 weight-gradient GEMM
+        (128 x 128, K = 32 `ksteps` tokens, TN layout) on every CU a workgroup
+        lands on, split-K through float atomics into one of `slabs` slabs of 64
+        KiB per workgroup, read back and cleared every `epoch` laps; every
+        selected part (None: all) judged. `inject`, `blocks`, `max_rounds`, the
+        ProbeError with rc GRADLOAD_UNSWEPT and the result are load_sweep's.
+        Arena, tables and slabs are allocated on the device per launch and
+        freed after it."""
+        out = self._part_sweep(GRADLOAD_SWEEP, summarize_load_sweep, dev, blocks, parts, inject, max_rounds,
+                               (seed, laps, ksteps, epoch, slabs), {"seed": seed}, wording=GRADLOAD_WORDING,
+                               tail=load_record_tail)
+        out["summary"].update(laps=laps, ksteps=ksteps, epoch=epoch, slabs=slabs)
         return out
 
     # ----------------------------------------------------------- VALU sweep
