@@ -4,7 +4,8 @@ sweep's `ops/_hipscalar`, the consensus sweep's `ops/_hipconsensus`, the
 fetch sweep's `ops/_hipfetch`, the load sweep's `ops/_hipload`, the MX load
 sweep's `ops/_hipmxload`, the bf16 load sweep's `ops/_hipbfload`, the
 attention load sweep's `ops/_hipattnload`, the stream load sweep's
-`ops/_hipstreamload` and the gradient load sweep's `ops/_hipgradload`).
+`ops/_hipstreamload`, the gradient load sweep's `ops/_hipgradload` and the FP8
+load sweep's `ops/_hipf8load`).
 
 Both land next to the Python sources (not site-packages) so the built `.so`
 files travel with the repo snapshot to the MI355X box and show up as loaded
@@ -158,15 +159,16 @@ def build_hip(verbose: bool = True) -> Path | None:
     attnload = [s for s in srcs if s.name == "attnload_sweep.hip"]  # ops/_hipattnload.so, likewise
     streamload = [s for s in srcs if s.name == "streamload_sweep.hip"]  # ops/_hipstreamload.so, likewise
     gradload = [s for s in srcs if s.name == "gradload_sweep.hip"]  # ops/_hipgradload.so, likewise
+    f8load = [s for s in srcs if s.name == "f8load_sweep.hip"]  # ops/_hipf8load.so, likewise
     out = PKG / "ops" / "_hipprobe.so"
-    apart = mem + scalar + consensus + fetch + load + mxload + bfload + attnload + streamload + gradload
+    apart = mem + scalar + consensus + fetch + load + mxload + bfload + attnload + streamload + gradload + f8load
     for lib, lib_srcs in ((out, [s for s in srcs if s not in apart]),
                           (PKG / "ops" / "_hipmem.so", mem), (PKG / "ops" / "_hipscalar.so", scalar),
                           (PKG / "ops" / "_hipconsensus.so", consensus), (PKG / "ops" / "_hipfetch.so", fetch),
                           (PKG / "ops" / "_hipload.so", load), (PKG / "ops" / "_hipmxload.so", mxload),
                           (PKG / "ops" / "_hipbfload.so", bfload), (PKG / "ops" / "_hipattnload.so", attnload),
                           (PKG / "ops" / "_hipstreamload.so", streamload),
-                          (PKG / "ops" / "_hipgradload.so", gradload)):
+                          (PKG / "ops" / "_hipgradload.so", gradload), (PKG / "ops" / "_hipf8load.so", f8load)):
         newest = max([s.stat().st_mtime for s in lib_srcs] + [_headers_mtime()])
         if lib.exists() and lib.stat().st_mtime >= newest:
             continue

@@ -354,14 +354,15 @@ def health_fn_args(args) -> dict:
     --health-matrix-sweep, --health-lane-sweep, --health-valu-sweep,
     --health-scalar-sweep, --health-consensus-sweep, --health-fetch-sweep, --health-mem-sweep,
     --health-load-sweep, --health-mxload-sweep, --health-bfload-sweep, --health-attnload-sweep,
-    --health-streamload-sweep, --health-gradload-sweep: as _part_list_flag says, but the matrix keys are always
-    there (False, None).
+    --health-streamload-sweep, --health-gradload-sweep, --health-f8load-sweep: as _part_list_flag says, but the
+    matrix keys are always there (False, None).
     --health-load-sweep-laps: with --health-load-sweep, load_args = {"laps": N};
     --health-mxload-sweep-laps: with --health-mxload-sweep, mxload_args likewise;
     --health-bfload-sweep-laps: with --health-bfload-sweep, bfload_args likewise;
     --health-attnload-sweep-laps: with --health-attnload-sweep, attnload_args likewise;
     --health-streamload-sweep-laps: with --health-streamload-sweep, streamload_args likewise;
-    --health-gradload-sweep-laps: with --health-gradload-sweep, gradload_args likewise.
+    --health-gradload-sweep-laps: with --health-gradload-sweep, gradload_args likewise;
+    --health-f8load-sweep-laps: with --health-f8load-sweep, f8load_args likewise.
     --health-hbm-sweep: absent -> no hbm keys, bare -> all free HBM less the
     reserve (hbm_gib None), else that many GiB.
     --health-register-sweep: absent -> no regfile key."""
@@ -378,8 +379,8 @@ def health_fn_args(args) -> dict:
               **_part_list_flag(args, "mem", "routes"), **_part_list_flag(args, "load", "parts"),
               **_part_list_flag(args, "mxload", "parts"), **_part_list_flag(args, "bfload", "parts"),
               **_part_list_flag(args, "attnload", "parts"), **_part_list_flag(args, "streamload", "parts"),
-              **_part_list_flag(args, "gradload", "parts"))
-    for kind in ("load", "mxload", "bfload", "attnload", "streamload", "gradload"):
+              **_part_list_flag(args, "gradload", "parts"), **_part_list_flag(args, "f8load", "parts"))
+    for kind in ("load", "mxload", "bfload", "attnload", "streamload", "gradload", "f8load"):
         laps = getattr(args, f"health_{kind}_sweep_laps", None)
         if kw.get(kind) and laps is not None:
             kw[f"{kind}_args"] = {"laps": laps}
@@ -679,6 +680,18 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--health-gradload-sweep-laps", type=int, default=None, metavar="N",
                    help="laps (gradient tiles per workgroup) of one --health-gradload-sweep launch; default: "
                         "the measured one")
+    p.add_argument("--health-f8load-sweep", nargs="?", const="all", default=None, metavar="PARTS",
+                   help="health probe plus the FP8 load sweep: operand, gemm, round and store (a checked rowwise-scaled "
+                        "FP8 GEMM with bf16 output on every CU: e4m3 operands by LDS DMA into the unscaled "
+                        "v_mfma_f32_32x32x64_f8f6f4, two waves on every SIMD, and a production epilogue: scale, "
+                        "v_cvt_pk_bf16_f32, a transpose through LDS and global_store_dwordx4 of every tile to a ring in "
+                        "device memory, read back by another wave some laps later; every sum, every rounded pair and "
+                        "every word read back compared on the device by equality; a comma list selects what is judged, "
+                        "default all); its ring (512 MiB) is held for the length of the launch only; it runs directly "
+                        "after the gradient load sweep, last of all, a bad XCD is fenced like --health-sweep's and its "
+                        "parts are published as f8LoadFaults. Implies --health-probe; independent of the other sweeps")
+    p.add_argument("--health-f8load-sweep-laps", type=int, default=None, metavar="N",
+                   help="laps (macro tiles per workgroup) of one --health-f8load-sweep launch; default: the measured one")
     p.add_argument("--health-mem-sweep", nargs="?", const="all", default=None, metavar="ROUTES",
                    help="health probe plus the memory-path sweep: gwidth, buffer, flat, atomic, l1, l2 and scalar (global, "
                         "buffer and flat loads and stores of every width, the memory-side atomics, the vector L1, the "

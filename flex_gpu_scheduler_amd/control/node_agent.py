@@ -147,6 +147,9 @@ STREAMLOAD_SWEEP_KIND = SweepKind("streamload", "streamload_sweep", "streamload"
 # And the gradient load sweep directly after that one: now it is the last of all.
 GRADLOAD_SWEEP_KIND = SweepKind("gradload", "gradload_sweep", "gradload", "gradLoadSweep", "parts", "gradLoadFaults",
                                 lambda v: list(v["failed_parts"]))
+# And the FP8 load sweep directly after that one: now it is the last of all.
+F8LOAD_SWEEP_KIND = SweepKind("f8load", "f8load_sweep", "f8load", "f8LoadSweep", "parts", "f8LoadFaults",
+                              lambda v: list(v["failed_parts"]))
 
 FAULT_KINDS = {
     # What the per-CU sweeps found on a faulty XCD. Informational: the XCD is
@@ -178,6 +181,8 @@ FAULT_KINDS = {
     STREAMLOAD_SWEEP_KIND.faults_key: FaultKind(per_xcd=False),
     # What the gradient load sweep found on the GPU: {XCD id: [part, ...]}, likewise.
     GRADLOAD_SWEEP_KIND.faults_key: FaultKind(per_xcd=False),
+    # What the FP8 load sweep found on the GPU: {XCD id: [part, ...]}, likewise.
+    F8LOAD_SWEEP_KIND.faults_key: FaultKind(per_xcd=False),
 }
 
 
@@ -532,19 +537,20 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
                   bfload_args: dict | None = None, attnload: bool = False, attnload_parts: list | None = None,
                   attnload_args: dict | None = None, streamload: bool = False, streamload_parts: list | None = None,
                   streamload_args: dict | None = None, gradload: bool = False, gradload_parts: list | None = None,
-                  gradload_args: dict | None = None) -> Callable[[int], "bool | GpuHealth"]:
+                  gradload_args: dict | None = None, f8load: bool = False, f8load_parts: list | None = None,
+                  f8load_args: dict | None = None) -> Callable[[int], "bool | GpuHealth"]:
     """Health callback backed by the HIP probes (HBM pattern + checksum and an
     MFMA tile check per GPU).
 
     Each kind of SWEEP_KINDS, SCALAR_SWEEP_KIND, CONSENSUS_SWEEP_KIND, FETCH_SWEEP_KIND, MEM_SWEEP_KIND,
-    LOAD_SWEEP_KIND, MXLOAD_SWEEP_KIND, BFLOAD_SWEEP_KIND, ATTNLOAD_SWEEP_KIND, STREAMLOAD_SWEEP_KIND and
-    GRADLOAD_SWEEP_KIND, in the order they run,
+    LOAD_SWEEP_KIND, MXLOAD_SWEEP_KIND, BFLOAD_SWEEP_KIND, ATTNLOAD_SWEEP_KIND, STREAMLOAD_SWEEP_KIND,
+    GRADLOAD_SWEEP_KIND and F8LOAD_SWEEP_KIND, in the order they run,
     has a switch `<kind>` that also runs that per-CU sweep of HipProbe (`sweep`: the CU sweep), `<kind>_args` for its keywords
     and, where it sweeps named parts, `<kind>_<parts>` to select some (None for
     all). Its summary and, the CU sweep apart, its {xcd: fault} go into the
     verdict's detail under the kind's keys. A fault is the list of the failed
     formats, paths, units, scalar parts, consensus parts, fetch parts, routes, load parts, MX load parts, bf16 load parts
-    attention load parts, stream load parts or gradient load parts;
+    attention load parts, stream load parts, gradient load parts or FP8 load parts;
     of `regfile`, {"files": [...], "cells": n,
     "flipMask": "0x...", "simds": n}. The VALU sweep's failed steps are in
     detail["valuSweep"]. The consensus sweep judges a CU by the vote of the
@@ -554,14 +560,16 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
     MX load sweep, the bf16 load sweep and the attention load sweep an arena
     and a table each for the life of the process, the stream load sweep an
     arena of HBM size and the gradient load sweep its arena, tables and slabs
-    (512 MiB by default) for the length of one launch;
+    (512 MiB by default) for the length of one launch, the FP8 load sweep an
+    arena and tables for the life of the process and its ring (512 MiB by
+    default) for the length of one launch;
     where that cannot be had the device is logged as unswept, which neither
     fails it nor touches the other sweeps' verdicts. The load sweep and, behind
     it, the MX load sweep, the bf16 load sweep, the attention load sweep, the
-    stream load sweep and the gradient load sweep run last: they heat the part
+    stream load sweep, the gradient load sweep and the FP8 load sweep run last: they heat the part
     (`load_args={"laps": n}`, `mxload_args={"laps": n}`, `bfload_args={"laps": n}`,
-    `attnload_args={"laps": n}`, `streamload_args={"laps": n}` and
-    `gradload_args={"laps": n}` set their lengths).
+    `attnload_args={"laps": n}`, `streamload_args={"laps": n}`,
+    `gradload_args={"laps": n}` and `f8load_args={"laps": n}` set their lengths).
     The callback runs on every heartbeat, so the sweeps' verdict is reused for
     `sweep_period_s`. On a device that shows all 8 XCDs the verdict is a
     GpuHealth naming the bad physical XCDs of any of these sweeps; a
@@ -580,8 +588,8 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
     memory could be had is logged as unswept and a sweep that got less than it
     asked for as short; neither fails the device."""
     given = locals()  # the parameters by name, for SWEEP_KINDS
-    from ..ops.hip_probe import (ATTNLOAD_UNSWEPT, BFLOAD_UNSWEPT, GRADLOAD_UNSWEPT, HBM_UNSWEPT, LOAD_UNSWEPT,
-                                 MEM_UNSWEPT, MXLOAD_UNSWEPT, STREAMLOAD_UNSWEPT, ProbeError, probe)
+    from ..ops.hip_probe import (ATTNLOAD_UNSWEPT, BFLOAD_UNSWEPT, F8LOAD_UNSWEPT, GRADLOAD_UNSWEPT, HBM_UNSWEPT,
+                                 LOAD_UNSWEPT, MEM_UNSWEPT, MXLOAD_UNSWEPT, STREAMLOAD_UNSWEPT, ProbeError, probe)
 
     p = probe()
     last: dict[int, tuple[float, object]] = {}  # dev -> (monotonic time, sweep verdict)
@@ -590,11 +598,13 @@ def hip_health_fn(sweep: bool = False, sweep_period_s: float = 600.0, sweep_args
                           **(given[f"{k.enabled_by}_args"] or {})})
                      for k in SWEEP_KINDS + (SCALAR_SWEEP_KIND, CONSENSUS_SWEEP_KIND, FETCH_SWEEP_KIND, MEM_SWEEP_KIND,
                                              LOAD_SWEEP_KIND, MXLOAD_SWEEP_KIND, BFLOAD_SWEEP_KIND,
-                                             ATTNLOAD_SWEEP_KIND, STREAMLOAD_SWEEP_KIND, GRADLOAD_SWEEP_KIND)
+                                             ATTNLOAD_SWEEP_KIND, STREAMLOAD_SWEEP_KIND, GRADLOAD_SWEEP_KIND,
+                                             F8LOAD_SWEEP_KIND)
                      if given[k.enabled_by]]
     unswept = {MEM_SWEEP_KIND: MEM_UNSWEPT, LOAD_SWEEP_KIND: LOAD_UNSWEPT, MXLOAD_SWEEP_KIND: MXLOAD_UNSWEPT,
                BFLOAD_SWEEP_KIND: BFLOAD_UNSWEPT, ATTNLOAD_SWEEP_KIND: ATTNLOAD_UNSWEPT,
-               STREAMLOAD_SWEEP_KIND: STREAMLOAD_UNSWEPT, GRADLOAD_SWEEP_KIND: GRADLOAD_UNSWEPT}
+               STREAMLOAD_SWEEP_KIND: STREAMLOAD_UNSWEPT, GRADLOAD_SWEEP_KIND: GRADLOAD_UNSWEPT,
+               F8LOAD_SWEEP_KIND: F8LOAD_UNSWEPT}
 
     def sweep_verdict(dev: int):
         now = time.monotonic()

@@ -71,15 +71,23 @@ Sweeps of every CU (csrc/hip/<name>.hip), each naming the XCD of a CU that fails
     device memory, which is read back and cleared with global_atomic_swap
     after every epoch; every sum one exact float, the register partials
     compared after each lap and the slab after each epoch; names the parts
-    (stage, transpose, gemm, accum). A library of its own, _hipgradload.so.
+    (stage, transpose, gemm, accum). A library of its own, _hipgradload.so;
+  * f8load_sweep: the same under a checked rowwise-scaled FP8 GEMM
+    Y = bf16((A Bt^T) sa sb): e4m3 operands of four binades from memory by LDS
+    DMA into the unscaled v_mfma_f32_32x32x64_f8f6f4, every sum one exact
+    float; the epilogue scales, packs with v_cvt_pk_bf16_f32, transposes
+    through LDS and stores every tile to a ring in device memory with
+    global_store_dwordx4, and another wave reads it back `slots` laps later;
+    names the parts (operand, gemm, round, store). A library of its own,
+    _hipf8load.so.
 The matrix, lane, VALU and memory sweeps are sweeps over named parts:
 PART_SWEEPS describes each, and one implementation serves the four and the
 scalar sweep, whose row SCALAR_SWEEP stands beside the table, as do
 CONSENSUS_SWEEP, the consensus sweep's, FETCH_SWEEP, the fetch sweep's,
 LOAD_SWEEP, the load sweep's, MXLOAD_SWEEP, the MX load sweep's,
 BFLOAD_SWEEP, the bf16 load sweep's, ATTNLOAD_SWEEP, the attention load
-sweep's, STREAMLOAD_SWEEP, the stream load sweep's, and GRADLOAD_SWEEP, the
-gradient load sweep's.
+sweep's, STREAMLOAD_SWEEP, the stream load sweep's, GRADLOAD_SWEEP, the gradient
+load sweep's, and F8LOAD_SWEEP, the FP8 load sweep's.
 
 hbm_sweep (csrc/hip/hbm_sweep.hip): all free HBM under an address-keyed
 pattern in both polarities; names the vectors and bits that read back wrong.
@@ -113,6 +121,8 @@ _ATTNLOAD_LIB = Path(__file__).resolve().parent / "_hipattnload.so"
 _STREAMLOAD_LIB = Path(__file__).resolve().parent / "_hipstreamload.so"
 # And the gradient load sweep.
 _GRADLOAD_LIB = Path(__file__).resolve().parent / "_hipgradload.so"
+# And the FP8 load sweep.
+_F8LOAD_LIB = Path(__file__).resolve().parent / "_hipf8load.so"
 MODES = {"read": 0, "write": 1, "copy": 2, "triad": 3}
 
 
@@ -351,6 +361,26 @@ GRADLOAD_SYMBOLS = ("xs_gradload_sweep_last_error", "xs_gradload_parts", "xs_gra
                     "xs_gradload_sweep_expected", "xs_gradload_sweep_info", "xs_gradload_sweep",
                     "xs_gradload_operands")
 
+# k_f8load_sweep (csrc/hip/f8load_sweep.hip): one 128-byte record per workgroup,
+# laid out as k_load_sweep's: four parts and the three masks.
+F8LOAD_RECORD_WORDS = 32
+F8LOAD_SEED = 0x3C6EF372
+F8LOAD_BLOCK = 512  # threads per workgroup: 8 waves, two on every SIMD
+F8LOAD_LAPS = 2048  # macro tiles per workgroup and launch; measured in profiles/f8load_sweep_defaults.md
+F8LOAD_KSTEPS = 16  # the sweep's shape: K = 64 x 16 = 1,024 e4m3
+F8LOAD_MAX_KSTEPS = 18  # K = 1,152: beyond it a sum may leave the 2^24 units a float holds exactly
+F8LOAD_SLOTS = 8  # ring slots of 64 KiB per workgroup: 512 MiB at 4 workgroups per CU
+F8LOAD_MAX_SLOTS = 16
+F8LOAD_SETS = 16  # operand sets of 384 KiB at the sweep's shape
+F8LOAD_TILE = LOAD_TILE  # C of one lap; Y is as many bf16
+F8LOAD_MASK_WORD = LOAD_MASK_WORD  # the first of the three mask words
+# xs_f8load_sweep could not allocate its arena, its tables or its ring: nothing was launched.
+F8LOAD_UNSWEPT = LOAD_UNSWEPT
+F8LOAD_WORDING = LOAD_WORDING
+# The C ABI of _hipf8load.so.
+F8LOAD_SYMBOLS = ("xs_f8load_sweep_last_error", "xs_f8load_parts", "xs_f8load_shape", "xs_f8load_probe",
+                  "xs_f8load_sweep_expected", "xs_f8load_sweep_info", "xs_f8load_sweep", "xs_f8load_operands")
+
 
 @dataclass(frozen=True)
 class PartSweep:
@@ -409,6 +439,9 @@ STREAMLOAD_SWEEP = PartSweep("streamload", "xs_streamload_parts", "stream load p
 # And the gradient load sweep's: the load sweep's head, four parts.
 GRADLOAD_SWEEP = PartSweep("gradload", "xs_gradload_parts", "gradient load part", "failed_parts", "parts",
                            GRADLOAD_RECORD_WORDS, digests=8, bad=4, bad_simds=12)
+# And the FP8 load sweep's: likewise.
+F8LOAD_SWEEP = PartSweep("f8load", "xs_f8load_parts", "FP8 load part", "failed_parts", "parts", F8LOAD_RECORD_WORDS,
+                         digests=8, bad=4, bad_simds=12)
 
 # k_hbm_fill / k_hbm_verify (csrc/hip/hbm_sweep.hip)
 HBM_SWEEP_SEED = 0x5EED1E55
@@ -526,9 +559,9 @@ class HipProbe:
                  fetch_path: str | Path = _FETCH_LIB, load_path: str | Path = _LOAD_LIB,
                  mxload_path: str | Path = _MXLOAD_LIB, bfload_path: str | Path = _BFLOAD_LIB,
                  attnload_path: str | Path = _ATTNLOAD_LIB, streamload_path: str | Path = _STREAMLOAD_LIB,
-                 gradload_path: str | Path = _GRADLOAD_LIB):
+                 gradload_path: str | Path = _GRADLOAD_LIB, f8load_path: str | Path = _F8LOAD_LIB):
         for built in (path, mem_path, scalar_path, consensus_path, fetch_path, load_path, mxload_path, bfload_path,
-                      attnload_path, streamload_path, gradload_path):
+                      attnload_path, streamload_path, gradload_path, f8load_path):
             if not Path(built).exists():
                 raise ProbeError(f"{built} not built; run `python -m flex_gpu_scheduler_amd.build_ext --hip`")
         try:
@@ -759,6 +792,20 @@ class HipProbe:
         D.xs_gradload_sweep.argtypes = sweep_types[:5] + [ctypes.c_uint32] * 3 + sweep_types[5:]
         for name in GRADLOAD_SYMBOLS:
             setattr(L, name, getattr(D, name))
+        # f8load_sweep.hip's library, likewise: the load sweep's signatures (the probe's last number is its slots),
+        # with ksteps and slots behind the laps of the sweep and of its expected digests, and the operands' two
+        # scale arrays.
+        self.f8load_lib = ctypes.CDLL(str(f8load_path))
+        E = self.f8load_lib
+        E.xs_f8load_sweep_last_error.restype = ctypes.c_char_p
+        E.xs_f8load_parts.restype = ctypes.c_char_p
+        E.xs_f8load_operands.argtypes = [ctypes.c_uint32] * 3 + [ctypes.c_void_p] * 4
+        for what in ("shape", "probe", "sweep_info"):
+            getattr(E, f"xs_f8load_{what}").argtypes = getattr(G, f"xs_load_{what}").argtypes
+        E.xs_f8load_sweep_expected.argtypes = [ctypes.c_uint32] * 5 + [ctypes.POINTER(ctypes.c_uint32)]
+        E.xs_f8load_sweep.argtypes = sweep_types[:5] + [ctypes.c_uint32] * 2 + sweep_types[5:]
+        for name in F8LOAD_SYMBOLS:
+            setattr(L, name, getattr(E, name))
         L.xs_hbm_sweep_last_error.restype = ctypes.c_char_p
         L.xs_hbm_sweep_pattern.argtypes = [ctypes.c_uint64, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int,
                                            ctypes.c_void_p]
@@ -2013,6 +2060,75 @@ class HipProbe:
                                (seed, laps, ksteps, epoch, slabs), {"seed": seed}, wording=GRADLOAD_WORDING,
                                tail=load_record_tail)
         out["summary"].update(laps=laps, ksteps=ksteps, epoch=epoch, slabs=slabs)
+        return out
+
+    # ------------------------------------------------------- FP8 load sweep
+    def f8load_parts(self) -> list[str]:
+        """Part names of the FP8 load sweep; the index is the part's bit."""
+        return self._part_names(F8LOAD_SWEEP)
+
+    def f8load_operands(self, seed: int = F8LOAD_SEED, set_: int = 0, ksteps: int = F8LOAD_KSTEPS):
+        """One operand set as the MFMA sees it, computed on the host: (A uint8
+        [128, 64 ksteps], Bt uint8 [256, 64 ksteps], both e4m3 with k
+        contiguous; sa float32 [128], sb float32 [256], the rows' scales). No
+        device call."""
+        import numpy as np
+
+        k = 64 * max(int(ksteps), 0)
+        a, bt = np.zeros((F8LOAD_TILE[0], k), np.uint8), np.zeros((F8LOAD_TILE[1], k), np.uint8)
+        sa, sb = np.zeros(F8LOAD_TILE[0], np.float32), np.zeros(F8LOAD_TILE[1], np.float32)
+        self._call("f8load_sweep", "f8load_operands", seed, set_, ksteps, a.ctypes.data, bt.ctypes.data,
+                   sa.ctypes.data, sb.ctypes.data)
+        return a, bt, sa, sb
+
+    def f8load_probe(self, dev: int, parts=None, seed: int = F8LOAD_SEED, laps: int = 1, ksteps: int = F8LOAD_KSTEPS,
+                     slots: int = 1) -> dict:
+        """k_f8load_probe: one workgroup of 512 threads runs `laps` laps at any
+        shape over 16 sets and stores what it holds: {"gemm": float32 [laps,
+        128, 256], C of every lap; "store": uint32 [laps, 128, 128], the bf16
+        pairs the read-back of each lap's tile returned from the ring;
+        "operand": uint32 [512], every thread's fold}. `parts` selects whether
+        the fold is issued (the pipeline always runs)."""
+        import numpy as np
+
+        mask = self._part_mask(F8LOAD_SWEEP, parts)
+        n, c = max(int(laps), 0), F8LOAD_TILE[0] * F8LOAD_TILE[1]
+        out = np.zeros(n * (c + c // 2) + F8LOAD_BLOCK, np.uint32)
+        self._call("f8load_sweep", "f8load_probe", dev, mask, seed, laps, ksteps, slots, out.ctypes.data, out.size,
+                   wording=F8LOAD_WORDING)
+        return {"gemm": out[:n * c].view(np.float32).reshape(n, *F8LOAD_TILE),
+                "store": out[n * c:n * (c + c // 2)].reshape(n, F8LOAD_TILE[0], F8LOAD_TILE[1] // 2),
+                "operand": out[n * (c + c // 2):]}
+
+    def f8load_sweep_expected(self, parts=None, seed: int = F8LOAD_SEED, laps: int = F8LOAD_LAPS,
+                              ksteps: int = F8LOAD_KSTEPS, slots: int = F8LOAD_SLOTS) -> dict:
+        """The workgroup digest a healthy CU leaves per selected part, computed
+        on the host in plain integers (C 2^8 as int32, the bf16 rounding on
+        the float's bits). ProbeError with rc -1000 when ksteps is above 18: a
+        sum could leave the exact range."""
+        return self._part_expected(F8LOAD_SWEEP, parts, seed, laps, ksteps, slots)
+
+    def f8load_sweep_info(self, dev: int = 0) -> dict:
+        """What the runtime reports for k_f8load_sweep: `num_regs`,
+        `scratch_bytes` per lane, `lds_bytes` per workgroup, `blocks_per_cu`."""
+        return self._sweep_info("f8load_sweep", dev, ("num_regs", "scratch_bytes", "lds_bytes", "blocks_per_cu"))
+
+    def f8load_sweep(self, dev: int = 0, blocks: int = 0, parts=None, seed: int = F8LOAD_SEED,
+                     laps: int = F8LOAD_LAPS, inject: tuple | None = None, max_rounds: int = 4,
+                     ksteps: int = F8LOAD_KSTEPS, slots: int = F8LOAD_SLOTS) -> dict:
+        """k_f8load_sweep: `laps` macro tiles of a checked rowwise-scaled FP8
+        GEMM (128 x 256, K = 64 `ksteps`, bf16 out) on every CU a workgroup
+        lands on, every tile stored to one of `slots` ring slots of 64 KiB per
+        workgroup and read back `slots` laps later; every selected part (None:
+        all) judged. `inject`, `blocks`, `max_rounds`, the ProbeError with rc
+        F8LOAD_UNSWEPT and the result are load_sweep's. Arena (6 MiB) and
+        tables (3 MiB) stay on the device for the life of the process; the
+        ring (blocks x slots x 64 KiB) is allocated per launch and freed after
+        it."""
+        out = self._part_sweep(F8LOAD_SWEEP, summarize_load_sweep, dev, blocks, parts, inject, max_rounds,
+                               (seed, laps, ksteps, slots), {"seed": seed}, wording=F8LOAD_WORDING,
+                               tail=load_record_tail)
+        out["summary"].update(laps=laps, ksteps=ksteps, slots=slots)
         return out
 
     # ----------------------------------------------------------- VALU sweep
